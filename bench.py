@@ -26,7 +26,14 @@ page holds a stripe's k chunks back to back, cache.c:3843; the parity buffer hol
 segment/jerasure.c:1836).  --pad B leaves B unused bytes after every shard row instead;
 layout.padded reports the same stripes with a 1 KiB pad, launch-timed, for the record.
 
-Also reported (same JSON line):
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline needs and no more:
+it sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step,
+config).  --dump-outputs DIR also writes what the last timed step computed, the parity shards and
+the rebuilt shard, to DIR/parity.npy and DIR/rebuilt.npy as float32 (a fixed seeded sample of
+elements when the output is large; the inputs are the same stream on every run, so two builds can
+be compared file for file).
+
+With --full also reported (same JSON line):
   roofline      encode kernel: algorithmic HBM bytes (k+m)*C*N per launch / avg launch time
                 (HIP events on the launch stream) vs 8 TB/s
   per_rank      every rank's own encode / decode launch rates and roofline fractions
@@ -38,7 +45,7 @@ Also reported (same JSON line):
                 per rank, and aggregated as sum of bytes / max time over ranks
   hbm_copy_ref  this box's device-to-device copy rate (the practical HBM ceiling) and the
                 encode / decode kernels' rates relative to it
-Every run checks parity bit-exactly against the reference (oracle/_ref) on sampled stripes.
+Every --full run checks parity bit-exactly against the reference (oracle/_ref) on sampled stripes.
 """
 import argparse
 import glob
@@ -55,6 +62,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK = 8.0e12  # B/s, MI355X HBM3E (MI355X_MICROARCH.md)
 HEADLINE = "erasure encode+decode GiB/s (device-resident), RS(6+3) 1 MiB stripes"
+DUMP_ELEMS = 12 << 20  # --dump-outputs: elements written over all files and ranks (48 MiB as float32)
 
 
 def parse(argv=None):
@@ -83,6 +91,13 @@ def parse(argv=None):
                     help="skip the in-run rocprofv3 PMC traffic passes (roofline.traffic from a committed profile)")
     ap.add_argument("--share-gpus", action="store_true",
                     help="allow more ranks than visible GPUs (a rehearsal: ranks share devices, and the line says so)")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole record: per-kernel roofline with in-run PMC traffic, parity check against the "
+                         "reference, layout A/B, HBM copy references, CPU baseline and host path (the --no-* options "
+                         "trim it); without it only the headline is set up, warmed up, timed and printed")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last step computed (parity and rebuilt shards, a "
+                         "fixed seeded sample when large) to DIR/<name>.npy as float32")
     return ap.parse_args(argv)
 
 
@@ -512,6 +527,31 @@ class HipEngine:
         return ok, ("bit-exact vs oracle/_ref (vendor/jerasure) on stripes %s" % pick if ref else
                     "bit-exact vs the oracle restatement on stripes %s (_ref not built)" % pick)
 
+    def dump_outputs(self, path, N, rank, world):
+        """--dump-outputs: what the last timed step left for its caller, the encode's parity shards
+        [N][m][C] and the decode's rebuilt shard [N][1][C], as float32 .npy files under `path`
+        (one pair per rank at N > 1).  An output of more than its share of DUMP_ELEMS elements is
+        sampled: element indices (into the flattened [N][rows][C] array) drawn with replacement
+        from a fixed seed and sorted, so two builds run with the same arguments write the same
+        elements.  Returns what was written, for the JSON line."""
+        torch = self.torch
+        os.makedirs(path, exist_ok=True)
+        _, par, rebuilt = self.tensors
+        suffix = "" if world == 1 else f"_rank{rank}"
+        written = {}
+        for name, t, share, seed in (("parity", par, 2 * DUMP_ELEMS // 3, 0x70), ("rebuilt", rebuilt, DUMP_ELEMS // 3, 0x72)):
+            n, rows, C = t.shape
+            total, limit = n * rows * C, max(1, share // world)
+            if total <= limit:
+                vals = t.to(torch.float32).cpu().numpy()
+            else:
+                idx = torch.from_numpy(np.sort(np.random.default_rng(seed).integers(0, total, size=limit))).to(self.dev)
+                vals = t[idx // (rows * C), (idx // C) % rows, idx % C].to(torch.float32).cpu().numpy()
+                del idx
+            np.save(os.path.join(path, f"{name}{suffix}.npy"), vals)
+            written[f"{name}{suffix}.npy"] = {"shape": list(vals.shape), "of_elements": total, "sampled": total > limit}
+        return written
+
     def extras(self, N, t_enc, t_dec, rank, world, barrier=None):
         """N = 1 extras on rank 0: the padded layout A/B, the HBM copy probe and the CPU
         reference.  The PCIe-inclusive host path runs on every rank (concurrently at N > 1)."""
@@ -753,6 +793,45 @@ def run_rank(a, rank, world, local, engine_cls=HipEngine):
     if world > 1:
         elapsed = max_over_ranks(elapsed, eng.reduce_device(dist))
 
+    # ---- what the last timed step computed, before anything else runs over these buffers
+    dumped = eng.dump_outputs(a.dump_outputs, N, rank, world) if a.dump_outputs else None
+
+    # ---- the headline: all a plain run reports
+    if a.total_stripes > 0:
+        value = k * C * a.total_stripes * a.steps / elapsed / 2**30
+    else:
+        value = k * C * N * world * a.steps / elapsed / 2**30
+    head = None
+    if rank == 0:
+        method = a.method
+        head = {
+            "metric": HEADLINE if (method, k, m, C) == ("reed_sol_van", 6, 3, 1 << 20) else
+            f"erasure encode+decode GiB/s (device-resident), {method}({k}+{m}) {C} B chunks",
+            "value": round(value, 2),
+            "unit": "GiB/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": round(elapsed / a.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "strong" if a.total_stripes > 0 else "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic: SURVEY §8d splitmix64 stream, seed 0x4C53544F5245, stripe s at word s*k*C/8, resident in HBM",
+            "config": {"workload": f"{method}({k}+{m}) encode + decode(lost shard {a.lost}), C={C} B per shard, "
+                                   f"{N} stripes/GPU, k*C={k * C} B user data per stripe",
+                       "method": method, "k": k, "m": m, "chunk_bytes": C, "packet_size": eng.P,
+                       "stripes_per_gpu": N, "lost_shard": a.lost, "shard_pad_bytes": a.pad,
+                       "parallelism": f"static stripe partition x{world}" + (
+                           f" (rehearsal: {world} ranks on {len({_dev_key(d) for d in idents})} GPU(s), --share-gpus)"
+                           if dup else "")},
+            "distinct_gpus": None if ident is None else len({_dev_key(d) for d in idents}),
+        }
+        if dumped is not None:
+            head["dump_outputs"] = dumped
+    if not a.full:
+        return _finish(a, eng, world, head)
+
     # ---- per-kernel timing on the launch stream (roofline), on every rank
     reps = max(3, min(10, a.steps))
     t_enc, t_dec = eng.launch_times(encode, decode, reps)
@@ -793,38 +872,12 @@ def run_rank(a, rank, world, local, engine_cls=HipEngine):
             host = dict(host, aggregate=agg)
         host.pop("times", None)
         host["pinned"].pop("times", None)
-    if a.total_stripes > 0:
-        value = k * C * a.total_stripes * a.steps / elapsed / 2**30
-    else:
-        value = data_bytes * world * a.steps / elapsed / 2**30
     achieved = enc_hbm / t_enc
     traffic, traffic_src = eng.traffic(N)
 
     out = None
     if rank == 0:
-        method = a.method
-        out = {
-            "metric": HEADLINE if (method, k, m, C) == ("reed_sol_van", 6, 3, 1 << 20) else
-            f"erasure encode+decode GiB/s (device-resident), {method}({k}+{m}) {C} B chunks",
-            "value": round(value, 2),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": round(elapsed / a.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "strong" if a.total_stripes > 0 else "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic: SURVEY §8d splitmix64 stream, seed 0x4C53544F5245, stripe s at word s*k*C/8, resident in HBM",
-            "config": {"workload": f"{method}({k}+{m}) encode + decode(lost shard {a.lost}), C={C} B per shard, "
-                                   f"{N} stripes/GPU, k*C={k * C} B user data per stripe",
-                       "method": method, "k": k, "m": m, "chunk_bytes": C, "packet_size": eng.P,
-                       "stripes_per_gpu": N, "lost_shard": a.lost, "shard_pad_bytes": a.pad,
-                       "parallelism": f"static stripe partition x{world}" + (
-                           f" (rehearsal: {world} ranks on {len({_dev_key(d) for d in idents})} GPU(s), --share-gpus)"
-                           if dup else "")},
-            "distinct_gpus": None if ident is None else len({_dev_key(d) for d in idents}),
+        out = dict(head, **{
             "encode_gibps": round(data_bytes / t_enc / 2**30, 2),
             "decode_gibps": round(data_bytes / t_dec / 2**30, 2),
             "roofline": {"bound": "hbm", "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK / 1e9,
@@ -840,13 +893,22 @@ def run_rank(a, rank, world, local, engine_cls=HipEngine):
             "cpu_baseline": extras.get("cpu_baseline"),
             "host_path": host,
             "parity_check": parity_note,
-        }
+        })
+    return _finish(a, eng, world, out)
+
+
+def _finish(a, eng, world, out):
+    """rank 0 prints its JSON line (and writes --json-out); every rank leaves the group and closes
+    its engine.  Returns the line's dict (None on other ranks)."""
+    if out is not None:
         line = json.dumps(out)
         print(line, flush=True)
         if a.json_out:
             with open(a.json_out, "w") as f:
                 f.write(line + "\n")
     if world > 1:
+        import torch.distributed as dist
+
         dist.barrier()
         dist.destroy_process_group()
     eng.close()
@@ -937,7 +999,7 @@ def main():
     rc = preflight(a)
     if rc:
         sys.exit(rc)
-    if not a.no_pmc and os.environ.get("RANK", "0") == "0":
+    if a.full and not a.no_pmc and os.environ.get("RANK", "0") == "0":
         # before this process touches the GPU (before it spawns ranks, or, under a launcher, on
         # rank 0 before it joins the others): the counter passes run rank 0's geometry as a
         # single-rank child under rocprofv3, on rank 0's GPU

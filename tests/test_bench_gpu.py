@@ -17,7 +17,7 @@ def test_bench_self_launches_two_ranks(cuda, tmp_path):
     env = dict(os.environ, LSEC_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "-u", "bench.py", "--gpus", "2", "--stripes", "64", "--steps", "3", "--warmup", "1",
-                        "--no-cpu", "--no-host-path", "--share-gpus", "--json-out", str(out)],
+                        "--full", "--no-cpu", "--no-host-path", "--share-gpus", "--json-out", str(out)],
                        cwd=ROOT, env=env, timeout=240, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads(out.read_text())
@@ -49,3 +49,40 @@ def test_bench_refuses_mismatched_world_size(tmp_path):
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--stripes", "8"], cwd=ROOT, env=env, timeout=120,
                        capture_output=True, text=True)
     assert r.returncode == 2 and "WORLD_SIZE=2" in r.stdout
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("limit", [None, 3000])
+def test_dump_outputs_are_the_last_steps_shards(cuda, tmp_path, monkeypatch, limit):
+    """--dump-outputs writes the timed path's parity and rebuilt shards as float32: whole when they
+    fit, else the elements a fixed seed picks; the same arguments give the same files, and every
+    value written is the reference's (CPU oracle over the same splitmix64 stripes)."""
+    import numpy as np
+
+    import bench
+    import oracle as O
+    from patterns import stripe
+
+    monkeypatch.setenv("LSEC_NUMA", "0")  # leave the test process's CPU affinity alone
+    if limit:
+        monkeypatch.setattr(bench, "DUMP_ELEMS", limit)
+    k, m, C, N = 6, 3, 8192, 5
+    got = []
+    for d in ("a", "b"):
+        a = bench.parse(["--stripes", str(N), "--chunk", str(C), "--steps", "2", "--warmup", "1",
+                         "--dump-outputs", str(tmp_path / d)])
+        line = bench.run_rank(a, 0, 1, 0)
+        assert sorted(line["dump_outputs"]) == ["parity.npy", "rebuilt.npy"] and "roofline" not in line
+        got.append({n: np.load(tmp_path / d / n) for n in line["dump_outputs"]})
+        assert all(v.dtype == np.float32 for v in got[-1].values())
+    for n in got[0]:
+        assert np.array_equal(got[0][n], got[1][n])
+    data = np.stack([stripe(k, C, s) for s in range(N)])
+    want = {"parity.npy": np.stack([O.encode(O.REED_SOL_VAN, data[s], m) for s in range(N)]),
+            "rebuilt.npy": data[:, :1]}
+    for n, (share, seed) in {"parity.npy": (2, 0x70), "rebuilt.npy": (1, 0x72)}.items():
+        ref = want[n].astype(np.float32)
+        if limit:
+            idx = np.sort(np.random.default_rng(seed).integers(0, ref.size, size=share * limit // 3))
+            ref = ref.reshape(-1)[idx]
+        assert got[0][n].shape == ref.shape and np.array_equal(got[0][n], ref), n

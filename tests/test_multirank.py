@@ -128,7 +128,7 @@ class OracleEngine:
 
 
 def _args(*extra):
-    return bench.parse(["--chunk", "4096", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-host-path",
+    return bench.parse(["--full", "--chunk", "4096", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-host-path",
                         "--no-layout-ab", "--no-copy-ref", *extra])
 
 
@@ -182,7 +182,7 @@ def test_host_path_on_every_rank_with_aggregate(built, tmp_path, monkeypatch):
     and rank 0 reports per-rank rates and the aggregate (sum of bytes / slowest rank's time)."""
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     out = tmp_path / "line.json"
-    args = bench.parse(["--chunk", "4096", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-layout-ab",
+    args = bench.parse(["--full", "--chunk", "4096", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-layout-ab",
                         "--no-copy-ref", "--gpus", "2", "--stripes", "2", "--json-out", str(out)])
     assert bench.launch(args, OracleEngine) == 0
     line = json.loads(out.read_text())
@@ -289,3 +289,22 @@ def test_usable_cpus_reports_quota_and_visible():
     assert 1 <= threads <= visible
     if quota:
         assert threads <= quota
+
+
+def test_plain_run_times_and_prints_only_the_headline(built, tmp_path, monkeypatch):
+    """Without --full a run is set-up, warm-up, the timed steps and the line: no per-kernel timing,
+    no parity check against the reference (OracleEngine.check would write its dump), no extras."""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setenv("LSEC_TEST_DUMP", str(tmp_path))
+    calls = []
+    monkeypatch.setattr(OracleEngine, "launch_times", lambda *a, **kw: calls.append("launch_times"))
+    monkeypatch.setattr(OracleEngine, "extras", lambda *a, **kw: calls.append("extras"))
+    out = tmp_path / "line.json"
+    args = bench.parse(["--chunk", "4096", "--steps", "3", "--warmup", "1", "--stripes", "2", "--json-out", str(out)])
+    assert not args.full and bench.launch(args, OracleEngine) == 0
+    line = json.loads(out.read_text())
+    assert line["metric"].startswith("erasure encode+decode GiB/s") and line["unit"] == "GiB/s"
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert line["dtype"] == "u8" and line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert not {"roofline", "per_rank", "parity_check", "cpu_baseline", "host_path", "layout", "hbm_copy_ref"} & set(line)
+    assert calls == [] and not list(tmp_path.glob("rank*.json"))

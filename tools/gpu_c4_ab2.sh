@@ -11,7 +11,7 @@ done
 echo ok sweep
 for v in "on X=1" "off LSEC_DMA_2D=0"; do
   set -- $v
-  env $2 LSEC_TRACE=1 timeout -k 10 300 python bench.py --method cauchy_good --k 10 --m 4 --chunk 4194304 --total-stripes 2048 --gpus 2 --share-gpus \
+  env $2 LSEC_TRACE=1 timeout -k 10 300 python bench.py --full --method cauchy_good --k 10 --m 4 --chunk 4194304 --total-stripes 2048 --gpus 2 --share-gpus \
     --steps 5 --no-pmc --json-out $O/c4_$1.json > $O/c4_$1.log 2>&1 || { tail -5 $O/c4_$1.log; exit 1; }
 done
 echo ok ranks

@@ -7,7 +7,7 @@ python tools/rocpd_stats.py gpurun_out/prof_x/run_kernel_trace.csv [out.csv] [--
 python tools/rocpd_stats.py gpurun_out/prof_x/run_results.db out.csv --first=33
 
 --first=N splits each (kernel, grid) group by launch order into its first N launches and the
-rest (column Phase: "first<N>" / "rest").  For a default bench.py run N = 33 separates the
+rest (column Phase: "first<N>" / "rest").  For a default bench.py --full run N = 33 separates the
 padded-layout launches (3 warm-up + 20 steps + 10 HIP-event reps) from the unpadded
 re-timing (1 + 10), so the "first" row compares directly with roofline.avg_launch_ms.
 
