@@ -93,7 +93,7 @@ int et_decode(lio_erasure_plan_t *plan, long long int fsize, const char *fname, 
 
 /* ===================================================================== Part 2: extensions */
 
-#define LSEC_ABI_VERSION 2
+#define LSEC_ABI_VERSION 3   /* 3: + lsec_decode_dev_patterns, lsec_decode_dev_rotated (additive) */
 
 /* Stripe-batched host-memory calls.  ptrs holds nstripes*(k+m) pointers laid out exactly
  * like segjerase_write_func's ptr[] array (segment/jerasure.c:1647, :1812-1836): stripe s
@@ -115,6 +115,46 @@ int lsec_encode_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int ns
                     long long block_size, void *stream);
 int lsec_decode_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
                     long long block_size, const int *erasures, void *stream);
+
+/* Stripes that do not share an erasure pattern, one launch.  `patterns` holds npatterns
+ * erasure lists back to back, each -1 terminated as decode_block takes them; an empty list
+ * (just -1) is valid: nothing to rebuild.  stripe_pattern (device memory, nstripes bytes)
+ * gives each stripe's index into them.  Shards are logical chunks, as for lsec_decode_dev.
+ *
+ * - The bytes written are exactly what lsec_decode_dev writes for that stripe with that
+ *   pattern.  Only the erased slots of each stripe are written; survivors are only read.  A
+ *   stripe whose pattern is empty is neither read nor written.
+ * - A RAID4 pattern that loses only the parity counts as empty (raid4.c:48, as lsec_decode_dev).
+ * - A stripe_pattern value >= npatterns makes that stripe behave as the empty pattern; the
+ *   kernel never indexes past its tables.
+ * - Patterns of one call may have different erasure counts, from 0 to m.
+ * - 1 <= npatterns <= 256.
+ * - nstripes == 0 validates the arguments and builds, uploads and caches the call's device
+ *   tables (stripe_pattern may then be NULL), so a caller can prepare ahead; the tables are
+ *   cached on the plan per device, keyed by the pattern lists in their order, until the plan is
+ *   destroyed, and a repeated call does no matrix work and no upload.
+ * - Plans: lsec_plan_kernel 1 (bytewise GF(2^8): RS, r6, raid4) and 2 (bit-sliced GF(2^8):
+ *   Cauchy at w = 8).  Further limits: k <= 64, k + m <= 128, at most 8 erasures per pattern.
+ * - Anything outside these limits -- plan kernels 3-5, wider stripes, an id out of range, more
+ *   than m erasures, a NULL pointer -- returns -1 with a message for lsec_last_error that names
+ *   the limit.  There is no fallback and no partial work.
+ * - Alignment and block_size rules are those of lsec_decode_dev.
+ * Enqueued on `stream`; returns without synchronising.  0 / -1. */
+int lsec_decode_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
+                             long long block_size, const int *patterns, int npatterns,
+                             const unsigned char *stripe_pattern, void *stream);
+
+/* Degraded read of a rotated LUN.  devs[i] (i < k+m) is PHYSICAL device i: it holds, for
+ * stripe s, logical chunk (i + (first_stripe + s) * n_shift) mod (k+m)  (lun.c:1178-1223).
+ * `lost` lists unreadable physical devices (-1 terminated, at most m); their entries in devs
+ * point at the memory that receives the rebuilt chunks.  Each stripe is decoded with the
+ * pattern its rotation gives (the lost devices' logical chunks), under the semantics and limits
+ * of lsec_decode_dev_patterns; n_shift < 0 and first_stripe < 0 return -1.  The tables are
+ * cached by (lost, n_shift mod (k+m)) and do not depend on first_stripe; nstripes == 0
+ * prepares them.  Enqueued on `stream`; returns without synchronising.  0 / -1. */
+int lsec_decode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                            long long block_size, const int *lost, int n_shift,
+                            long long first_stripe, void *stream);
 
 /* Per-stripe "magic": the 4-byte little-endian zlib adler32 over the concatenation of a
  * stripe's k+m chunks that LStore's erasure segment stores in front of every chunk

@@ -74,6 +74,22 @@ struct DecodeEntry {
   std::vector<uint32_t> wrows;          // wordwise: the e x k GF(2^w) decode rows (XOR networks)
 };
 
+// The table of a per-stripe-pattern call shape (lsec_decode_dev_patterns / _rotated): one record
+// per pattern and one CoefCell[rmax][k] image per pattern with something to rebuild (ec_kernels.h,
+// PatRecord), as the host built them and as uploaded per device.
+struct PatternTable {
+  std::vector<int> key;  // 0, then each pattern's sorted ids and a -1, in the caller's order; or 1, n_shift mod n, the sorted lost devices
+  int rmax = 0;          // the largest erasure count: rows of every image, 0 when every pattern is empty
+  std::vector<lsec::PatRecord> recs;
+  std::vector<CoefCell> cells;
+  std::vector<char> reachable;  // rotated: 0 for a rotation (first_stripe + s) * n_shift mod n never takes
+  struct Dev {
+    lsec::PatRecord *recs = nullptr;
+    CoefCell *cells = nullptr;
+  };
+  std::map<int, Dev> dev;  // device -> uploaded table
+};
+
 constexpr int kFastDevs = 16;  // devices whose encode image pointer is cached lock-free
 
 struct PlanImpl {
@@ -98,6 +114,7 @@ struct PlanImpl {
                                                          // wordwise: m x k x w products
   std::map<int, uint32_t *> enc_dev_masks;
   std::map<std::vector<int>, DecodeEntry> decode_cache;  // sorted erased ids -> entry
+  std::map<std::vector<int>, PatternTable> pattern_cache;  // PatternTable::key -> table (kept until the plan is destroyed)
 };
 
 // The public struct must stay first: callers only ever see &PlanExt::pub, and
@@ -128,6 +145,13 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
                   long long size, int packet, hipStream_t st, int w = 8);
 int encode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, hipStream_t st);
 int decode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *erasures, hipStream_t st);
+// stripes that do not share an erasure pattern, one launch per 32-bit range of tiles
+int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift, PatternTable &tab);
+uint32_t pattern_rot0(int n, int n_shift, long long first_stripe);
+int decode_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
+                        const unsigned char *stripe_pattern, hipStream_t st);
+int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
+                       long long first_stripe, hipStream_t st);
 void fp_encode_block(lio_erasure_plan_t *p, char **ptr, int block_size);         // ec_route.cpp
 int fp_dummy(lio_erasure_plan_t *);                                            // ec_route.cpp
 int encode_stripes_impl(PlanExt *e, char **ptrs, int nstripes, long long C);  // ec_route.cpp

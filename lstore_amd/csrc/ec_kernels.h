@@ -114,6 +114,48 @@ struct ApplyArgs {
   ShardRef out[kMaxR];
 };
 
+// Per-stripe erasure patterns (lsec_decode_dev_patterns / _rotated): one launch decodes stripes
+// that do not share an erasure pattern.  A tile belongs to one stripe; the kernel looks the
+// stripe's pattern up once per tile and takes the matrix, the input shards and the output shards
+// from that pattern's record.  The table (records + one CoefCell[Rmax][K] image per pattern, Rmax
+// the largest erasure count of the table, rows past a pattern's own count zero cells) lives in
+// device memory and is read through the constant address space; the shard refs travel in the
+// kernel arguments, indexed by the record's selection lists.
+constexpr int kPatMaxOut = 8;        // erasures per pattern
+constexpr int kPatMaxShards = 128;   // k + m of a patterned call (the shard refs are kernel arguments)
+constexpr int kPatMaxPatterns = 256; // patterns per table (stripe_pattern holds bytes)
+
+struct alignas(64) PatRecord {
+  uint32_t nout;               // erasure count; 0: the stripe is neither read nor written
+  uint32_t cells_off;          // first cell of the pattern's CoefCell[Rmax][K] image in PatternArgs::cells
+  uint32_t pad[2];
+  uint32_t in_sel[kMaxK];      // PatternArgs::sh index of input j (the pattern's j-th survivor)
+  uint32_t out_sel[kPatMaxOut];  // PatternArgs::sh index of output r (its r-th erased chunk)
+};
+static_assert(sizeof(PatRecord) == 320, "PatRecord layout");
+
+// An argument struct of its own: ApplyArgs, which every other launch passes by value, stays as it is.
+struct PatternArgs {
+  const PatRecord *recs;       // npat records (device memory)
+  const CoefCell *cells;       // the patterns' images (device memory)
+  const uint8_t *stripe_pattern;  // nstripes pattern ids (device memory), or null: the rotation below
+  uint32_t npat;               // records in the table; a stripe whose id is >= npat is left alone
+  uint32_t rot0, rot_step, rot_n;  // stripe_pattern null: stripe s has pattern (rot0 + s * rot_step) mod rot_n
+  int K;
+  int nstripes;
+  int packet;                  // bit-sliced: packet size P (bytes)
+  int nshards;                 // entries of sh in use
+  int64_t size;                // bytes per shard (chunk C)
+  unsigned *tiles;             // as ApplyArgs
+  uint32_t tiles_pre;
+  uint32_t tile_phase;
+  ShardRef sh[kPatMaxShards];  // the call's shards
+};
+
+// rmax = the table's largest erasure count (1..kPatMaxOut): the kernel's output rows
+hipError_t launch_pattern_bytewise(const PatternArgs &a, int rmax, hipStream_t stream);
+hipError_t launch_pattern_bitsliced(const PatternArgs &a, int rmax, hipStream_t stream);
+
 // Work-sharing tiles.  The streaming kernels deal each XCD a contiguous eighth of the tiles
 // (xcd_remap), but the XCDs do not run at one rate: on the headline's memory shape the odd ones
 // take ~15 % longer per tile, every launch, so the even ones idle for the last 6-8 % of it

@@ -363,6 +363,37 @@ hipError_t launch_gfw_bitsliced(const ApplyArgs &a, hipStream_t st, int grid_blo
   return by_r(a.R, [&](auto r) { return dispatch_gfw_bitsliced<decltype(r)::value>(a, st, grid); });
 }
 
+namespace {
+bool pattern_args_ok(const PatternArgs &a, int rmax) {
+  return a.K >= 1 && a.K <= kMaxK && rmax >= 1 && rmax <= kPatMaxOut && a.recs && a.cells && a.npat >= 1 &&
+         a.npat <= kPatMaxPatterns && a.nshards >= 1 && a.nshards <= kPatMaxShards && a.size % 8 == 0 &&
+         (a.stripe_pattern || (a.rot_n >= 1 && a.rot0 < a.rot_n && a.rot_step < a.rot_n && a.rot_n <= a.npat));
+}
+}  // namespace
+
+hipError_t launch_pattern_bytewise(const PatternArgs &a, int rmax, hipStream_t st) {
+  if (!pattern_args_ok(a, rmax)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int shape = pat_shape(a.K, rmax);
+  const uint64_t tile = static_cast<uint64_t>(kBlock) * 4 * bw_shape_vw(shape) * bw_shape_it(shape);
+  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
+  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
+  const int grid = default_grid(ntiles);
+  return by_r(rmax, [&](auto r) { return dispatch_pat_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_pattern_bitsliced(const PatternArgs &a, int rmax, hipStream_t st) {
+  if (!pattern_args_ok(a, rmax) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const uint64_t col_bytes = a.size / 8;
+  const uint64_t tile = kBlock * 4ull;
+  const uint64_t ntiles = ((col_bytes + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
+  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
+  const int grid = default_grid(ntiles);
+  return by_r(rmax, [&](auto r) { return dispatch_pat_bitsliced<decltype(r)::value>(a, st, grid); });
+}
+
 // ------------------------------------------------------------------ stripe magic (adler32)
 namespace {
 

@@ -1200,6 +1200,285 @@ hipError_t dispatch_gfw_bitsliced(const ApplyArgs &a, hipStream_t st, int grid) 
   }
 }
 
+// ------------------------------------------------------------------ per-stripe erasure patterns
+// Decodes of stripes that do not share an erasure pattern, in one launch (ec_kernels.h,
+// PatternArgs).  The arithmetic is that of k_gf8_bytewise / k_gf8_bitsliced; what differs is
+// where a tile takes its matrix and its shards from: its stripe's pattern record, looked up once
+// per tile.  Everything the lookup yields is wave-uniform (the tile index is, the pattern id is
+// made so, the record and the cells come through the constant address space), so the selection
+// costs scalar loads only.  R is the table's largest erasure count: a pattern with fewer
+// erasures has zero cells in its remaining rows and its stores stop at its own count.
+typedef const __attribute__((address_space(4))) PatRecord ConstRec;
+
+// the pattern id of stripe s (s uniform over the workgroup)
+__device__ __forceinline__ uint32_t stripe_pattern_id(const PatternArgs &a, uint32_t s) {
+  if (a.stripe_pattern)
+    return __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(*gptr<uint8_t>(reinterpret_cast<uint64_t>(a.stripe_pattern) + s)));
+  return (a.rot0 + (s % a.rot_n) * a.rot_step) % a.rot_n;  // rot0, rot_step < rot_n <= kPatMaxShards: 32 bits do
+}
+
+template <typename Kern>
+hipError_t launch_tiled(Kern *k, int grid, hipStream_t st, PatternArgs a) {
+  // `grid` is the tile count here, as in the ApplyArgs form above
+  a.tile_phase = tile_phase_on() && a.nstripes > 0 && grid % a.nstripes == 0 ? static_cast<uint32_t>(grid / a.nstripes / 8) : 0;
+  unsigned *slot = tile_queue_slot(st, static_cast<uint64_t>(grid));
+  a.tiles = nullptr;
+  a.tiles_pre = 0;
+  if (slot) {
+    const int pg = persistent_grid(reinterpret_cast<const void *>(k), grid, st);
+    if (pg > 0) {
+      a.tiles = slot;
+      a.tiles_pre = tiles_prefix(static_cast<uint32_t>(grid));
+      grid = static_cast<int>(8 * a.tiles_pre) + pg;
+    }
+  }
+  const hipError_t e = launch_kernel_shm(k, dim3(grid), dim3(kBlock), occupancy_lds_bytes(a.size), st, a);
+  tile_queue_release(st, slot);
+  return e;
+}
+
+// BF as k_gf8_bytewise: the branch-free coefficient path, or per-cell branches (R = 1).  KC > 0:
+// K fixed at compile time, so a full tile has all its K*IT loads in flight before any arithmetic,
+// as the single-pattern kernel's fixed-K forms have (with four inputs at a time the one-row
+// kernel ran at 0.56 of 8 TB/s against their 0.75: profiles/patterns_kbench_runtime_k.txt).
+// Instantiated for the one-row kernel only (dispatch_pat_bytewise).
+template <int R, int KC, int IT, int VW, bool BF>
+__global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
+  typedef typename VecT<VW>::type V;
+  constexpr int kStep = BwTile<IT, VW>::kStep;
+  constexpr int kTile = BwTile<IT, VW>::kBytes;
+  constexpr int kLane = 4 * VW;
+  const int K = KC ? KC : a.K;
+  const int64_t C = a.size;
+  const uint32_t tiles_per_stripe = static_cast<uint32_t>((C + kTile - 1) / kTile);
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstRec *recs = reinterpret_cast<ConstRec *>(reinterpret_cast<uintptr_t>(a.recs));
+  ConstCell *images = const_cells(a.cells);
+
+  for_tiles<(kTile >= 8192 ? 1 : 8192 / kTile)>(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const uint32_t p = stripe_pattern_id(a, s);
+    if (p >= a.npat) return;  // no such pattern: the stripe is left alone
+    ConstRec *rec = recs + p;
+    const uint32_t nout = rec->nout;
+    if (nout == 0) return;  // nothing to rebuild
+    ConstCell *cells = images + rec->cells_off;
+    const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
+    const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
+
+    V acc[IT][R];
+#pragma unroll
+    for (int it = 0; it < IT; ++it)
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[it][r] = 0u;
+
+    if (full) {
+      if constexpr (KC > 0) {
+        V v[KC][IT];
+#pragma unroll
+        for (int j = 0; j < KC; ++j) {
+          const ShardRef in = a.sh[rec->in_sel[j]];
+          const uint64_t q = in.base + s * in.stride + off0;
+#pragma unroll
+          for (int it = 0; it < IT; ++it) v[j][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
+        }
+        if constexpr (BF) {
+#pragma unroll
+          for (int j = 0; j + 1 < KC; j += 2) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[j], v[j + 1], cells, K, j);
+          if constexpr (KC % 2) bw_accumulate_bf<R, IT, VW, false, false>(acc, v[KC - 1], v[KC - 1], cells, K, KC - 1);
+        } else {
+#pragma unroll
+          for (int j = 0; j < KC; ++j) bw_accumulate<R, IT, VW>(acc, v[j], cells, K, j);
+        }
+      } else {
+        for (int j0 = 0; j0 < K; j0 += 4) {
+          V v[4][IT];
+          const int nj = min(4, K - j0);
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            if (jj < nj) {
+              const ShardRef in = a.sh[rec->in_sel[j0 + jj]];
+              const uint64_t q = in.base + s * in.stride + off0;
+#pragma unroll
+              for (int it = 0; it < IT; ++it) v[jj][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
+            }
+          }
+          if constexpr (BF) {
+            if (nj >= 2) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[0], v[1], cells, K, j0);
+            if (nj == 4) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[2], v[3], cells, K, j0 + 2);
+            if (nj == 1 || nj == 3) bw_accumulate_bf<R, IT, VW, false, false>(acc, v[nj - 1], v[nj - 1], cells, K, j0 + nj - 1);
+          } else {
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+              if (jj < nj) bw_accumulate<R, IT, VW>(acc, v[jj], cells, K, j0 + jj);
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
+          const ShardRef out = a.sh[rec->out_sel[r]];
+          const uint64_t q = out.base + s * out.stride + off0;
+#pragma unroll
+          for (int it = 0; it < IT; ++it) put_nt<false, V>(q + it * kStep, acc[it][r]);
+        }
+      }
+    } else {
+      // ragged last tile: C is a multiple of 8, so a 16-byte lane unit may be half full
+      for (int j = 0; j < K; ++j) {
+        const ShardRef in = a.sh[rec->in_sel[j]];
+        const uint64_t q = in.base + s * in.stride;
+        V v[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+          const int64_t o = off0 + it * kStep;
+          v[it] = 0u;
+          if (o + kLane <= C) {
+            v[it] = *gptr<V>(q + o);
+          } else if (o < C) {
+            const u32x2 h = *gptr<u32x2>(q + o);
+            v[it][0] = h.x;
+            v[it][1] = h.y;
+          }
+        }
+        bw_acc1<R, IT, VW, BF, false>(acc, v, cells, K, j);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (static_cast<uint32_t>(r) < nout) {
+          const ShardRef out = a.sh[rec->out_sel[r]];
+          const uint64_t q = out.base + s * out.stride;
+#pragma unroll
+          for (int it = 0; it < IT; ++it) {
+            const int64_t o = off0 + it * kStep;
+            if (o + kLane <= C) {
+              put<false, V>(q + o, acc[it][r]);
+            } else if (o < C) {
+              u32x2 h;
+              h.x = acc[it][r][0];
+              h.y = acc[it][r][1];
+              put<false, u32x2>(q + o, h);
+            }
+          }
+        }
+      }
+    }
+  }, a.tile_phase);
+}
+
+// k_gf8_bitsliced's lanes (one dword of packet-column space per lane) under a pattern record
+template <int R>
+__global__ __launch_bounds__(kBlock) void k_pat_bitsliced(PatternArgs a) {
+  const int K = a.K;
+  const uint32_t P = static_cast<uint32_t>(a.packet);
+  const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
+  constexpr uint32_t kTile = kBlock * 4;
+  const uint32_t tiles_per_stripe = (col_bytes + kTile - 1) / kTile;
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstRec *recs = reinterpret_cast<ConstRec *>(reinterpret_cast<uintptr_t>(a.recs));
+  ConstCell *images = const_cells(a.cells);
+
+  for_tiles(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const uint32_t p = stripe_pattern_id(a, s);
+    if (p >= a.npat) return;
+    ConstRec *rec = recs + p;
+    const uint32_t nout = rec->nout;
+    if (nout == 0) return;
+    ConstCell *cells = images + rec->cells_off;
+    const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * 4;
+    if (colb >= col_bytes) return;  // lanes past the end of a ragged last tile
+    const uint32_t sp = colb / P;
+    const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+
+    uint32_t acc[R][8];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
+
+    for (int j = 0; j < K; ++j) {
+      const ShardRef in = a.sh[rec->in_sel[j]];
+      const uint64_t q = in.base + s * in.stride + off;
+      uint32_t e[8];
+#pragma unroll
+      for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<uint32_t>(q + x * P));
+      uint32_t c[R];
+      uint32_t cm = 0;  // bits used by any output: no doublings past the highest one
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        c[r] = cells[r * K + j].coef;
+        cm |= c[r];
+      }
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if ((c[r] >> b) & 1u) {
+#pragma unroll
+            for (int x = 0; x < 8; ++x) acc[r][x] ^= e[x];
+          }
+        if ((cm >> (b + 1)) == 0) break;
+        if (b < 7) {  // e <- 2*e in bit-sliced form
+          const uint32_t top = e[7];
+          e[7] = e[6];
+          e[6] = e[5];
+          e[5] = e[4];
+          e[4] = e[3] ^ top;
+          e[3] = e[2] ^ top;
+          e[2] = e[1] ^ top;
+          e[1] = e[0];
+          e[0] = top;
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
+        const ShardRef out = a.sh[rec->out_sel[r]];
+        const uint64_t q = out.base + s * out.stride + off;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) put_nt<false, uint32_t>(q + x * P, acc[r][x]);
+      }
+    }
+  }, a.tile_phase);
+}
+
+// Launch shapes of the patterned bytewise kernel, by the table's row count and K as
+// bytewise_shape picks them for the single-pattern kernel: R == 1 -> 8 B per lane with per-cell
+// branches, K >= 16 -> 16 B per lane, else 2 x 16 B per lane (both branch-free).  The one-row
+// kernel has fixed-K forms for K = 6 and 10; tables of two or more rows run with K at run time:
+// their fixed-K forms, with every input's 2 x 16 B in flight on top of the accumulators, took
+// 186 (K = 6) and 256 (K = 10) VGPRs and measured slower (RS(10+4), three erasures: 17.5 ms
+// against 10.2; profiles/patterns_fixedk_ab.txt).
+inline int pat_shape(int K, int R) { return R == 1 ? 4 : K >= 16 ? 1 : 0; }
+
+template <int R>
+hipError_t dispatch_pat_bytewise(const PatternArgs &a, hipStream_t st, int grid) {
+  if constexpr (R == 1) {
+    if (a.K == 6) return launch_tiled(&k_pat_bytewise<1, 6, 1, 2, false>, grid, st, a);
+    if (a.K == 10) return launch_tiled(&k_pat_bytewise<1, 10, 1, 2, false>, grid, st, a);
+    return launch_tiled(&k_pat_bytewise<1, 0, 1, 2, false>, grid, st, a);
+  } else {
+    if (pat_shape(a.K, R) == 1) return launch_tiled(&k_pat_bytewise<R, 0, 1, 4, true>, grid, st, a);
+    return launch_tiled(&k_pat_bytewise<R, 0, 2, 4, true>, grid, st, a);
+  }
+}
+
+template <int R>
+hipError_t dispatch_pat_bitsliced(const PatternArgs &a, hipStream_t st, int grid) {
+  return launch_tiled(&k_pat_bitsliced<R>, grid, st, a);
+}
+
+// instantiated per R in ec_patterns_inst.hip
+#define LSEC_DECLARE_PAT_R(RR)                                                                  \
+  extern template hipError_t dispatch_pat_bytewise<RR>(const PatternArgs &, hipStream_t, int);  \
+  extern template hipError_t dispatch_pat_bitsliced<RR>(const PatternArgs &, hipStream_t, int);
+#ifndef LSEC_INSTANTIATING_PAT
+LSEC_DECLARE_PAT_R(1) LSEC_DECLARE_PAT_R(2) LSEC_DECLARE_PAT_R(3) LSEC_DECLARE_PAT_R(4)
+LSEC_DECLARE_PAT_R(5) LSEC_DECLARE_PAT_R(6) LSEC_DECLARE_PAT_R(7) LSEC_DECLARE_PAT_R(8)
+#endif
+
 #define LSEC_DECLARE_R(RR)                                                                         \
   extern template hipError_t dispatch_bytewise<RR>(const ApplyArgs &, hipStream_t, int, int);      \
   extern template hipError_t dispatch_bitsliced<RR>(const ApplyArgs &, hipStream_t, int, int);         \

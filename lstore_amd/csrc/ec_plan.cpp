@@ -469,9 +469,10 @@ int decode_entry(PlanExt *e, const std::vector<int> &ids, DecodeEntry **out, con
   return rc;
 }
 
-int decode_entry_locked(PlanExt *e, const std::vector<int> &ids, int dev, DecodeEntry **out, const void **cells) {
+// the pattern's host plan (survivors, erased ids, decode rows / masks): built once, kept in
+// decode_cache; no device is touched
+int decode_host_locked(PlanExt *e, const std::vector<int> &ids, DecodeEntry **out) {
   const int kind = kernel_kind(e->pub.method, e->pub.w);
-  const bool bitm = uses_u32_image(kind);
   auto it = e->impl->decode_cache.find(ids);
   if (it == e->impl->decode_cache.end()) {
     DecodeEntry ent;
@@ -504,7 +505,16 @@ int decode_entry_locked(PlanExt *e, const std::vector<int> &ids, int dev, Decode
     }
     it = e->impl->decode_cache.emplace(ids, std::move(ent)).first;
   }
-  DecodeEntry &ent = it->second;
+  *out = &it->second;
+  return 0;
+}
+
+int decode_entry_locked(PlanExt *e, const std::vector<int> &ids, int dev, DecodeEntry **out, const void **cells) {
+  const int kind = kernel_kind(e->pub.method, e->pub.w);
+  const bool bitm = uses_u32_image(kind);
+  DecodeEntry *host = nullptr;
+  if (decode_host_locked(e, ids, &host)) return -1;
+  DecodeEntry &ent = *host;
   if (bitm && !ent.xor_only) {
     auto dm = ent.dev_masks.find(dev);
     if (dm == ent.dev_masks.end()) {
@@ -715,6 +725,292 @@ int decode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
   return enqueue_apply(decode_kind(e, ent), cells, k, R, in, out, nstripes, C, p->packet_size, st, p->w);
 }
 
+// ---------------------------------------------------------------- per-stripe erasure patterns
+// lsec_decode_dev_patterns / lsec_decode_dev_rotated: one table of pattern records and matrix
+// images (ec_kernels.h, PatRecord) per call shape, built from the per-pattern host plans of
+// decode_cache -- the matrices lsec_decode_dev applies -- and cached per device on the plan.
+std::atomic<int> g_pattern_split{0};  // lsec_test_set_pattern_split: stripes per launch, 0 = the 32-bit tile limit only
+
+// (first_stripe * n_shift) mod n in 64 bits: first_stripe >= 0, n_shift >= 0, n >= 1
+uint32_t pattern_rot0(int n, int n_shift, long long first_stripe) {
+  const unsigned long long un = static_cast<unsigned long long>(n);
+  return static_cast<uint32_t>((static_cast<unsigned long long>(first_stripe) % un) *
+                               (static_cast<unsigned long long>(n_shift) % un) % un);
+}
+
+namespace {
+
+int gcd_int(int a, int b) {
+  while (b) {
+    const int t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+
+// the limits both calls share; every message names its limit
+int pattern_limits(const lio_erasure_plan_t *p) {
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("per-stripe patterns need plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is kernel %d",
+                JE_method[p->method], p->w, kind);
+  if (p->data_strips < 1 || p->data_strips > lsec::kMaxK)
+    return fail("per-stripe patterns: k=%d outside 1..%d", p->data_strips, lsec::kMaxK);
+  if (p->parity_strips < 1 || p->data_strips + p->parity_strips > lsec::kPatMaxShards)
+    return fail("per-stripe patterns: k+m=%d exceeds %d shards per call", p->data_strips + p->parity_strips,
+                lsec::kPatMaxShards);
+  return 0;
+}
+
+// Appends one pattern's record and image rows to the host table.  `ids`: its erased logical ids
+// (sorted, distinct; empty: nothing to rebuild); rot: shard index = (logical id - rot) mod n
+// (0 for the patterned call, whose shards are logical chunks).  Takes the plan's mutex.
+int pattern_record(PlanExt *e, const std::vector<int> &ids, int rot, lsec::PatRecord &rec, lsec::gf8::Mat &rows) {
+  const lio_erasure_plan_t *p = &e->pub;
+  const int k = p->data_strips, n = k + p->parity_strips;
+  std::memset(&rec, 0, sizeof(rec));
+  rows.clear();
+  if (ids.empty()) return 0;
+  if (p->method == RAID4 && ids[0] >= k) return 0;  // raid4.c:48 leaves lost parity alone
+  if (static_cast<int>(ids.size()) > lsec::kPatMaxOut)
+    return fail("per-stripe patterns: %zu erasures in one pattern exceed %d", ids.size(), lsec::kPatMaxOut);
+  DecodeEntry *ent = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(e->impl->mu);
+    if (decode_host_locked(e, ids, &ent)) return -1;
+  }
+  // (entries are never moved or freed before the plan is destroyed: decode_entry)
+  rec.nout = static_cast<uint32_t>(ent->dp.erased.size());
+  for (int j = 0; j < k; ++j) rec.in_sel[j] = static_cast<uint32_t>(((ent->dp.survivors[j] - rot) % n + n) % n);
+  for (uint32_t r = 0; r < rec.nout; ++r) rec.out_sel[r] = static_cast<uint32_t>(((ent->dp.erased[r] - rot) % n + n) % n);
+  rows = ent->dp.rows;
+  return 0;
+}
+
+}  // namespace
+
+// The argument checks of a call shape, and what they yield without any matrix work: the cache key
+// and each entry's erased logical ids.  patterns != null: npatterns -1 terminated lists back to
+// back; else the rotated call's: entry rot (0 <= rot < n) for every rotation (first_stripe + s) *
+// n_shift mod n can take, an empty entry (reachable[rot] = 0) for the others.
+struct PatternLists {
+  std::vector<int> key;                // PatternTable::key
+  std::vector<std::vector<int>> ids;   // erased logical ids per entry (sorted, distinct)
+  std::vector<int> rots;               // shard index = (logical id - rot) mod n
+  std::vector<char> reachable;
+};
+
+int parse_pattern_lists(const lio_erasure_plan_t *p, const int *patterns, int npatterns, const int *lost, int n_shift,
+                        PatternLists &pl) {
+  if (pattern_limits(p)) return -1;
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  if (patterns) {
+    if (npatterns < 1 || npatterns > lsec::kPatMaxPatterns)
+      return fail("per-stripe patterns: npatterns=%d outside 1..%d", npatterns, lsec::kPatMaxPatterns);
+    pl.key.push_back(0);
+    const int *at = patterns;
+    for (int i = 0; i < npatterns; ++i) {
+      std::vector<int> ids;
+      if (parse_erasures(p, at, ids) < 0) return -1;  // id out of range, more than m erasures, ...
+      if (static_cast<int>(ids.size()) > lsec::kPatMaxOut)
+        return fail("per-stripe patterns: %zu erasures in one pattern exceed %d", ids.size(), lsec::kPatMaxOut);
+      while (*at != -1) ++at;
+      ++at;
+      pl.key.insert(pl.key.end(), ids.begin(), ids.end());
+      pl.key.push_back(-1);
+      pl.ids.push_back(std::move(ids));
+      pl.rots.push_back(0);
+      pl.reachable.push_back(1);
+    }
+    return 0;
+  }
+  if (!lost) return fail("lost is NULL");
+  if (n_shift < 0) return fail("n_shift %d is negative", n_shift);
+  std::vector<int> devs;
+  for (int i = 0; lost[i] != -1; ++i) {
+    if (lost[i] < 0 || lost[i] >= n) return fail("lost device %d out of range 0..%d", lost[i], n - 1);
+    if (std::find(devs.begin(), devs.end(), lost[i]) == devs.end()) devs.push_back(lost[i]);
+    if (i > 4 * n) return fail("lost list not terminated");
+  }
+  std::sort(devs.begin(), devs.end());
+  if (static_cast<int>(devs.size()) > m) return fail("%zu lost devices exceed m=%d", devs.size(), m);
+  if (static_cast<int>(devs.size()) > lsec::kPatMaxOut)
+    return fail("per-stripe patterns: %zu lost devices exceed %d", devs.size(), lsec::kPatMaxOut);
+  const int step = n_shift % n;
+  pl.key.push_back(1);
+  pl.key.push_back(step);
+  pl.key.insert(pl.key.end(), devs.begin(), devs.end());
+  const int g = gcd_int(n, step);  // step 0: n, only rotation 0 occurs
+  for (int rot = 0; rot < n; ++rot) {
+    std::vector<int> ids;
+    const bool occurs = rot % g == 0;
+    if (occurs)
+      for (int d : devs) ids.push_back((d + rot) % n);
+    std::sort(ids.begin(), ids.end());
+    pl.ids.push_back(std::move(ids));
+    pl.rots.push_back(rot);
+    pl.reachable.push_back(occurs ? 1 : 0);
+  }
+  return 0;
+}
+
+// The host table of parsed lists: the matrix work.  No device is touched.
+int fill_pattern_table(PlanExt *e, PatternLists &pl, PatternTable &tab) {
+  const int k = e->pub.data_strips;
+  const std::vector<std::vector<int>> &lists = pl.ids;
+  const std::vector<int> &rots = pl.rots;
+  tab.key = std::move(pl.key);
+  tab.reachable = std::move(pl.reachable);
+  if (ensure_coding(e)) return -1;
+  const size_t np = lists.size();
+  std::vector<lsec::gf8::Mat> rows(np);
+  tab.recs.assign(np, lsec::PatRecord());
+  tab.rmax = 0;
+  for (size_t i = 0; i < np; ++i) {
+    if (pattern_record(e, lists[i], rots[i], tab.recs[i], rows[i])) return -1;
+    tab.rmax = std::max(tab.rmax, static_cast<int>(tab.recs[i].nout));
+  }
+  // one CoefCell[rmax][k] image per entry with something to rebuild; rows past its count are zero cells
+  tab.cells.clear();
+  CoefCell zero;
+  lsec::make_cell(0, zero);
+  for (size_t i = 0; i < np; ++i) {
+    if (tab.recs[i].nout == 0) continue;
+    std::vector<CoefCell> h;
+    host_cells(rows[i], static_cast<int>(tab.recs[i].nout), k, h);
+    tab.recs[i].cells_off = static_cast<uint32_t>(tab.cells.size());
+    tab.cells.insert(tab.cells.end(), h.begin(), h.end());
+    tab.cells.resize(tab.cells.size() + static_cast<size_t>(tab.rmax - static_cast<int>(tab.recs[i].nout)) * k, zero);
+  }
+  if (tab.cells.empty()) tab.cells.push_back(zero);  // every entry empty: the kernel reads none of it
+  return 0;
+}
+
+int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift, PatternTable &tab) {
+  PatternLists pl;
+  if (parse_pattern_lists(&e->pub, patterns, npatterns, lost, n_shift, pl)) return -1;
+  return fill_pattern_table(e, pl, tab);
+}
+
+namespace {
+
+int upload_records(const std::vector<lsec::PatRecord> &h, lsec::PatRecord **out) {
+  lsec::PatRecord *d = nullptr;
+  HIP_OK(hipMalloc(&d, sizeof(lsec::PatRecord) * h.size()));
+  hipError_t err = hipMemcpy(d, h.data(), sizeof(lsec::PatRecord) * h.size(), hipMemcpyHostToDevice);
+  if (err != hipSuccess) {
+    (void)hipFree(d);
+    return fail("hipMemcpy(pattern records): %s", hipGetErrorString(err));
+  }
+  *out = d;
+  return 0;
+}
+
+// the call shape's table on the current device: cached on the plan, built and uploaded once
+int pattern_table_dev(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift,
+                      const PatternTable **out_tab, PatternTable::Dev *out_dev) {
+  PatternLists pl;
+  if (parse_pattern_lists(&e->pub, patterns, npatterns, lost, n_shift, pl)) return -1;  // every argument check, before any HIP call
+  int dev = 0;
+  HIP_OK(hipGetDevice(&dev));
+  {
+    std::lock_guard<std::mutex> lk(e->impl->mu);
+    auto it = e->impl->pattern_cache.find(pl.key);
+    if (it != e->impl->pattern_cache.end()) {
+      auto d = it->second.dev.find(dev);
+      if (d != it->second.dev.end()) {  // the repeated call: no matrix work, no upload
+        *out_tab = &it->second;
+        *out_dev = d->second;
+        return 0;
+      }
+    }
+  }
+  PatternTable fresh;
+  if (fill_pattern_table(e, pl, fresh)) return -1;  // (takes the plan's mutex per pattern)
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  // (map nodes never move and live until the plan is destroyed, as decode_cache's)
+  PatternTable &tab = e->impl->pattern_cache.emplace(fresh.key, std::move(fresh)).first->second;
+  auto d = tab.dev.find(dev);
+  if (d == tab.dev.end()) {
+    PatternTable::Dev nd;
+    if (upload_records(tab.recs, &nd.recs)) return -1;
+    if (upload_cells(tab.cells, &nd.cells)) {
+      (void)hipFree(nd.recs);
+      return -1;
+    }
+    d = tab.dev.emplace(dev, nd).first;
+  }
+  *out_tab = &tab;
+  *out_dev = d->second;
+  return 0;
+}
+
+// the launches of a patterned call, split so that tile indices stay 32-bit (as enqueue_apply)
+int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::Dev &dv, const lsec_shard_t *sh, int nstripes,
+                     long long C, const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, hipStream_t st) {
+  const lio_erasure_plan_t *p = &e->pub;
+  const int n = p->data_strips + p->parity_strips;
+  if (nstripes <= 0 || C == 0 || tab.rmax == 0) return 0;  // rmax 0: every pattern is empty
+  lsec::PatternArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.recs = dv.recs;
+  a.cells = dv.cells;
+  a.npat = static_cast<uint32_t>(tab.recs.size());
+  a.K = p->data_strips;
+  a.packet = p->packet_size;
+  a.nshards = n;
+  a.size = C;
+  a.rot_step = rot_step;
+  a.rot_n = stripe_pattern ? 0 : static_cast<uint32_t>(n);
+  const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
+  long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
+  const int split = g_pattern_split.load(std::memory_order_relaxed);
+  if (split > 0) per = std::min<long long>(per, split);
+  for (long long s0 = 0; s0 < nstripes; s0 += per) {
+    a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
+    for (int i = 0; i < n; ++i)
+      a.sh[i] = {reinterpret_cast<uint64_t>(sh[i].base) + static_cast<uint64_t>(s0) * sh[i].stride, sh[i].stride};
+    a.stripe_pattern = stripe_pattern ? stripe_pattern + s0 : nullptr;
+    a.rot0 = stripe_pattern ? 0 : static_cast<uint32_t>((rot0 + (s0 % n) * rot_step) % n);
+    // a Cauchy plan's patterns all take the bit-sliced kernel, 0 / 1 rows too (the same bytes in either layout)
+    const hipError_t err = sliced ? lsec::launch_pattern_bitsliced(a, tab.rmax, st) : lsec::launch_pattern_bytewise(a, tab.rmax, st);
+    if (err != hipSuccess) return fail("pattern kernel launch failed: %s", hipGetErrorString(err));
+  }
+  return 0;
+}
+
+}  // namespace
+
+int decode_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
+                        const unsigned char *stripe_pattern, hipStream_t st) {
+  lio_erasure_plan_t *p = &e->pub;
+  if (!patterns) return fail("patterns is NULL");
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (nstripes > 0 && !stripe_pattern) return fail("stripe_pattern is NULL");
+  if (pattern_limits(p) || check_geometry(p, C)) return -1;
+  const PatternTable *tab = nullptr;
+  PatternTable::Dev dv;
+  if (pattern_table_dev(e, patterns, npatterns, nullptr, 0, &tab, &dv)) return -1;
+  return enqueue_patterns(e, *tab, dv, sh, nstripes, C, stripe_pattern, 0, 0, st);
+}
+
+int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
+                       long long first_stripe, hipStream_t st) {
+  lio_erasure_plan_t *p = &e->pub;
+  if (!lost) return fail("lost is NULL");
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (n_shift < 0) return fail("n_shift %d is negative", n_shift);
+  if (first_stripe < 0) return fail("first_stripe %lld is negative", first_stripe);
+  if (pattern_limits(p) || check_geometry(p, C)) return -1;
+  const PatternTable *tab = nullptr;
+  PatternTable::Dev dv;
+  if (pattern_table_dev(e, nullptr, 0, lost, n_shift, &tab, &dv)) return -1;
+  const int n = p->data_strips + p->parity_strips;
+  return enqueue_patterns(e, *tab, dv, devs, nstripes, C, nullptr, pattern_rot0(n, n_shift, first_stripe),
+                          static_cast<uint32_t>(n_shift % n), st);
+}
+
 }  // namespace eng
 
 using namespace eng;
@@ -849,6 +1145,12 @@ void et_destroy_plan(lio_erasure_plan_t *p) {
         (void)hipFree(kv.second);
       }
     }
+    for (auto &tab : e->impl->pattern_cache)
+      for (auto &kv : tab.second.dev) {
+        (void)hipSetDevice(kv.first);
+        (void)hipFree(kv.second.recs);
+        (void)hipFree(kv.second.cells);
+      }
     if (cur >= 0) (void)hipSetDevice(cur);
     delete e->impl;
     e->magic = 0;
@@ -1133,6 +1435,47 @@ void lsec_test_set_cauchy8_policy(int mode) { g_c8_policy.store(mode == 1 ? 1 : 
 // bit 1 the compiled networks (lsec::tile_phase_on; LSEC_TILE_PHASE sets the start value, 1), for
 // A/B runs in one allocation.
 void lsec_test_set_tile_phase(int mode) { lsec::set_tile_phase(mode); }
+
+// Test hook, not in include/: a patterned call launches at most `stripes` stripes at a time
+// (0, the default: only the 32-bit tile limit splits), so a small batch exercises the split.
+void lsec_test_set_pattern_split(int stripes) { g_pattern_split.store(std::max(0, stripes), std::memory_order_relaxed); }
+
+// Test hook, not in include/ (no GPU): entry pattern_id of the table the host builds for
+// lsec_decode_dev_patterns (patterns != NULL) or lsec_decode_dev_rotated (patterns NULL: lost,
+// n_shift; pattern_id is the rotation).  *nout = its erasure count (-1: a rotation that cannot
+// occur), in_sel[0..k) and out_sel[0..nout) its shard indices, coef[nout * k] its decode rows.
+// 0, or -1 with a message.
+int lsec_test_pattern_table(lio_erasure_plan_t *plan, const int *patterns, int npatterns, const int *lost, int n_shift,
+                            int pattern_id, int *nout, int *in_sel, int *out_sel, int *coef) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!nout || !in_sel || !out_sel || !coef) return fail("lsec_test_pattern_table: NULL output");
+  PatternTable tab;
+  if (build_pattern_table(e, patterns, npatterns, lost, n_shift, tab)) return -1;
+  if (pattern_id < 0 || pattern_id >= static_cast<int>(tab.recs.size()))
+    return fail("lsec_test_pattern_table: entry %d outside 0..%zu", pattern_id, tab.recs.size() - 1);
+  const lsec::PatRecord &rec = tab.recs[pattern_id];
+  const int k = plan->data_strips;
+  *nout = tab.reachable[pattern_id] ? static_cast<int>(rec.nout) : -1;
+  for (int j = 0; j < k; ++j) in_sel[j] = rec.nout ? static_cast<int>(rec.in_sel[j]) : -1;
+  for (uint32_t r = 0; r < rec.nout; ++r) {
+    out_sel[r] = static_cast<int>(rec.out_sel[r]);
+    for (int j = 0; j < k; ++j) coef[r * k + j] = static_cast<int>(tab.cells[rec.cells_off + r * k + j].coef);
+  }
+  // the rows past the entry's own count must be zero cells
+  for (int r = static_cast<int>(rec.nout); rec.nout && r < tab.rmax; ++r)
+    for (int j = 0; j < k; ++j)
+      if (tab.cells[rec.cells_off + static_cast<size_t>(r) * k + j].coef != 0 ||
+          tab.cells[rec.cells_off + static_cast<size_t>(r) * k + j].ta_lo != 0)
+        return fail("lsec_test_pattern_table: entry %d row %d is not zero", pattern_id, r);
+  return 0;
+}
+
+// Test hook, not in include/: the rotation of a rotated call's first stripe, as the call computes it
+int lsec_test_pattern_rot0(int n, int n_shift, long long first_stripe) {
+  if (n < 1 || n_shift < 0 || first_stripe < 0) return fail("lsec_test_pattern_rot0: n >= 1, n_shift >= 0, first_stripe >= 0");
+  return static_cast<int>(pattern_rot0(n, n_shift, first_stripe));
+}
 
 
 // Self-test of the bitmatrix decode planner (test hook, not in include/; no GPU): for the

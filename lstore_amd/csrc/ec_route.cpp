@@ -600,6 +600,23 @@ int lsec_decode_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int ns
   return decode_dev(e, shards, nstripes, block_size, erasures, static_cast<hipStream_t>(stream));
 }
 
+int lsec_decode_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
+                             const int *patterns, int npatterns, const unsigned char *stripe_pattern, void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!shards) return fail("shards is NULL");
+  return decode_dev_patterns(e, shards, nstripes, block_size, patterns, npatterns, stripe_pattern,
+                             static_cast<hipStream_t>(stream));
+}
+
+int lsec_decode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                            const int *lost, int n_shift, long long first_stripe, void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!devs) return fail("devs is NULL");
+  return decode_dev_rotated(e, devs, nstripes, block_size, lost, n_shift, first_stripe, static_cast<hipStream_t>(stream));
+}
+
 int et_encode_stripes_magic(lio_erasure_plan_t *plan, char **ptrs, int nstripes, int block_size, char *magic) {
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");

@@ -80,7 +80,8 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_segment_straddle_bytes", "lsec_segment_read", "lsec_segment_inspect",
            "lsec_prepare_decode", "lsec_abi_version", "lsec_device_count", "lsec_last_error", "lsec_plan_kernel",
            "lsec_set_kernel_variant", "lsec_set_host_devices", "lsec_hbm_copy_dev", "lsec_hbm_mix_dev", "lsec_prepare_encode", "lsec_plan_jit", "lsec_device_numa",
-           "lsec_set_tile_sharing", "lsec_tile_sharing", "lsec_host_unpin_drain", "lsec_hbm_decode_shape_dev")
+           "lsec_set_tile_sharing", "lsec_tile_sharing", "lsec_host_unpin_drain", "lsec_hbm_decode_shape_dev",
+           "lsec_decode_dev_patterns", "lsec_decode_dev_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -133,6 +134,15 @@ def lib():
     L.et_decode_stripes.argtypes = [P, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.lsec_encode_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p]
     L.lsec_decode_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_void_p]
+    L.lsec_decode_dev_patterns.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
+                                           C.c_void_p, C.c_void_p]
+    L.lsec_decode_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
+                                          C.c_longlong, C.c_void_p]
+    L.lsec_test_set_pattern_split.argtypes = [C.c_int]
+    L.lsec_test_set_pattern_split.restype = None
+    L.lsec_test_pattern_table.argtypes = [P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lsec_test_pattern_rot0.argtypes = [C.c_int, C.c_int, C.c_longlong]
     L.lsec_prepare_decode.argtypes = [P, C.POINTER(C.c_int)]
     L.lsec_prepare_encode.argtypes = [P]
     L.lsec_plan_jit.argtypes = [P, C.POINTER(C.c_int)]
@@ -184,6 +194,14 @@ def _check(rc: int, what: str) -> int:
 def _erasure_array(erasures: Iterable[int]):
     vals = list(erasures) + [-1]
     return (C.c_int * len(vals))(*vals)
+
+
+def _pattern_array(patterns):
+    """erasure lists back to back, each -1 terminated (lsec_decode_dev_patterns)"""
+    vals = []
+    for pat in patterns:
+        vals += [int(x) for x in pat] + [-1]
+    return (C.c_int * max(1, len(vals)))(*vals)
 
 
 def nearest_prime(w: int, which: int) -> int:
@@ -502,6 +520,33 @@ class Plan:
                 refs[e] = (out.data_ptr() + r * out.stride(1), out.stride(0))
         self.decode_dev_refs(refs, n, size, erasures, _stream_handle(stream))
 
+    def decode_dev_patterns_refs(self, refs, nstripes: int, block_size: int, patterns, stripe_pattern_ptr: int,
+                                 stream: int = 0) -> None:
+        """lsec_decode_dev_patterns: stripes that do not share an erasure pattern, one launch.
+        patterns: a sequence of erasure lists; stripe_pattern_ptr: device address of nstripes bytes,
+        each stripe's index into patterns (0 / None with nstripes == 0: only prepare the tables)."""
+        patterns = list(patterns)
+        _check(lib().lsec_decode_dev_patterns(self._p, self.shard_refs(refs), nstripes, block_size,
+                                              _pattern_array(patterns), len(patterns), stripe_pattern_ptr or None,
+                                              stream), "lsec_decode_dev_patterns")
+
+    def decode_dev_patterns(self, data, parity, patterns, stripe_pattern, stream=None) -> None:
+        """torch: rebuild, in place, the erased shards of every stripe of data [N,k,C] / parity
+        [N,m,C] under its own pattern; stripe_pattern: uint8 device tensor [N] of indices into patterns."""
+        refs, n, size = self.tensor_refs(data, parity)
+        if stripe_pattern.dtype.itemsize != 1 or not stripe_pattern.is_cuda or not stripe_pattern.is_contiguous() \
+                or stripe_pattern.numel() != n:
+            raise ValueError("stripe_pattern must be a contiguous uint8 device tensor with one entry per stripe")
+        self.decode_dev_patterns_refs(refs, n, size, patterns, stripe_pattern.data_ptr(), _stream_handle(stream))
+
+    def decode_dev_rotated_refs(self, refs, nstripes: int, block_size: int, lost, n_shift: int, first_stripe: int,
+                                stream: int = 0) -> None:
+        """lsec_decode_dev_rotated: degraded read of a rotated LUN.  refs[i] is PHYSICAL device i
+        (stripe s holds logical chunk (i + (first_stripe + s) * n_shift) mod (k+m) there); the refs
+        of the `lost` devices receive the rebuilt chunks."""
+        _check(lib().lsec_decode_dev_rotated(self._p, self.shard_refs(refs), nstripes, block_size, _erasure_array(lost),
+                                             n_shift, first_stripe, stream), "lsec_decode_dev_rotated")
+
     def prepare_decode(self, erasures) -> None:
         _check(lib().lsec_prepare_decode(self._p, _erasure_array(erasures)), "lsec_prepare_decode")
 
@@ -569,6 +614,38 @@ def tile_sharing() -> int:
 
 def set_kernel_variant(bytewise: int = 0, bitsliced: int = 0) -> None:
     lib().lsec_set_kernel_variant(bytewise, bitsliced)
+
+
+def set_pattern_split(stripes: int = 0) -> None:
+    """Test hook: a patterned decode launches at most `stripes` stripes at a time (0: no extra split)."""
+    lib().lsec_test_set_pattern_split(int(stripes))
+
+
+def pattern_rot0(n: int, n_shift: int, first_stripe: int) -> int:
+    """Test hook: (first_stripe * n_shift) mod n as lsec_decode_dev_rotated computes it."""
+    return _check_nonneg(lib().lsec_test_pattern_rot0(n, n_shift, first_stripe), "lsec_test_pattern_rot0")
+
+
+def _check_nonneg(rc: int, what: str) -> int:
+    if rc < 0:
+        raise ErasureError(f"{what} failed (rc={rc}): {last_error()}")
+    return rc
+
+
+def pattern_table_entry(plan: "Plan", pattern_id: int, patterns=None, lost=None, n_shift: int = 0):
+    """Test hook (no GPU): entry pattern_id of the host table of lsec_decode_dev_patterns (patterns
+    given) or lsec_decode_dev_rotated (lost, n_shift; pattern_id is the rotation) ->
+    (nout, in_sel [k], out_sel [nout], rows [nout, k]); nout = -1 for a rotation that cannot occur."""
+    k, n = plan.k, plan.k + plan.m
+    nout = C.c_int(0)
+    in_sel, out_sel, coef = (C.c_int * k)(), (C.c_int * n)(), (C.c_int * (n * k))()
+    pats = None if patterns is None else list(patterns)
+    _check(lib().lsec_test_pattern_table(plan.ptr, None if pats is None else _pattern_array(pats),
+                                         0 if pats is None else len(pats),
+                                         None if lost is None else _erasure_array(lost), n_shift, pattern_id,
+                                         C.byref(nout), in_sel, out_sel, coef), "lsec_test_pattern_table")
+    e = max(0, nout.value)
+    return nout.value, list(in_sel[:k]), list(out_sel[:e]), np.array(coef[:e * k], dtype=np.int32).reshape(e, k)
 
 
 def host_unpin_drain() -> None:

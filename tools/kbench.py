@@ -3,6 +3,10 @@
 
 python tools/kbench.py [--stripes N] [--rounds R] [--configs rs63,cg104,cg63,cg:K:M:C_KiB,...]
 Prints HBM GB/s (algorithmic bytes / launch time, HIP events on the launch stream).
+
+python tools/kbench.py --patterns [--nine] [--rounds R] [--reps N]
+The per-stripe-pattern decodes against the single-pattern decode, interleaved on the same buffers
+(RS(6+3) and Cauchy-good(6+3), C = 1 MiB, 4095 stripes): see patterns_bench.
 """
 import argparse
 import os
@@ -73,6 +77,89 @@ CONFIGS = {
 }
 
 
+def patterns_bench(a):
+    """Degraded decodes four ways, interleaved round by round on the same k+m buffers (one per
+    chunk / device, C = 1 MiB; rebuilt chunks go to scratch buffers, so the inputs stay as they are):
+      (a) lsec_decode_dev, erasures --pattern-lost ([0])    the yardstick: code the patterned calls do not touch
+      (b) lsec_decode_dev_patterns, every stripe on that    (a)'s traffic: isolates the table indirection
+          one pattern
+      (c) lsec_decode_dev_rotated, device 0 lost, n_shift 1 the rotated degraded read: k+m patterns in turn
+      (d) --nine: k+m whole-stage lsec_decode_dev launches, one per rotation: (c)'s cost without the call
+    (a)'s own min-max over the rounds is the margin (b) and (c) are judged by (with the default
+    --pattern-lost; (c) always rebuilds one chunk per stripe).  Results are checked before timing."""
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream()
+    C, N = 1 << 20, a.pattern_stripes
+    lost = sorted({int(x) for x in a.pattern_lost.split(",")})  # (a) and (b): these logical chunks; (c), (d): device 0
+    for name in a.pattern_codes.split(","):
+        meth, k, m = CONFIGS[name][:3]
+        n = k + m
+        plan = L.Plan.for_chunk(meth, k, m, C)
+        bufs = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(n)]
+        outs = [torch.empty((N, C), dtype=torch.uint8, device=dev) for _ in lost]
+        out, out2 = outs[0], torch.empty((N, C), dtype=torch.uint8, device=dev)
+        refs = [(b.data_ptr(), C) for b in bufs]
+        plan.encode_dev_refs(refs, N, C, stream.cuda_stream)  # consistent parity in buffers k..n-1
+        into = lambda o: [(o.data_ptr(), C)] + refs[1:]  # shard / device 0 is the lost one
+        scratch = list(refs)  # the lost chunks' refs point at the scratch outputs
+        for o, e in zip(outs, lost):
+            scratch[e] = (o.data_ptr(), C)
+        ids = torch.zeros(N, dtype=torch.uint8, device=dev)
+        sh = stream.cuda_stream
+        plan.prepare_decode(lost)
+        plan.decode_dev_patterns_refs(refs, 0, C, [lost], 0)
+        plan.decode_dev_rotated_refs(refs, 0, C, [0], 1, 0)
+
+        def nine(o):
+            for rot in range(n):  # logical chunk c of a rotation-rot stripe is on device (c - rot) mod n
+                plan.decode_dev_refs([into(o)[(c - rot) % n] for c in range(n)], N, C, [rot], sh)
+
+        runs = {"a": lambda: plan.decode_dev_refs(scratch, N, C, lost, sh),
+                "b": lambda: plan.decode_dev_patterns_refs(scratch, N, C, [lost], ids.data_ptr(), sh),
+                "c": lambda: plan.decode_dev_rotated_refs(into(out), N, C, [0], 1, 0, sh)}
+        if a.nine:
+            runs["d"] = lambda: nine(out2)
+        # results first: (a) rebuilds the lost chunks, (b) writes the same bytes, (c) equals per-rotation decodes
+        for key in "ab":
+            for o in outs:
+                o.zero_()
+            runs[key]()
+            torch.cuda.synchronize()
+            for o, e in zip(outs, lost):
+                assert torch.equal(o, bufs[e]), f"({key}) did not rebuild chunk {e}"
+        runs["c"]()
+        torch.cuda.synchronize()
+        for rot in range(n):
+            plan.decode_dev_refs([into(out2)[(c - rot) % n] for c in range(n)], N, C, [rot], sh)
+            torch.cuda.synchronize()
+            assert torch.equal(out[rot::n], out2[rot::n]), f"(c) differs from lsec_decode_dev at rotation {rot}"
+        times = {key: [] for key in runs}
+        for _ in range(a.rounds):
+            for key, fn in runs.items():
+                fn()  # warm
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.reps):
+                    fn()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[key].append(e0.elapsed_time(e1) / a.reps)
+        lo, hi = min(times["a"]), max(times["a"])
+        what = {"a": f"lsec_decode_dev {lost}", "b": f"patterns, all stripes {lost}", "c": "rotated, 1 lost, n_shift 1",
+                "d": f"{n} whole-stage lsec_decode_dev"}
+        for key, ts in times.items():
+            med = sorted(ts)[len(ts) // 2]
+            db = (k + (len(lost) if key in "ab" else 1)) * C * N  # bytes the stripes' decodes have to move
+            band = "" if key in "ad" else ("  inside (a)'s band" if lo <= med <= hi else
+                                          f"  {'below' if med < lo else 'above'} (a)'s band by {abs(med - (lo if med < lo else hi)) / med:.2%}")
+            print(f"{name} N={N} C={C} ({key}) {what[key]:34s} median {med:7.3f} ms  min {min(ts):7.3f}  max {max(ts):7.3f}  "
+                  f"{db / med / 1e6:7.1f} GB/s ({db / med / 8e9:5.1%} of 8 TB/s){band}", flush=True)
+        print(f"{name} (a) band: {lo:.3f} .. {hi:.3f} ms ({(hi - lo) / lo:.2%}) over {a.rounds} rounds of {a.reps} launches", flush=True)
+        del bufs, outs, out, out2, ids
+        plan.close()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data-gib", type=float, default=24.0)
@@ -86,7 +173,16 @@ def main():
     ap.add_argument("--lost", default="0", help="erasures of the timed decode, e.g. 0,1,k+1 as ids (default: D0)")
     ap.add_argument("--mix", action="store_true",
                     help="also time lsec_hbm_mix_dev over the same shards: the encode's traffic, XOR only")
+    ap.add_argument("--patterns", action="store_true",
+                    help="time the per-stripe-pattern decodes against lsec_decode_dev (patterns_bench) and exit")
+    ap.add_argument("--nine", action="store_true", help="--patterns: also nine whole-stage lsec_decode_dev launches")
+    ap.add_argument("--pattern-stripes", type=int, default=4095)
+    ap.add_argument("--pattern-codes", default="rs63,cg63", help="--patterns: names from CONFIGS (their k and m; C = 1 MiB)")
+    ap.add_argument("--pattern-lost", default="0", help="--patterns: the erasure list of (a) and (b)")
     a = ap.parse_args()
+    if a.patterns:
+        patterns_bench(a)
+        return
     dev = torch.device("cuda:0")
     variants = [tuple(int(x) for x in v.split(",")) for v in a.variants.split(";")]
     for name in a.configs.split(","):
