@@ -105,7 +105,15 @@ int et_decode_stripes(lio_erasure_plan_t *plan, char **ptrs, int nstripes, int b
  *   (char *)shards[i].base + s * shards[i].stride        (device memory)
  * e.g. LStore's layout: data base = page + i*C, stride = k*C; parity base = par + i*C,
  * stride = m*C.  Work is enqueued on `stream` (a hipStream_t; NULL = legacy default stream)
- * and the call returns without synchronising. */
+ * and the call returns without synchronising.
+ *
+ * Layout rule, the same for every lsec_*_dev entry point that takes a plan: each base and each
+ * stride is a multiple of 8 bytes (as block_size is); nothing more is required -- shards need
+ * be neither 16-byte aligned nor contiguous, and each shard may have a stride of its own.  The
+ * shards of one call must not overlap (a call reads its inputs while it writes its outputs).
+ * A base that is not a multiple of 8, or such a stride with nstripes > 1, returns -1 with a
+ * message naming this rule, and nothing is enqueued.  nstripes == 0 with NULL bases stays
+ * valid (the calls that prepare ahead). */
 typedef struct {
     void *base;
     long long stride;
@@ -138,7 +146,7 @@ int lsec_decode_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int ns
  * - Anything outside these limits -- plan kernels 3-5, wider stripes, an id out of range, more
  *   than m erasures, a NULL pointer -- returns -1 with a message for lsec_last_error that names
  *   the limit.  There is no fallback and no partial work.
- * - Alignment and block_size rules are those of lsec_decode_dev.
+ * - Alignment and block_size rules are those of lsec_decode_dev (lsec_shard_t, above).
  * Enqueued on `stream`; returns without synchronising.  0 / -1. */
 int lsec_decode_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
                              long long block_size, const int *patterns, int npatterns,

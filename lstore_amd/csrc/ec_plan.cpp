@@ -601,8 +601,11 @@ int cauchy8_bitsliced_dw(int K, int R, long long size) {
 // (<= 2 for the bitmatrix kernel) and K into groups of <= lsec::kMaxK inputs.  `image` is the
 // CoefCell[R][K] matrix image, the uint32 row masks [((r*w+l)*K + j)*NW + q] (KBITMATRIX) or the
 // word products [(r*K + j)*w + b] (KWORDWISE / KBITSLICEDW), grouped when K > kMaxK.
+thread_local int tl_apply_path = 0;  // lsec_test_apply_path: what this thread's last enqueue_apply launched
+
 int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in, const ShardRef *out,
                   int nstripes, long long size, int packet, hipStream_t st, int w) {
+  tl_apply_path = 0;
   const bool net = kind == KBYTEWISE   ? lsec::bytewise_variant() == 0 && lsec::jit::wants_xornet(R, K)
                    : kind == KWORDWISE ? lsec::bitsliced_variant() == 0 && lsec::jit::wants_gfw_net(R, K, w)
                                        : false;
@@ -620,6 +623,7 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
         for (int r = 0; r < R; ++r) bo[r] = {out[r].base + static_cast<uint64_t>(s0) * out[r].stride, out[r].stride};
         const hipError_t err = lsec::jit::launch(fn, R, K, bi, bo, n, whole, st, kind == KWORDWISE ? w : 8);
         if (err != hipSuccess) return fail("xor network launch failed: %s", hipGetErrorString(err));
+        tl_apply_path |= 1;
       }
       if (whole == size) return 0;
       for (int j = 0; j < K; ++j) tin[j] = {in[j].base + static_cast<uint64_t>(whole), in[j].stride};
@@ -637,6 +641,7 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
     if (hipFunction_t fn = lsec::jit::ready(image, R, K)) {  // the bitmatrix's compiled packet network
       const hipError_t err = lsec::jit::launch_pkt(fn, R, K, in, out, nstripes, size, packet, w, st);
       if (err != hipSuccess) return fail("packet network launch failed: %s", hipGetErrorString(err));
+      tl_apply_path |= 2;
       return 0;
     }
   const int rmax = kind == KBITMATRIX ? 2 : ((kind == KBITSLICEDW || kind == KWORDWISE) && w == 32) ? 4 : 8;
@@ -676,6 +681,7 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
                                : kind == KBITSLICEDW ? lsec::launch_gfw_bitsliced(b, st)
                                                     : lsec::launch_bitsliced(b, st, 0, c8_dw);
         if (err != hipSuccess) return fail("kernel launch failed: %s", hipGetErrorString(err));
+        tl_apply_path |= 4;
       }
     }
   }
@@ -1426,6 +1432,12 @@ int lsec_tile_sharing(void) { return lsec::tile_mode(); }
 void lsec_test_set_stamps(void *dev_buf, unsigned n) {
   lsec::set_launch_stamps(static_cast<unsigned long long *>(dev_buf), n);
 }
+
+// Test hook, not in include/: what the calling thread's last lsec_encode_dev / lsec_decode_dev
+// launched -- bit 0 a compiled XOR / GF(2^w) network, bit 1 a compiled packet network, bit 2 a
+// generic kernel (a w = 16 / 32 network with a ragged tail: bits 0 and 2).  The bytes are the same
+// on every path, so only this tells a test which one alignment and readiness picked.
+int lsec_test_apply_path(void) { return tl_apply_path; }
 
 // Test hook, not in include/: 1 = Cauchy at w = 8 on its compiled packet network wherever one exists,
 // 0 = by shape (cauchy8_bitsliced_dw, the default).

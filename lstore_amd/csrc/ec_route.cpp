@@ -564,6 +564,21 @@ int fp_decode_block(lio_erasure_plan_t *p, char **ptr, int block_size, int *eras
 
 int fp_dummy(lio_erasure_plan_t *) { return 0; }
 
+// The rule of lsec_shard_t (include/lstore_ec.h) for every lsec_*_dev entry point: each base, and
+// each stride once a second stripe uses it, is a multiple of 8 bytes.  A geometry no call accepts
+// is left to check_geometry's message.
+int check_shards(const lio_erasure_plan_t *p, const lsec_shard_t *sh, int nstripes) {
+  const int n = p->data_strips + p->parity_strips;
+  if (p->data_strips < 1 || p->parity_strips < 1 || n > kMaxDevs) return 0;
+  for (int i = 0; i < n; ++i) {
+    if (reinterpret_cast<uintptr_t>(sh[i].base) % 8 != 0)
+      return fail("shard %d: base %p is not a multiple of 8 bytes (lsec_shard_t)", i, sh[i].base);
+    if (nstripes > 1 && sh[i].stride % 8 != 0)
+      return fail("shard %d: stride %lld is not a multiple of 8 bytes (lsec_shard_t)", i, sh[i].stride);
+  }
+  return 0;
+}
+
 }  // namespace eng
 }  // namespace lsec
 
@@ -589,6 +604,7 @@ int lsec_encode_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int ns
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
   if (!shards) return fail("shards is NULL");
+  if (check_shards(plan, shards, nstripes)) return -1;
   return encode_dev(e, shards, nstripes, block_size, static_cast<hipStream_t>(stream));
 }
 
@@ -597,6 +613,7 @@ int lsec_decode_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int ns
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
   if (!shards) return fail("shards is NULL");
+  if (check_shards(plan, shards, nstripes)) return -1;
   return decode_dev(e, shards, nstripes, block_size, erasures, static_cast<hipStream_t>(stream));
 }
 
@@ -605,6 +622,7 @@ int lsec_decode_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shard
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
   if (!shards) return fail("shards is NULL");
+  if (check_shards(plan, shards, nstripes)) return -1;
   return decode_dev_patterns(e, shards, nstripes, block_size, patterns, npatterns, stripe_pattern,
                              static_cast<hipStream_t>(stream));
 }
@@ -614,6 +632,7 @@ int lsec_decode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
   if (!devs) return fail("devs is NULL");
+  if (check_shards(plan, devs, nstripes)) return -1;
   return decode_dev_rotated(e, devs, nstripes, block_size, lost, n_shift, first_stripe, static_cast<hipStream_t>(stream));
 }
 
@@ -634,6 +653,7 @@ int lsec_stripe_magic_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, 
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
   if (!shards || !magic) return fail("shards / magic is NULL");
+  if (check_shards(plan, shards, nstripes)) return -1;
   return magic_dev_impl(e, shards, nstripes, block_size, static_cast<uint8_t *>(magic), static_cast<hipStream_t>(stream));
 }
 
@@ -642,6 +662,7 @@ int lsec_encode_magic_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, 
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
   if (!shards || !magic) return fail("shards / magic is NULL");
+  if (check_shards(plan, shards, nstripes)) return -1;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int k = plan->data_strips, m = plan->parity_strips;
   // One pass: the encode kernel also accumulates the magic of the k inputs and m outputs.

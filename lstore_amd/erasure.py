@@ -367,16 +367,24 @@ class Plan:
         _check(lib().et_stripes_magic(self._p, arr, n, size, magic.ctypes.data), "et_stripes_magic")
         return magic
 
+    def encode_magic_dev_refs(self, refs, nstripes: int, block_size: int, magic_ptr: int, stream: int = 0) -> None:
+        """lsec_encode_magic_dev over raw shard refs; magic_ptr: device address of 4*nstripes bytes."""
+        _check(lib().lsec_encode_magic_dev(self._p, self.shard_refs(refs), nstripes, block_size, magic_ptr, stream),
+               "lsec_encode_magic_dev")
+
+    def stripe_magic_dev_refs(self, refs, nstripes: int, block_size: int, magic_ptr: int, stream: int = 0) -> None:
+        """lsec_stripe_magic_dev over raw shard refs: the magic of the k+m chunks as they are."""
+        _check(lib().lsec_stripe_magic_dev(self._p, self.shard_refs(refs), nstripes, block_size, magic_ptr, stream),
+               "lsec_stripe_magic_dev")
+
     def encode_magic_dev(self, data, parity, magic, stream=None) -> None:
         """torch: encode + magic (uint8 [N,4] device tensor)."""
         refs, n, size = self.tensor_refs(data, parity)
-        _check(lib().lsec_encode_magic_dev(self._p, self.shard_refs(refs), n, size, magic.data_ptr(),
-                                           _stream_handle(stream)), "lsec_encode_magic_dev")
+        self.encode_magic_dev_refs(refs, n, size, magic.data_ptr(), _stream_handle(stream))
 
     def stripe_magic_dev(self, data, parity, magic, stream=None) -> None:
         refs, n, size = self.tensor_refs(data, parity)
-        _check(lib().lsec_stripe_magic_dev(self._p, self.shard_refs(refs), n, size, magic.data_ptr(),
-                                           _stream_handle(stream)), "lsec_stripe_magic_dev")
+        self.stripe_magic_dev_refs(refs, n, size, magic.data_ptr(), _stream_handle(stream))
 
     # -- segment adapter (segjerase_write_func + LUN placement)
     def segment_write(self, data: np.ndarray, n_shift: int = 1, first_stripe: int = 0,
@@ -614,6 +622,15 @@ def tile_sharing() -> int:
 
 def set_kernel_variant(bytewise: int = 0, bitsliced: int = 0) -> None:
     lib().lsec_set_kernel_variant(bytewise, bitsliced)
+
+
+PATH_NETWORK, PATH_PACKET_NETWORK, PATH_GENERIC = 1, 2, 4
+
+
+def apply_path() -> int:
+    """Test hook: what this thread's last encode_dev / decode_dev launched, as PATH_* bits (a
+    w = 16 / 32 network that leaves a ragged tail to the generic kernel: PATH_NETWORK | PATH_GENERIC)."""
+    return int(lib().lsec_test_apply_path())
 
 
 def set_pattern_split(stripes: int = 0) -> None:
