@@ -94,6 +94,8 @@ int et_decode(lio_erasure_plan_t *plan, long long int fsize, const char *fname, 
 /* ===================================================================== Part 2: extensions */
 
 #define LSEC_ABI_VERSION 3   /* 3: + lsec_decode_dev_patterns, lsec_decode_dev_rotated (additive) */
+/* lsec_check_dev came later and is purely additive: the version stays 3, and a caller detects
+ * it by the symbol (dlsym). */
 
 /* Stripe-batched host-memory calls.  ptrs holds nstripes*(k+m) pointers laid out exactly
  * like segjerase_write_func's ptr[] array (segment/jerasure.c:1647, :1812-1836): stripe s
@@ -163,6 +165,35 @@ int lsec_decode_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shard
 int lsec_decode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
                             long long block_size, const int *lost, int n_shift,
                             long long first_stripe, void *stream);
+
+/* Parity check of device-resident stripes, one pass: are these stripes consistent, and if not,
+ * which parity rows disagree?  `shards` are the k+m logical chunks as for lsec_encode_dev; all
+ * of them are only read.  `syndrome` is device memory holding nstripes 32-bit words.
+ *
+ * - After the call, bit r (r < m) of syndrome[s] is set exactly when parity chunk r, as
+ *   lsec_encode_dev would write it for the stored data chunks of stripe s, differs in at least
+ *   one byte from the stored parity chunk r.  Bits m..31 are 0.
+ * - The call sets every word itself (a hipMemsetAsync on `stream` ahead of the kernel): the
+ *   caller does not pre-zero.
+ * - bad_count is optional (may be NULL): one 32-bit word of device memory that receives the
+ *   number of stripes with a nonzero syndrome.  The call sets it; it does not add to it.
+ * - Nothing else is written, and nothing proportional to the data is allocated: the pass reads
+ *   k + m chunks per stripe and writes only for inconsistent stripes.
+ * - syndrome and bad_count must be 4-byte aligned and must not overlap the shards.
+ * - Layout, alignment and block_size rules are those of lsec_encode_dev (lsec_shard_t, above;
+ *   for Cauchy a multiple of 8 * packet_size).
+ * - nstripes == 0 validates the arguments, returns 0 and touches no GPU (syndrome may then be
+ *   NULL), so a caller can check a call shape ahead.
+ * - Plans: lsec_plan_kernel 1 (bytewise GF(2^8): RS, r6, raid4) and 2 (bit-sliced GF(2^8):
+ *   Cauchy at w = 8).  Further limits: k <= 64, m <= 8.
+ * - Anything outside these limits -- plan kernels 3-5, wider stripes, a NULL shards, a NULL
+ *   syndrome with nstripes > 0, a misaligned pointer -- returns -1 with a message for
+ *   lsec_last_error that names the limit, and nothing is enqueued.  There is no fallback to
+ *   encode-and-compare.
+ * Enqueued on `stream`; returns without synchronising.  0 / -1. */
+int lsec_check_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
+                   long long block_size, unsigned int *syndrome, unsigned int *bad_count,
+                   void *stream);
 
 /* Per-stripe "magic": the 4-byte little-endian zlib adler32 over the concatenation of a
  * stripe's k+m chunks that LStore's erasure segment stores in front of every chunk

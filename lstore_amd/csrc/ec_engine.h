@@ -145,6 +145,9 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
                   long long size, int packet, hipStream_t st, int w = 8);
 int encode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, hipStream_t st);
 int decode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *erasures, hipStream_t st);
+// one-pass parity check: syndrome[s] bit r = parity row r of stripe s differs from the stored chunk
+int check_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned *bad_count,
+              hipStream_t st);
 // stripes that do not share an erasure pattern, one launch per 32-bit range of tiles
 int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift, PatternTable &tab);
 uint32_t pattern_rot0(int n, int n_shift, long long first_stripe);

@@ -156,6 +156,35 @@ struct PatternArgs {
 hipError_t launch_pattern_bytewise(const PatternArgs &a, int rmax, hipStream_t stream);
 hipError_t launch_pattern_bitsliced(const PatternArgs &a, int rmax, hipStream_t stream);
 
+// Parity check of device-resident stripes (lsec_check_dev): one streaming pass forms the R parity
+// rows of every stripe in registers, as the encode kernels do, and compares them with the stored
+// parity chunks instead of storing them.  Bit r of syndrome[s] is set when row r of stripe s
+// differs anywhere; bad_count (may be null) counts the stripes whose word became nonzero.  Both
+// are zeroed by the caller (check_dev's hipMemsetAsync, ahead of the kernel on the same stream):
+// the kernels only ever OR bits in, one returning atomic per wave that found a difference, and
+// the wave whose atomic returns 0 -- the first to make the word nonzero, so exactly one per bad
+// stripe -- counts the stripe.  A clean wave writes nothing.  An argument struct of its own:
+// ApplyArgs and PatternArgs stay as they are.
+struct CheckArgs {
+  const CoefCell *cells;  // the encode image, R x K, row-major (device memory)
+  int K, R;
+  int nstripes;
+  int packet;             // bit-sliced: packet size P (bytes)
+  int64_t size;           // bytes per shard (chunk C)
+  unsigned *syndrome;     // nstripes words (device memory, zeroed)
+  unsigned *bad_count;    // one word (device memory, zeroed), or null
+  unsigned *tiles;        // as ApplyArgs
+  uint32_t tiles_pre;
+  uint32_t tile_phase;
+  ShardRef in[kMaxK];     // the data chunks
+  ShardRef par[kMaxR];    // the stored parity chunks (only read)
+};
+
+// R <= 8; the launch shape is the encode's for the same K x R (bytewise_shape's automatic policy)
+hipError_t launch_check_bytewise(const CheckArgs &a, hipStream_t stream);
+// dw_pref: dwords per lane (1, 2, 4; 0 = 1), as launch_bitsliced
+hipError_t launch_check_bitsliced(const CheckArgs &a, hipStream_t stream, int dw_pref = 0);
+
 // Work-sharing tiles.  The streaming kernels deal each XCD a contiguous eighth of the tiles
 // (xcd_remap), but the XCDs do not run at one rate: on the headline's memory shape the odd ones
 // take ~15 % longer per tile, every launch, so the even ones idle for the last 6-8 % of it

@@ -394,6 +394,38 @@ hipError_t launch_pattern_bitsliced(const PatternArgs &a, int rmax, hipStream_t 
   return by_r(rmax, [&](auto r) { return dispatch_pat_bitsliced<decltype(r)::value>(a, st, grid); });
 }
 
+namespace {
+bool check_args_ok(const CheckArgs &a) {
+  return a.K >= 1 && a.K <= kMaxK && a.R >= 1 && a.R <= 8 && a.cells && a.syndrome && a.size % 8 == 0 &&
+         reinterpret_cast<uintptr_t>(a.syndrome) % 4 == 0 && reinterpret_cast<uintptr_t>(a.bad_count) % 4 == 0;
+}
+}  // namespace
+
+hipError_t launch_check_bytewise(const CheckArgs &a, hipStream_t st) {
+  if (!check_args_ok(a)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int shape = chk_shape(a.K, a.R);
+  const uint64_t tile = static_cast<uint64_t>(kBlock) * 4 * bw_shape_vw(shape) * bw_shape_it(shape);
+  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
+  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
+  const int grid = default_grid(ntiles);
+  return by_r(a.R, [&](auto r) { return dispatch_chk_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_check_bitsliced(const CheckArgs &a, hipStream_t st, int dw_pref) {
+  if (!check_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  int dw = dw_pref == 2 || dw_pref == 4 ? dw_pref : 1;
+  while (dw > 1 && a.packet % (4 * dw) != 0) dw >>= 1;
+  const uint64_t col_bytes = a.size / 8;
+  const uint64_t tile = kBlock * 4ull * dw;
+  const uint64_t ntiles = ((col_bytes + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
+  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
+  const int grid = default_grid(ntiles);
+  return by_r(a.R, [&](auto r) { return dispatch_chk_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+}
+
 // ------------------------------------------------------------------ stripe magic (adler32)
 namespace {
 

@@ -1479,6 +1479,336 @@ LSEC_DECLARE_PAT_R(1) LSEC_DECLARE_PAT_R(2) LSEC_DECLARE_PAT_R(3) LSEC_DECLARE_P
 LSEC_DECLARE_PAT_R(5) LSEC_DECLARE_PAT_R(6) LSEC_DECLARE_PAT_R(7) LSEC_DECLARE_PAT_R(8)
 #endif
 
+// ------------------------------------------------------------------ parity check
+// lsec_check_dev (ec_kernels.h, CheckArgs): the encode kernels' tile loop, loads and arithmetic,
+// with the stored parity chunks read alongside the data and compared in registers where the
+// encode stores: k + m chunk reads per stripe and no writes unless a stripe is inconsistent.
+// There is no barrier and no LDS in the tile body: a wave reduces its rows with a wave-wide vote
+// and publishes on its own.
+template <typename Kern>
+hipError_t launch_tiled(Kern *k, int grid, hipStream_t st, CheckArgs a) {
+  // `grid` is the tile count here, as in the ApplyArgs form above
+  a.tile_phase = tile_phase_on() && a.nstripes > 0 && grid % a.nstripes == 0 ? static_cast<uint32_t>(grid / a.nstripes / 8) : 0;
+  unsigned *slot = tile_queue_slot(st, static_cast<uint64_t>(grid));
+  a.tiles = nullptr;
+  a.tiles_pre = 0;
+  if (slot) {
+    const int pg = persistent_grid(reinterpret_cast<const void *>(k), grid, st);
+    if (pg > 0) {
+      a.tiles = slot;
+      a.tiles_pre = tiles_prefix(static_cast<uint32_t>(grid));
+      grid = static_cast<int>(8 * a.tiles_pre) + pg;
+    }
+  }
+  const hipError_t e = launch_kernel_shm(k, dim3(grid), dim3(kBlock), occupancy_lds_bytes(a.size), st, a);
+  tile_queue_release(st, slot);
+  return e;
+}
+
+// d |= x ^ y in one VALU op (v_bitop3_b32, truth table (a ^ b) | c = 0xBE)
+__device__ __forceinline__ uint32_t or_diff(uint32_t x, uint32_t y, uint32_t d) {
+  return __builtin_amdgcn_bitop3_b32(x, y, d, 0xBE);
+}
+
+// A wave's finding for stripe s (s uniform over the wave): d[r] != 0 in any active lane sets bit
+// r.  One vote decides the common case -- no lane of the wave saw a difference: nothing is issued
+// -- and only a wave that did votes per row and has its first active lane publish.  The atomic's
+// return value tells the one wave that made the word nonzero, which counts the stripe.
+template <int R>
+__device__ __forceinline__ void chk_publish(const CheckArgs &a, uint32_t s, const uint32_t (&d)[R]) {
+  uint32_t any = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) any |= d[r];
+  if (__ballot(any != 0) == 0) return;  // wave-uniform
+  uint32_t mask = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) mask |= (__ballot(d[r] != 0) != 0 ? 1u : 0u) << r;
+  const uint32_t first = static_cast<uint32_t>(__builtin_ctzll(__ballot(1)));
+  if ((threadIdx.x & 63u) == first) {
+    const uint32_t old = atomicOr(a.syndrome + s, mask);
+    if (old == 0 && a.bad_count) atomicAdd(a.bad_count, 1u);
+  }
+}
+
+// one lane unit of a ragged last tile: C is a multiple of 8, so a 16-byte unit may be half full
+// (its two valid dwords are read, the rest is 0), and a unit wholly past C is 0
+template <int VW>
+__device__ __forceinline__ typename VecT<VW>::type chk_load_ragged(uint64_t p, int64_t o, int64_t C) {
+  typename VecT<VW>::type v = 0u;
+  if (o + 4 * VW <= C) {
+    v = *gptr<typename VecT<VW>::type>(p + o);
+  } else if (o < C) {
+    const u32x2 h = *gptr<u32x2>(p + o);
+    v[0] = h.x;
+    v[1] = h.y;
+  }
+  return v;
+}
+
+// BF, X0, KC as bytewise_tiles.  A full tile with K fixed has its K*IT data loads and its R*IT
+// parity loads in flight before any arithmetic (the parity rows cost R*IT*VW VGPRs more than the
+// encode: 24 at RS(6+3)); with K at run time the parity loads go out ahead of the first four inputs.
+template <int R, int KC, int IT, bool BF, int VW, bool X0>
+__device__ __forceinline__ void chk_bytewise_tiles(const CheckArgs &a) {
+  typedef typename VecT<VW>::type V;
+  constexpr int kStep = BwTile<IT, VW>::kStep;
+  constexpr int kTile = BwTile<IT, VW>::kBytes;
+  constexpr int kLane = 4 * VW;
+  const int K = KC ? KC : a.K;
+  const int64_t C = a.size;
+  const uint32_t tiles_per_stripe = static_cast<uint32_t>((C + kTile - 1) / kTile);
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+
+  for_tiles<(kTile >= 8192 ? 1 : 8192 / kTile)>(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
+    const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
+
+    V acc[IT][R], pv[R][IT];
+#pragma unroll
+    for (int it = 0; it < IT; ++it)
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[it][r] = 0u;
+
+    if (full) {
+      if constexpr (KC > 0) {
+        V v[KC][IT];
+#pragma unroll
+        for (int j = 0; j < KC; ++j) {
+          const uint64_t p = a.in[j].base + s * a.in[j].stride + off0;
+#pragma unroll
+          for (int it = 0; it < IT; ++it) v[j][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const uint64_t q = a.par[r].base + s * a.par[r].stride + off0;
+#pragma unroll
+          for (int it = 0; it < IT; ++it) pv[r][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
+        }
+        if constexpr (BF) {
+#pragma unroll
+          for (int j = 0; j + 1 < KC; j += 2) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[j], v[j + 1], cells, K, j);
+          if constexpr (KC % 2) bw_accumulate_bf<R, IT, VW, false, X0>(acc, v[KC - 1], v[KC - 1], cells, K, KC - 1);
+        } else {
+#pragma unroll
+          for (int j = 0; j < KC; ++j) bw_accumulate<R, IT, VW>(acc, v[j], cells, K, j);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const uint64_t q = a.par[r].base + s * a.par[r].stride + off0;
+#pragma unroll
+          for (int it = 0; it < IT; ++it) pv[r][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
+        }
+        for (int j0 = 0; j0 < K; j0 += 4) {
+          V v[4][IT];
+          const int nj = min(4, K - j0);
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            if (jj < nj) {
+              const uint64_t p = a.in[j0 + jj].base + s * a.in[j0 + jj].stride + off0;
+#pragma unroll
+              for (int it = 0; it < IT; ++it) v[jj][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
+            }
+          }
+          if constexpr (BF) {
+            if (nj >= 2) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[0], v[1], cells, K, j0);
+            if (nj == 4) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[2], v[3], cells, K, j0 + 2);
+            if (nj == 1 || nj == 3) bw_accumulate_bf<R, IT, VW, false, X0>(acc, v[nj - 1], v[nj - 1], cells, K, j0 + nj - 1);
+          } else {
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+              if (jj < nj) bw_accumulate<R, IT, VW>(acc, v[jj], cells, K, j0 + jj);
+          }
+        }
+      }
+    } else {
+      // ragged last tile: zero-filled inputs give zero parity there, and the stored parity is
+      // zero-filled the same way, so bytes past C never show as a difference
+      for (int j = 0; j < K; ++j) {
+        const uint64_t p = a.in[j].base + s * a.in[j].stride;
+        V v[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) v[it] = chk_load_ragged<VW>(p, off0 + it * kStep, C);
+        bw_acc1<R, IT, VW, BF, X0>(acc, v, cells, K, j);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint64_t q = a.par[r].base + s * a.par[r].stride;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) pv[r][it] = chk_load_ragged<VW>(q, off0 + it * kStep, C);
+      }
+    }
+    uint32_t d[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      d[r] = 0;
+#pragma unroll
+      for (int it = 0; it < IT; ++it)
+#pragma unroll
+        for (int e = 0; e < VW; ++e) d[r] = or_diff(acc[it][r][e], pv[r][it][e], d[r]);
+    }
+    chk_publish<R>(a, s, d);
+  }, a.tile_phase);
+}
+
+// the XOR-row flag picks one of two whole instantiations, by k_gf8_bytewise's rule
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_chk_bytewise(CheckArgs a) {
+  if constexpr (BF && R >= 2 && (KC == 0 || KC * R >= 40)) {
+    if (const_cells(a.cells)->pad & kCellXorRow) {
+      chk_bytewise_tiles<R, KC, IT, BF, VW, true>(a);
+      return;
+    }
+  }
+  chk_bytewise_tiles<R, KC, IT, BF, VW, false>(a);
+}
+
+// k_gf8_bitsliced's lanes and doubling loop.  The stored parity words are loaded ahead of the
+// inputs while they fit beside the accumulators (R * DW <= 8: 8 * R * DW VGPRs), else row by row
+// after them.  Lanes past the end of a ragged last tile leave the tile body (whole waves may).
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_chk_bitsliced(CheckArgs a) {
+  typedef typename VecT<DW>::type V;
+  constexpr bool kAhead = R * DW <= 8;
+  const int K = a.K;
+  const uint32_t P = static_cast<uint32_t>(a.packet);
+  const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
+  constexpr uint32_t kTile = kBlock * 4 * DW;
+  const uint32_t tiles_per_stripe = (col_bytes + kTile - 1) / kTile;
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+
+  for_tiles(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * (4 * DW);
+    if (colb >= col_bytes) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
+    const uint32_t sp = colb / P;
+    const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+
+    V acc[R][8], pv[kAhead ? R : 1][8];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
+    if constexpr (kAhead) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint64_t q = a.par[r].base + s * a.par[r].stride + off;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) pv[r][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
+      }
+    }
+
+    for (int j = 0; j < K; ++j) {
+      const uint64_t p = a.in[j].base + s * a.in[j].stride + off;
+      V e[8];
+#pragma unroll
+      for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<V>(p + x * P));
+      uint32_t c[R];
+      uint32_t cm = 0;  // bits used by any output: no doublings past the highest one
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        c[r] = cells[r * K + j].coef;
+        cm |= c[r];
+      }
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if ((c[r] >> b) & 1u) {
+#pragma unroll
+            for (int x = 0; x < 8; ++x) acc[r][x] ^= e[x];
+          }
+        if ((cm >> (b + 1)) == 0) break;
+        if (b < 7) {  // e <- 2*e in bit-sliced form
+          const V top = e[7];
+          e[7] = e[6];
+          e[6] = e[5];
+          e[5] = e[4];
+          e[4] = e[3] ^ top;
+          e[3] = e[2] ^ top;
+          e[2] = e[1] ^ top;
+          e[1] = e[0];
+          e[0] = top;
+        }
+      }
+    }
+    uint32_t d[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if constexpr (!kAhead) {
+        const uint64_t q = a.par[r].base + s * a.par[r].stride + off;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) pv[0][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
+      }
+      d[r] = 0;
+#pragma unroll
+      for (int x = 0; x < 8; ++x)
+#pragma unroll
+        for (int w = 0; w < DW; ++w)
+          d[r] = or_diff(reinterpret_cast<const uint32_t *>(&acc[r][x])[w],
+                         reinterpret_cast<const uint32_t *>(&pv[kAhead ? r : 0][x])[w], d[r]);
+    }
+    chk_publish<R>(a, s, d);
+  }, a.tile_phase);
+}
+
+// The check's launch shape is the encode's automatic one for the same K x R (bytewise_shape in
+// ec_kernels.hip, without its A/B variants): R == 1 -> 8 B per lane with per-cell branches,
+// K >= 16 -> 16 B per lane, else 2 x 16 B per lane (both branch-free), so tile sizes and vector
+// widths match lsec_encode_dev's; fixed-K forms for the K the encode has them for.
+inline int chk_shape(int K, int R) { return R == 1 ? 4 : K >= 16 ? 1 : 0; }
+// A fixed-K form holds K data units, R stored-parity units and R accumulators per step: past 160
+// such dwords (RS(12+8) at 2 x 16 B: 224) it would fill the register file (256 VGPRs and copies in
+// AGPRs), so those stripes run with K at run time, four inputs in flight at a time.
+constexpr bool chk_fixed_k(int K, int R, int IT, int VW) { return (K + 2 * R) * IT * VW <= 160; }
+
+template <int R>
+hipError_t dispatch_chk_bytewise(const CheckArgs &a, hipStream_t st, int grid) {
+  if constexpr (R == 1) {
+    switch (a.K) {
+#define LSEC_CHK_K(KK) \
+  case KK: return launch_tiled(&k_chk_bytewise<1, KK, 1, false, 2>, grid, st, a);
+      LSEC_CHK_K(4) LSEC_CHK_K(6) LSEC_CHK_K(8) LSEC_CHK_K(10) LSEC_CHK_K(12) LSEC_CHK_K(16) LSEC_CHK_K(20)
+#undef LSEC_CHK_K
+      default: return launch_tiled(&k_chk_bytewise<1, 0, 1, false, 2>, grid, st, a);
+    }
+  } else {
+    switch (a.K) {
+#define LSEC_CHK_K(KK, IT)                      \
+  case KK:                                      \
+    if constexpr (chk_fixed_k(KK, R, IT, 4))    \
+      return launch_tiled(&k_chk_bytewise<R, KK, IT, true, 4>, grid, st, a); \
+    break;
+      LSEC_CHK_K(4, 2) LSEC_CHK_K(6, 2) LSEC_CHK_K(8, 2) LSEC_CHK_K(10, 2) LSEC_CHK_K(12, 2) LSEC_CHK_K(16, 1) LSEC_CHK_K(20, 1)
+#undef LSEC_CHK_K
+      default: break;
+    }
+    if (chk_shape(a.K, R) == 1) return launch_tiled(&k_chk_bytewise<R, 0, 1, true, 4>, grid, st, a);
+    return launch_tiled(&k_chk_bytewise<R, 0, 2, true, 4>, grid, st, a);
+  }
+}
+
+template <int R>
+hipError_t dispatch_chk_bitsliced(const CheckArgs &a, hipStream_t st, int grid, int dw) {
+  switch (dw) {
+    case 4: return launch_tiled(&k_chk_bitsliced<R, 4>, grid, st, a);
+    case 2: return launch_tiled(&k_chk_bitsliced<R, 2>, grid, st, a);
+    default: return launch_tiled(&k_chk_bitsliced<R, 1>, grid, st, a);
+  }
+}
+
+// instantiated per R in ec_check_inst.hip
+#define LSEC_DECLARE_CHK_R(RR)                                                               \
+  extern template hipError_t dispatch_chk_bytewise<RR>(const CheckArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_chk_bitsliced<RR>(const CheckArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_CHK
+LSEC_DECLARE_CHK_R(1) LSEC_DECLARE_CHK_R(2) LSEC_DECLARE_CHK_R(3) LSEC_DECLARE_CHK_R(4)
+LSEC_DECLARE_CHK_R(5) LSEC_DECLARE_CHK_R(6) LSEC_DECLARE_CHK_R(7) LSEC_DECLARE_CHK_R(8)
+#endif
+
 #define LSEC_DECLARE_R(RR)                                                                         \
   extern template hipError_t dispatch_bytewise<RR>(const ApplyArgs &, hipStream_t, int, int);      \
   extern template hipError_t dispatch_bitsliced<RR>(const ApplyArgs &, hipStream_t, int, int);         \

@@ -731,6 +731,59 @@ int decode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
   return enqueue_apply(decode_kind(e, ent), cells, k, R, in, out, nstripes, C, p->packet_size, st, p->w);
 }
 
+// ---------------------------------------------------------------- parity check
+// lsec_check_dev: syndrome[s] bit r = parity row r of stripe s, as encode_dev would write it,
+// differs from the stored one.  One launch per 32-bit range of tiles (as enqueue_apply) over the
+// encode image, in the encode's launch shape; the words are zeroed on the stream ahead of it.
+// Every limit's message names the limit; nothing is enqueued when one is passed.
+int check_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned *bad_count,
+              hipStream_t st) {
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("lsec_check_dev needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips;
+  if (k < 1 || k > lsec::kMaxK) return fail("lsec_check_dev: k=%d outside 1..%d (one launch's inputs)", k, lsec::kMaxK);
+  if (m < 1 || m > 8) return fail("lsec_check_dev: m=%d outside 1..8 (one launch's parity rows)", m);
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (check_geometry(p, C)) return -1;
+  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
+  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
+  if (reinterpret_cast<uintptr_t>(bad_count) % 4 != 0) return fail("bad_count %p is not a multiple of 4 bytes", static_cast<void *>(bad_count));
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_cells(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("lsec_check_dev: the plan encodes %d parity rows, m=%d", R, m);
+  // the call sets every word itself, stripes of an empty chunk included
+  HIP_OK(hipMemsetAsync(syndrome, 0, sizeof(unsigned) * static_cast<size_t>(nstripes), st));
+  if (bad_count) HIP_OK(hipMemsetAsync(bad_count, 0, sizeof(unsigned), st));
+  if (C == 0) return 0;
+  lsec::CheckArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.cells = static_cast<const CoefCell *>(cells);
+  a.K = k;
+  a.R = R;
+  a.size = C;
+  a.packet = p->packet_size;
+  a.bad_count = bad_count;
+  // the encode's dwords per lane for this shape (0: its packet network, which the check has no form of)
+  const int dw = kind == KBITSLICED ? cauchy8_bitsliced_dw(k, R, C) : 0;
+  const long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
+  for (long long s0 = 0; s0 < nstripes; s0 += per) {
+    a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
+    a.syndrome = syndrome + s0;
+    for (int j = 0; j < k; ++j)
+      a.in[j] = {reinterpret_cast<uint64_t>(sh[j].base) + static_cast<uint64_t>(s0) * sh[j].stride, sh[j].stride};
+    for (int r = 0; r < R; ++r)
+      a.par[r] = {reinterpret_cast<uint64_t>(sh[k + r].base) + static_cast<uint64_t>(s0) * sh[k + r].stride, sh[k + r].stride};
+    const hipError_t err = kind == KBITSLICED ? lsec::launch_check_bitsliced(a, st, dw) : lsec::launch_check_bytewise(a, st);
+    if (err != hipSuccess) return fail("check kernel launch failed: %s", hipGetErrorString(err));
+  }
+  return 0;
+}
+
 // ---------------------------------------------------------------- per-stripe erasure patterns
 // lsec_decode_dev_patterns / lsec_decode_dev_rotated: one table of pattern records and matrix
 // images (ec_kernels.h, PatRecord) per call shape, built from the per-pattern host plans of

@@ -81,7 +81,7 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_prepare_decode", "lsec_abi_version", "lsec_device_count", "lsec_last_error", "lsec_plan_kernel",
            "lsec_set_kernel_variant", "lsec_set_host_devices", "lsec_hbm_copy_dev", "lsec_hbm_mix_dev", "lsec_prepare_encode", "lsec_plan_jit", "lsec_device_numa",
            "lsec_set_tile_sharing", "lsec_tile_sharing", "lsec_host_unpin_drain", "lsec_hbm_decode_shape_dev",
-           "lsec_decode_dev_patterns", "lsec_decode_dev_rotated")
+           "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -138,6 +138,7 @@ def lib():
                                            C.c_void_p, C.c_void_p]
     L.lsec_decode_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
                                           C.c_longlong, C.c_void_p]
+    L.lsec_check_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lsec_test_set_pattern_split.argtypes = [C.c_int]
     L.lsec_test_set_pattern_split.restype = None
     L.lsec_test_pattern_table.argtypes = [P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
@@ -554,6 +555,24 @@ class Plan:
         of the `lost` devices receive the rebuilt chunks."""
         _check(lib().lsec_decode_dev_rotated(self._p, self.shard_refs(refs), nstripes, block_size, _erasure_array(lost),
                                              n_shift, first_stripe, stream), "lsec_decode_dev_rotated")
+
+    def check_dev_refs(self, refs, nstripes: int, block_size: int, syndrome_ptr: int, bad_count_ptr: int = 0,
+                       stream: int = 0) -> None:
+        """lsec_check_dev: one-pass parity check.  syndrome_ptr: device address of nstripes uint32 words,
+        bit r of word s set when parity row r of stripe s differs from the stored chunk; bad_count_ptr:
+        device address of one uint32 that receives the number of nonzero words (0: not wanted).  The
+        call sets both itself; the shards (refs None: NULL) are only read."""
+        _check(lib().lsec_check_dev(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                    syndrome_ptr or None, bad_count_ptr or None, stream), "lsec_check_dev")
+
+    def check_dev(self, data, parity, syndrome, bad_count=None, stream=None) -> None:
+        """torch: check data [N,k,C] against parity [N,m,C]; syndrome: int32 / uint32 device tensor [N],
+        bad_count: such a tensor of one element, or None."""
+        refs, n, size = self.tensor_refs(data, parity)
+        if syndrome.dtype.itemsize != 4 or not syndrome.is_cuda or not syndrome.is_contiguous() or syndrome.numel() != n:
+            raise ValueError("syndrome must be a contiguous 32-bit device tensor with one entry per stripe")
+        self.check_dev_refs(refs, n, size, syndrome.data_ptr(), 0 if bad_count is None else bad_count.data_ptr(),
+                            _stream_handle(stream))
 
     def prepare_decode(self, erasures) -> None:
         _check(lib().lsec_prepare_decode(self._p, _erasure_array(erasures)), "lsec_prepare_decode")

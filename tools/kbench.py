@@ -7,6 +7,9 @@ Prints HBM GB/s (algorithmic bytes / launch time, HIP events on the launch strea
 python tools/kbench.py --patterns [--nine] [--rounds R] [--reps N]
 The per-stripe-pattern decodes against the single-pattern decode, interleaved on the same buffers
 (RS(6+3) and Cauchy-good(6+3), C = 1 MiB, 4095 stripes): see patterns_bench.
+
+python tools/kbench.py --check [--rounds R] [--reps N]
+lsec_check_dev against lsec_encode_dev and against encode-and-compare, on the same shapes: see check_bench.
 """
 import argparse
 import os
@@ -160,6 +163,84 @@ def patterns_bench(a):
         torch.cuda.empty_cache()
 
 
+def check_bench(a):
+    """The parity check four ways, interleaved round by round on the same k+m buffers (one per chunk,
+    C = 1 MiB; nothing timed writes into them):
+      (a) lsec_encode_dev into scratch parity           the yardstick: the same k+m chunks of traffic, in
+                                                        code the check does not touch
+      (b) lsec_check_dev on consistent stripes          k+m reads, no writes past the memset
+      (c) lsec_check_dev, every byte of data chunk 0    every wave publishes: the atomics' worst case
+          of every stripe corrupted
+      (d) lsec_encode_dev into scratch parity + a       what a device caller does without the call
+          per-stripe torch comparison with the stored
+    (a)'s own min-max over the rounds is the margin (b) is judged by.  Results are checked before timing."""
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    C, N = 1 << 20, a.pattern_stripes
+    for name in a.pattern_codes.split(","):
+        meth, k, m = CONFIGS[name][:3]
+        n = k + m
+        plan = L.Plan.for_chunk(meth, k, m, C)
+        bufs = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(n)]
+        scratch = [torch.empty((N, C), dtype=torch.uint8, device=dev) for _ in range(m)]
+        refs = [(b.data_ptr(), C) for b in bufs]
+        plan.encode_dev_refs(refs, N, C, sh)  # consistent parity in buffers k..n-1
+        bad0 = bufs[0] ^ 0xFF  # every byte of data chunk 0 differs
+        bad_refs = [(bad0.data_ptr(), C)] + refs[1:]
+        to_scratch = lambda r: r[:k] + [(s.data_ptr(), C) for s in scratch]
+        syn = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        count = torch.full((1,), -1, dtype=torch.int32, device=dev)
+
+        def compare(r):  # (d): the syndrome words by encode-and-compare
+            plan.encode_dev_refs(to_scratch(r), N, C, sh)
+            out = torch.zeros(N, dtype=torch.int32, device=dev)
+            for i in range(m):
+                out |= (scratch[i] != bufs[k + i]).any(dim=1).to(torch.int32) << i
+            return out
+
+        runs = {"a": lambda: plan.encode_dev_refs(to_scratch(refs), N, C, sh),
+                "b": lambda: plan.check_dev_refs(refs, N, C, syn.data_ptr(), count.data_ptr(), sh),
+                "c": lambda: plan.check_dev_refs(bad_refs, N, C, syn.data_ptr(), count.data_ptr(), sh),
+                "d": lambda: compare(refs)}
+        # results first
+        runs["b"]()
+        torch.cuda.synchronize()
+        assert int(syn.count_nonzero()) == 0 and int(count) == 0, "(b) found a difference in consistent stripes"
+        want = compare(bad_refs)
+        runs["c"]()
+        torch.cuda.synchronize()
+        assert int(want.min()) > 0 and torch.equal(syn, want) and int(count) == N, "(c) differs from encode-and-compare"
+        assert int(compare(refs).count_nonzero()) == 0
+        times = {key: [] for key in runs}
+        for _ in range(a.rounds):
+            for key, fn in runs.items():
+                fn()  # warm
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.reps):
+                    fn()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[key].append(e0.elapsed_time(e1) / a.reps)
+        lo, hi = min(times["a"]), max(times["a"])
+        what = {"a": "lsec_encode_dev", "b": "lsec_check_dev, consistent", "c": "lsec_check_dev, all corrupt",
+                "d": "encode + torch compare"}
+        med = {key: sorted(ts)[len(ts) // 2] for key, ts in times.items()}
+        for key, ts in times.items():
+            db = n * C * N  # the k+m chunks a check has to move
+            band = "" if key != "b" else ("  inside (a)'s band" if lo <= med[key] <= hi else
+                                          f"  {'below' if med[key] < lo else 'above'} (a)'s band by "
+                                          f"{abs(med[key] - (lo if med[key] < lo else hi)) / med[key]:.2%}")
+            print(f"{name} N={N} C={C} ({key}) {what[key]:28s} median {med[key]:7.3f} ms  min {min(ts):7.3f}  max {max(ts):7.3f}  "
+                  f"{db / med[key] / 1e6:7.1f} GB/s ({db / med[key] / 8e9:5.1%} of 8 TB/s){band}", flush=True)
+        print(f"{name} (a) band: {lo:.3f} .. {hi:.3f} ms ({(hi - lo) / lo:.2%}) over {a.rounds} rounds of {a.reps} launches; "
+              f"(b)/(d) = {med['b'] / med['d']:.3f}, (c)/(b) = {med['c'] / med['b']:.3f}", flush=True)
+        del bufs, scratch, bad0, syn, count, want
+        plan.close()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data-gib", type=float, default=24.0)
@@ -179,9 +260,15 @@ def main():
     ap.add_argument("--pattern-stripes", type=int, default=4095)
     ap.add_argument("--pattern-codes", default="rs63,cg63", help="--patterns: names from CONFIGS (their k and m; C = 1 MiB)")
     ap.add_argument("--pattern-lost", default="0", help="--patterns: the erasure list of (a) and (b)")
+    ap.add_argument("--check", action="store_true",
+                    help="time lsec_check_dev against lsec_encode_dev and encode-and-compare (check_bench; "
+                         "--pattern-stripes, --pattern-codes) and exit")
     a = ap.parse_args()
     if a.patterns:
         patterns_bench(a)
+        return
+    if a.check:
+        check_bench(a)
         return
     dev = torch.device("cuda:0")
     variants = [tuple(int(x) for x in v.split(",")) for v in a.variants.split(";")]
