@@ -195,6 +195,60 @@ int lsec_check_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nst
                    long long block_size, unsigned int *syndrome, unsigned int *bad_count,
                    void *stream);
 
+/* Locating -- and with LSEC_LOCATE_REPAIR rebuilding -- the one corrupt chunk of device-resident
+ * stripes, in the pass lsec_check_dev makes.  Purely additive too: the version stays 3, a caller
+ * detects the call by its symbol.
+ *
+ * With S_r the difference between parity row r re-formed from the stored data and the stored
+ * parity chunk r, one wrong data chunk j gives S_r = (g[r][j] / g[0][j]) * S_0 at every byte
+ * column (g: the coding matrix), and one wrong parity chunk r gives S_r alone.  All four outputs
+ * are device memory; the call sets every element itself (memsets on `stream` ahead of the
+ * kernels), nothing is allocated per call and no scratch is shared between streams.
+ *
+ * - syndrome[s] (nstripes 32-bit words): exactly the word lsec_check_dev produces for stripe s.
+ * - hyp[s] (nstripes 64-bit words): bit j (j < k) is set exactly when data chunk j is a
+ *   single-chunk explanation of stripe s, that is, when replacing chunk j by what the other
+ *   chunks rebuild makes the stripe consistent.  Bits k..63 are 0.  A consistent stripe has all k
+ *   bits set (every hypothesis holds trivially); a stripe whose only fault is in parity has 0.
+ * - located[s] (nstripes bytes):
+ *     LSEC_LOCATE_CLEAN  when syndrome[s] == 0;
+ *     k + r              when exactly bit r of syndrome[s] is set (parity chunk r);
+ *     j                  when all m syndrome bits are set and hyp[s] has exactly the one bit j;
+ *     LSEC_LOCATE_MANY   otherwise: inconsistent, and no single chunk explains it.
+ *   located is directly usable as the stripe_pattern argument of lsec_decode_dev_patterns with
+ *   the k+m single-erasure lists in chunk order ({0,-1}, {1,-1}, ..., {k+m-1,-1}): both sentinels
+ *   are >= npatterns and so act as the empty pattern.
+ * - counts is optional (may be NULL): two 32-bit words, the stripes located (a chunk id in
+ *   located) and the stripes marked LSEC_LOCATE_MANY.
+ * - flags & LSEC_LOCATE_REPAIR: behind the locate, on the same stream, every located chunk is
+ *   rebuilt in place, with the bytes lsec_decode_dev writes for that stripe with that one erasure
+ *   (it is that patterned decode, with located as stripe_pattern).  Clean and LSEC_LOCATE_MANY
+ *   stripes are neither read again nor written.  Without the flag the shards are only read.
+ * - What a code can tell apart: with m >= 3, corruption confined to two chunks is always
+ *   reported LSEC_LOCATE_MANY.  With m = 2, two corrupt chunks can imitate a third one (two
+ *   syndromes cannot tell two unknown chunks from one); this is a property of the code, not of
+ *   the engine.  Corruption in more chunks than that can imitate a single chunk under any code.
+ * - Plans: lsec_plan_kernel 1 and 2, k <= 64, 2 <= m <= 8 (one parity row cannot locate, so RAID4
+ *   and every m = 1 plan is refused), and no zero coefficient in the coding matrix (none of the
+ *   RS, r6 and Cauchy matrices has one).  LSEC_LOCATE_REPAIR adds the limits of
+ *   lsec_decode_dev_patterns.
+ * - syndrome and counts must be 4-byte aligned, hyp 8-byte aligned; located has no alignment
+ *   requirement.  None of the outputs may overlap the shards.
+ * - Layout, alignment and block_size rules are those of lsec_check_dev.
+ * - nstripes == 0 validates the arguments, returns 0 and touches no GPU (the outputs may then be
+ *   NULL); with LSEC_LOCATE_REPAIR it also prepares the pattern tables, as
+ *   lsec_decode_dev_patterns with nstripes == 0 does.
+ * - Every refusal returns -1 with a message for lsec_last_error that names the limit, and nothing
+ *   is enqueued.  There is no fallback.
+ * Enqueued on `stream`; returns without synchronising.  0 / -1. */
+#define LSEC_LOCATE_CLEAN  0xFF   /* stripe is consistent */
+#define LSEC_LOCATE_MANY   0xFE   /* inconsistent, and no single chunk explains it */
+#define LSEC_LOCATE_REPAIR 1      /* flags: rebuild each located chunk in place */
+
+int lsec_locate_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
+                    long long block_size, unsigned int *syndrome, unsigned long long *hyp,
+                    unsigned char *located, unsigned int *counts, int flags, void *stream);
+
 /* Per-stripe "magic": the 4-byte little-endian zlib adler32 over the concatenation of a
  * stripe's k+m chunks that LStore's erasure segment stores in front of every chunk
  * (je_cksum_calc, src/lio/segment/jerasure.c:169-182; checked by je_cksum_compare, :188-194).

@@ -113,6 +113,8 @@ struct PlanImpl {
   std::vector<uint32_t> enc_masks;                       // bitmatrix codes: (m*w) x k row masks;
                                                          // wordwise: m x k x w products
   std::map<int, uint32_t *> enc_dev_masks;
+  lsec::gf8::Mat ratio;                                  // lsec_locate_dev: Q[r-1][j] = g[r][j] / g[0][j], (m-1) x k
+  std::map<int, CoefCell *> ratio_cells;                 // device -> (m-1) x k cells of it
   std::map<std::vector<int>, DecodeEntry> decode_cache;  // sorted erased ids -> entry
   std::map<std::vector<int>, PatternTable> pattern_cache;  // PatternTable::key -> table (kept until the plan is destroyed)
 };
@@ -148,6 +150,10 @@ int decode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
 // one-pass parity check: syndrome[s] bit r = parity row r of stripe s differs from the stored chunk
 int check_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned *bad_count,
               hipStream_t st);
+// locate (and with LSEC_LOCATE_REPAIR rebuild) the one corrupt chunk of each stripe
+int locate_ratio(PlanExt *e, const lsec::gf8::Mat **out);  // the host ratio image; no device is touched
+int locate_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned long long *hyp,
+               unsigned char *located, unsigned *counts, int flags, hipStream_t st);
 // stripes that do not share an erasure pattern, one launch per 32-bit range of tiles
 int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift, PatternTable &tab);
 uint32_t pattern_rot0(int n, int n_shift, long long first_stripe);

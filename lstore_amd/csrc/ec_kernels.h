@@ -185,6 +185,30 @@ hipError_t launch_check_bytewise(const CheckArgs &a, hipStream_t stream);
 // dw_pref: dwords per lane (1, 2, 4; 0 = 1), as launch_bitsliced
 hipError_t launch_check_bitsliced(const CheckArgs &a, hipStream_t stream, int dw_pref = 0);
 
+// Locating the corrupt chunk (lsec_locate_dev): the check's pass, whose per-row differences
+// S_r = (row r re-formed from the stored data) ^ (stored parity r) are the stripe's syndromes.  One
+// wrong data chunk j gives S_r = Q[r-1][j] * S_0 at every byte column, Q[r-1][j] = g[r][j] / g[0][j]
+// (the ratio image); one wrong parity chunk r gives S_r alone.  A wave that saw a difference tests
+// every j < K over its lanes' words, ORs its row mask into syndrome[s] and ANDs the k-bit mask of
+// the hypotheses that held into hyp[s]; a clean wave issues nothing.  The caller has set syndrome
+// to 0 and hyp to all ones on the stream ahead of the launch.  CheckArgs' fields mean what they
+// mean to the check (bad_count is unused: the finalize launch counts).
+struct LocateArgs : CheckArgs {
+  const CoefCell *ratio;      // (R - 1) x K, row-major (device memory): Q
+  unsigned long long *hyp;    // nstripes words (device memory, all ones)
+};
+
+constexpr unsigned kLocateClean = 0xFF, kLocateMany = 0xFE;  // LSEC_LOCATE_CLEAN / _MANY (lstore_ec.h)
+
+// 2 <= R <= 8; launch shapes are the check's
+hipError_t launch_locate_bytewise(const LocateArgs &a, hipStream_t stream);
+hipError_t launch_locate_bitsliced(const LocateArgs &a, hipStream_t stream, int dw_pref = 0);
+// One thread per stripe, behind the accumulate launches: masks hyp[s] to K bits, writes located[s]
+// (kLocateClean, K + r, j or kLocateMany: the rules of lsec_locate_dev) and, with counts, adds the
+// located stripes to counts[0] and the kLocateMany ones to counts[1] (zeroed by the caller).
+hipError_t launch_locate_finalize(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
+                                  unsigned *counts, int nstripes, int K, int R, hipStream_t stream);
+
 // Work-sharing tiles.  The streaming kernels deal each XCD a contiguous eighth of the tiles
 // (xcd_remap), but the XCDs do not run at one rate: on the headline's memory shape the odd ones
 // take ~15 % longer per tile, every launch, so the even ones idle for the last 6-8 % of it

@@ -426,6 +426,72 @@ hipError_t launch_check_bitsliced(const CheckArgs &a, hipStream_t st, int dw_pre
   return by_r(a.R, [&](auto r) { return dispatch_chk_bitsliced<decltype(r)::value>(a, st, grid, dw); });
 }
 
+namespace {
+bool locate_args_ok(const LocateArgs &a) {
+  return check_args_ok(a) && a.R >= 2 && a.ratio && a.hyp && reinterpret_cast<uintptr_t>(a.hyp) % 8 == 0;
+}
+
+// One thread per stripe, after the accumulate launches: the verdict of lsec_locate_dev.
+__global__ void k_locate_finalize(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
+                                  unsigned *counts, int nstripes, int K, int R) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nstripes) return;
+  const unsigned syn = syndrome[s];
+  const unsigned long long h = hyp[s] & (K >= 64 ? ~0ull : (1ull << K) - 1);
+  hyp[s] = h;
+  unsigned loc;
+  if (syn == 0) loc = kLocateClean;
+  else if (__popc(syn) == 1) loc = static_cast<unsigned>(K + __ffs(static_cast<int>(syn)) - 1);  // one parity row alone
+  else if (syn == (1u << R) - 1 && __popcll(h) == 1) loc = static_cast<unsigned>(__ffsll(h) - 1);
+  else loc = kLocateMany;
+  located[s] = static_cast<unsigned char>(loc);
+  if (counts && syn != 0) atomicAdd(counts + (loc == kLocateMany ? 1 : 0), 1u);
+}
+}  // namespace
+
+hipError_t launch_locate_bytewise(const LocateArgs &a, hipStream_t st) {
+  if (!locate_args_ok(a)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int shape = chk_shape(a.K, a.R);
+  const uint64_t tile = static_cast<uint64_t>(kBlock) * 4 * bw_shape_vw(shape) * bw_shape_it(shape);
+  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
+  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
+  const int grid = default_grid(ntiles);
+  switch (a.R) {
+#define LSEC_LOC_R(RR) case RR: return dispatch_loc_bytewise<RR>(a, st, grid);
+    LSEC_LOC_R(2) LSEC_LOC_R(3) LSEC_LOC_R(4) LSEC_LOC_R(5) LSEC_LOC_R(6) LSEC_LOC_R(7) LSEC_LOC_R(8)
+#undef LSEC_LOC_R
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_locate_bitsliced(const LocateArgs &a, hipStream_t st, int dw_pref) {
+  if (!locate_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  int dw = (dw_pref == 2 || dw_pref == 4) && a.R <= kLocWideRows ? dw_pref : 1;
+  while (dw > 1 && a.packet % (4 * dw) != 0) dw >>= 1;
+  const uint64_t col_bytes = a.size / 8;
+  const uint64_t tile = kBlock * 4ull * dw;
+  const uint64_t ntiles = ((col_bytes + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
+  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
+  const int grid = default_grid(ntiles);
+  switch (a.R) {
+#define LSEC_LOC_R(RR) case RR: return dispatch_loc_bitsliced<RR>(a, st, grid, dw);
+    LSEC_LOC_R(2) LSEC_LOC_R(3) LSEC_LOC_R(4) LSEC_LOC_R(5) LSEC_LOC_R(6) LSEC_LOC_R(7) LSEC_LOC_R(8)
+#undef LSEC_LOC_R
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_locate_finalize(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
+                                  unsigned *counts, int nstripes, int K, int R, hipStream_t st) {
+  if (!syndrome || !hyp || !located || K < 1 || K > kMaxK || R < 2 || R > 8) return hipErrorInvalidValue;
+  if (nstripes <= 0) return hipSuccess;
+  return launch_kernel(&k_locate_finalize, dim3((nstripes + 255) / 256), dim3(256), st, syndrome, hyp, located, counts,
+                       nstripes, K, R);
+}
+
 // ------------------------------------------------------------------ stripe magic (adler32)
 namespace {
 

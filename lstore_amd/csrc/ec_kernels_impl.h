@@ -29,6 +29,7 @@
 #include "ec_kernels.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace lsec {
 
@@ -1485,8 +1486,9 @@ LSEC_DECLARE_PAT_R(5) LSEC_DECLARE_PAT_R(6) LSEC_DECLARE_PAT_R(7) LSEC_DECLARE_P
 // encode stores: k + m chunk reads per stripe and no writes unless a stripe is inconsistent.
 // There is no barrier and no LDS in the tile body: a wave reduces its rows with a wave-wide vote
 // and publishes on its own.
-template <typename Kern>
-hipError_t launch_tiled(Kern *k, int grid, hipStream_t st, CheckArgs a) {
+// (CheckArgs, or LocateArgs, which extends it)
+template <typename Kern, typename Args, typename = typename std::enable_if<std::is_base_of<CheckArgs, Args>::value>::type>
+hipError_t launch_tiled(Kern *k, int grid, hipStream_t st, Args a) {
   // `grid` is the tile count here, as in the ApplyArgs form above
   a.tile_phase = tile_phase_on() && a.nstripes > 0 && grid % a.nstripes == 0 ? static_cast<uint32_t>(grid / a.nstripes / 8) : 0;
   unsigned *slot = tile_queue_slot(st, static_cast<uint64_t>(grid));
@@ -1530,6 +1532,144 @@ __device__ __forceinline__ void chk_publish(const CheckArgs &a, uint32_t s, cons
   }
 }
 
+// lsec_locate_dev (ec_kernels.h, LocateArgs).  The locate kernels are the check kernels over
+// LocateArgs: the tile bodies below end in loc_*_wave instead of chk_publish.  The first vote is
+// the check's, so a wave that saw no difference issues nothing; one that did takes the wave-uniform
+// slow path: it forms the syndromes S_r = acc ^ stored parity in place (the tile's registers are
+// dead after it), tests S_r == Q[r-1][j] * S_0 for every j < K over its lanes' words -- a
+// run-time loop, so its code does not grow with K and its registers are the ones the inputs
+// held -- and reduces each test with a vote into bit j of a mask that starts all ones.  A column
+// with S_0 = 0 and some S_r != 0 fails every j by the same comparison.
+__device__ __forceinline__ void loc_publish(const LocateArgs &a, uint32_t s, uint32_t rows, uint64_t hyp) {
+  const uint32_t first = static_cast<uint32_t>(__builtin_ctzll(__ballot(1)));
+  if ((threadIdx.x & 63u) == first) {
+    atomicOr(a.syndrome + s, rows);
+    if (hyp != ~0ull) atomicAnd(a.hyp + s, static_cast<unsigned long long>(hyp));  // (all ones: nothing to clear)
+  }
+}
+
+template <int R>
+__device__ __forceinline__ uint32_t loc_rows(const uint32_t (&d)[R]) {
+  uint32_t rows = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) rows |= (__ballot(d[r] != 0) != 0 ? 1u : 0u) << r;
+  return rows;
+}
+
+// bytewise: Q[r-1][j] * S_0 through the ratio cells' v_perm tables, as gf_mul_acc multiplies
+template <int R, int IT, int VW>
+__device__ __forceinline__ void loc_bytewise_wave(const LocateArgs &a, uint32_t s, const uint32_t (&d)[R],
+                                                  typename VecT<VW>::type (&acc)[IT][R],
+                                                  const typename VecT<VW>::type (&pv)[R][IT]) {
+  typedef typename VecT<VW>::type V;
+  uint32_t any = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) any |= d[r];
+  if (__ballot(any != 0) == 0) return;  // wave-uniform
+  const uint32_t rows = loc_rows<R>(d);
+  V s0[IT], fa[IT], fb[IT], fc[IT];
+#pragma unroll
+  for (int it = 0; it < IT; ++it) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[it][r] ^= pv[r][it];
+    s0[it] = acc[it][0];
+  }
+  bw_fields<IT, VW>(s0, fa, fb, fc);
+  ConstCell *q = const_cells(a.ratio);
+  const int K = a.K;
+  uint64_t hyp = ~0ull;
+#pragma unroll 1
+  for (int j = 0; j < K; ++j) {
+    uint32_t bad = 0;
+#pragma unroll
+    for (int r = 1; r < R; ++r) {
+      ConstCell *c = q + (r - 1) * K + j;  // wave-uniform -> scalar loads
+      const uint32_t t[6] = {c->ta_lo, c->ta_hi, c->tb_lo, c->tb_hi, c->tc_lo, c->tc_hi};
+#pragma unroll
+      for (int it = 0; it < IT; ++it)
+#pragma unroll
+        for (int e = 0; e < VW; ++e) bad |= gf_mul_acc(acc[it][r][e], fa[it][e], fb[it][e], fc[it][e], t);
+    }
+    if (__ballot(bad != 0) != 0) hyp &= ~(1ull << j);
+  }
+  loc_publish(a, s, rows, hyp);
+}
+
+// bit-sliced: the kernel's doubling loop with S_0 as the input.  Rows r >= 1 hold
+// T_r(j) = S_r ^ Q[r-1][j] * S_0 in place: T_r(j) = T_r(j-1) ^ (Q[r-1][j-1] ^ Q[r-1][j]) * S_0, with
+// Q[r-1][-1] = 0, so a hypothesis costs one pass of the loop and no registers beside the doubled
+// copy of S_0 -- the registers of the tile body's `e`.  AHEAD: the tile body kept the stored rows
+// (pv) and acc holds the re-formed ones; else acc holds the syndromes already.
+template <int R, int DW, bool AHEAD>
+__device__ __forceinline__ void loc_bitsliced_wave(const LocateArgs &a, uint32_t s, const uint32_t (&d)[R],
+                                                   typename VecT<DW>::type (&acc)[R][8],
+                                                   const typename VecT<DW>::type (&pv)[AHEAD ? R : 1][8]) {
+  typedef typename VecT<DW>::type V;
+  uint32_t any = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) any |= d[r];
+  if (__ballot(any != 0) == 0) return;  // wave-uniform
+  const uint32_t rows = loc_rows<R>(d);
+  if constexpr (AHEAD) {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 8; ++x) acc[r][x] ^= pv[r][x];
+  }
+  ConstCell *q = const_cells(a.ratio);
+  const int K = a.K;
+  uint64_t hyp = ~0ull;
+  uint32_t prev[R];
+#pragma unroll
+  for (int r = 1; r < R; ++r) prev[r] = 0;
+#pragma unroll 1
+  for (int j = 0; j < K; ++j) {
+    uint32_t c[R];
+    uint32_t cm = 0;
+#pragma unroll
+    for (int r = 1; r < R; ++r) {
+      const uint32_t cur = q[(r - 1) * K + j].coef;
+      c[r] = prev[r] ^ cur;
+      prev[r] = cur;
+      cm |= c[r];
+    }
+    V e[8];
+#pragma unroll
+    for (int x = 0; x < 8; ++x) e[x] = acc[0][x];
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+#pragma unroll
+      for (int r = 1; r < R; ++r)
+        if ((c[r] >> b) & 1u) {
+#pragma unroll
+          for (int x = 0; x < 8; ++x) acc[r][x] ^= e[x];
+        }
+      if ((cm >> (b + 1)) == 0) break;
+      if (b < 7) {  // e <- 2*e in bit-sliced form
+        const V top = e[7];
+        e[7] = e[6];
+        e[6] = e[5];
+        e[5] = e[4];
+        e[4] = e[3] ^ top;
+        e[3] = e[2] ^ top;
+        e[2] = e[1] ^ top;
+        e[1] = e[0];
+        e[0] = top;
+      }
+    }
+    V bad = 0u;
+#pragma unroll
+    for (int r = 1; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 8; ++x) bad |= acc[r][x];
+    uint32_t b1 = 0;
+#pragma unroll
+    for (int w = 0; w < DW; ++w) b1 |= reinterpret_cast<const uint32_t *>(&bad)[w];
+    if (__ballot(b1 != 0) != 0) hyp &= ~(1ull << j);
+  }
+  loc_publish(a, s, rows, hyp);
+}
+
 // one lane unit of a ragged last tile: C is a multiple of 8, so a 16-byte unit may be half full
 // (its two valid dwords are read, the rest is 0), and a unit wholly past C is 0
 template <int VW>
@@ -1548,8 +1688,9 @@ __device__ __forceinline__ typename VecT<VW>::type chk_load_ragged(uint64_t p, i
 // BF, X0, KC as bytewise_tiles.  A full tile with K fixed has its K*IT data loads and its R*IT
 // parity loads in flight before any arithmetic (the parity rows cost R*IT*VW VGPRs more than the
 // encode: 24 at RS(6+3)); with K at run time the parity loads go out ahead of the first four inputs.
-template <int R, int KC, int IT, bool BF, int VW, bool X0>
-__device__ __forceinline__ void chk_bytewise_tiles(const CheckArgs &a) {
+// Args: CheckArgs, or LocateArgs for the locate kernels (the same tile body up to the last call).
+template <int R, int KC, int IT, bool BF, int VW, bool X0, typename Args>
+__device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
   typedef typename VecT<VW>::type V;
   constexpr int kStep = BwTile<IT, VW>::kStep;
   constexpr int kTile = BwTile<IT, VW>::kBytes;
@@ -1649,13 +1790,14 @@ __device__ __forceinline__ void chk_bytewise_tiles(const CheckArgs &a) {
 #pragma unroll
         for (int e = 0; e < VW; ++e) d[r] = or_diff(acc[it][r][e], pv[r][it][e], d[r]);
     }
-    chk_publish<R>(a, s, d);
+    if constexpr (std::is_same<Args, LocateArgs>::value) loc_bytewise_wave<R, IT, VW>(a, s, d, acc, pv);
+    else chk_publish<R>(a, s, d);
   }, a.tile_phase);
 }
 
 // the XOR-row flag picks one of two whole instantiations, by k_gf8_bytewise's rule
-template <int R, int KC, int IT, bool BF, int VW>
-__global__ __launch_bounds__(kBlock) void k_chk_bytewise(CheckArgs a) {
+template <int R, int KC, int IT, bool BF, int VW, typename Args>
+__device__ __forceinline__ void chk_bytewise_body(const Args &a) {
   if constexpr (BF && R >= 2 && (KC == 0 || KC * R >= 40)) {
     if (const_cells(a.cells)->pad & kCellXorRow) {
       chk_bytewise_tiles<R, KC, IT, BF, VW, true>(a);
@@ -1665,13 +1807,25 @@ __global__ __launch_bounds__(kBlock) void k_chk_bytewise(CheckArgs a) {
   chk_bytewise_tiles<R, KC, IT, BF, VW, false>(a);
 }
 
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_chk_bytewise(CheckArgs a) {
+  chk_bytewise_body<R, KC, IT, BF, VW>(a);
+}
+
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_loc_bytewise(LocateArgs a) {
+  chk_bytewise_body<R, KC, IT, BF, VW>(a);
+}
+
 // k_gf8_bitsliced's lanes and doubling loop.  The stored parity words are loaded ahead of the
 // inputs while they fit beside the accumulators (R * DW <= 8: 8 * R * DW VGPRs), else row by row
 // after them.  Lanes past the end of a ragged last tile leave the tile body (whole waves may).
-template <int R, int DW>
-__global__ __launch_bounds__(kBlock) void k_chk_bitsliced(CheckArgs a) {
+// Args: as chk_bytewise_tiles.
+template <int R, int DW, typename Args>
+__device__ __forceinline__ void chk_bitsliced_tiles(const Args &a) {
   typedef typename VecT<DW>::type V;
   constexpr bool kAhead = R * DW <= 8;
+  constexpr bool kLocate = std::is_same<Args, LocateArgs>::value;
   const int K = a.K;
   const uint32_t P = static_cast<uint32_t>(a.packet);
   const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
@@ -1744,15 +1898,37 @@ __global__ __launch_bounds__(kBlock) void k_chk_bitsliced(CheckArgs a) {
         for (int x = 0; x < 8; ++x) pv[0][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
       }
       d[r] = 0;
+      if constexpr (kLocate && !kAhead) {
+        // the stored row is gone after this: keep the syndrome in the accumulator (one XOR and one
+        // OR per word where the check has one v_bitop3)
 #pragma unroll
-      for (int x = 0; x < 8; ++x)
+        for (int x = 0; x < 8; ++x) {
+          acc[r][x] ^= pv[0][x];
 #pragma unroll
-        for (int w = 0; w < DW; ++w)
-          d[r] = or_diff(reinterpret_cast<const uint32_t *>(&acc[r][x])[w],
-                         reinterpret_cast<const uint32_t *>(&pv[kAhead ? r : 0][x])[w], d[r]);
+          for (int w = 0; w < DW; ++w) d[r] |= reinterpret_cast<const uint32_t *>(&acc[r][x])[w];
+        }
+      } else {
+#pragma unroll
+        for (int x = 0; x < 8; ++x)
+#pragma unroll
+          for (int w = 0; w < DW; ++w)
+            d[r] = or_diff(reinterpret_cast<const uint32_t *>(&acc[r][x])[w],
+                           reinterpret_cast<const uint32_t *>(&pv[kAhead ? r : 0][x])[w], d[r]);
+      }
     }
-    chk_publish<R>(a, s, d);
+    if constexpr (kLocate) loc_bitsliced_wave<R, DW, kAhead>(a, s, d, acc, pv);
+    else chk_publish<R>(a, s, d);
   }, a.tile_phase);
+}
+
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_chk_bitsliced(CheckArgs a) {
+  chk_bitsliced_tiles<R, DW>(a);
+}
+
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_loc_bitsliced(LocateArgs a) {
+  chk_bitsliced_tiles<R, DW>(a);
 }
 
 // The check's launch shape is the encode's automatic one for the same K x R (bytewise_shape in
@@ -1800,8 +1976,49 @@ hipError_t dispatch_chk_bitsliced(const CheckArgs &a, hipStream_t st, int grid, 
   }
 }
 
+// The locate kernels take the check's shape for the same K x R (R >= 2: one row cannot locate).
+// Bit-sliced, the encode's policy gives more than one dword per lane only up to 4 rows
+// (cauchy8_bitsliced_dw), so the wider forms, which would not fit the register file, do not exist.
+constexpr int kLocWideRows = 4;
+template <int R>
+hipError_t dispatch_loc_bytewise(const LocateArgs &a, hipStream_t st, int grid) {
+  static_assert(R >= 2, "locating needs two parity rows");
+  switch (a.K) {
+#define LSEC_LOC_K(KK, IT)                      \
+  case KK:                                      \
+    if constexpr (chk_fixed_k(KK, R, IT, 4))    \
+      return launch_tiled(&k_loc_bytewise<R, KK, IT, true, 4>, grid, st, a); \
+    break;
+    LSEC_LOC_K(4, 2) LSEC_LOC_K(6, 2) LSEC_LOC_K(8, 2) LSEC_LOC_K(10, 2) LSEC_LOC_K(12, 2) LSEC_LOC_K(16, 1) LSEC_LOC_K(20, 1)
+#undef LSEC_LOC_K
+    default: break;
+  }
+  if (chk_shape(a.K, R) == 1) return launch_tiled(&k_loc_bytewise<R, 0, 1, true, 4>, grid, st, a);
+  return launch_tiled(&k_loc_bytewise<R, 0, 2, true, 4>, grid, st, a);
+}
+
+template <int R>
+hipError_t dispatch_loc_bitsliced(const LocateArgs &a, hipStream_t st, int grid, int dw) {
+  static_assert(R >= 2, "locating needs two parity rows");
+  // (more than one dword per lane only up to kLocWideRows rows: launch_locate_bitsliced)
+  if constexpr (R <= kLocWideRows) {
+    if (dw == 4) return launch_tiled(&k_loc_bitsliced<R, 4>, grid, st, a);
+    if (dw == 2) return launch_tiled(&k_loc_bitsliced<R, 2>, grid, st, a);
+  }
+  return dw == 1 ? launch_tiled(&k_loc_bitsliced<R, 1>, grid, st, a) : hipErrorInvalidValue;
+}
+
+// instantiated per R (2..8) in ec_locate_inst.hip
+#define LSEC_DECLARE_LOC_R(RR)                                                                \
+  extern template hipError_t dispatch_loc_bytewise<RR>(const LocateArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_loc_bitsliced<RR>(const LocateArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_LOC
+LSEC_DECLARE_LOC_R(2) LSEC_DECLARE_LOC_R(3) LSEC_DECLARE_LOC_R(4) LSEC_DECLARE_LOC_R(5)
+LSEC_DECLARE_LOC_R(6) LSEC_DECLARE_LOC_R(7) LSEC_DECLARE_LOC_R(8)
+#endif
+
 // instantiated per R in ec_check_inst.hip
-#define LSEC_DECLARE_CHK_R(RR)                                                               \
+#define LSEC_DECLARE_CHK_R(RR)                                                              \
   extern template hipError_t dispatch_chk_bytewise<RR>(const CheckArgs &, hipStream_t, int); \
   extern template hipError_t dispatch_chk_bitsliced<RR>(const CheckArgs &, hipStream_t, int, int);
 #ifndef LSEC_INSTANTIATING_CHK

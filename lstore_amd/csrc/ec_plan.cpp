@@ -1070,6 +1070,133 @@ int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
                           static_cast<uint32_t>(n_shift % n), st);
 }
 
+// ---------------------------------------------------------------- locate
+// lsec_locate_dev: the check's pass, whose differences S_r are the stripe's syndromes.  A wrong
+// data chunk j shows as S_r = Q[r-1][j] * S_0 at every byte column, Q[r-1][j] = g[r][j] / g[0][j]
+// (the ratio image, cached on the plan per device as the encode image is); a wrong parity chunk r
+// as S_r alone.  The accumulate launches (one per 32-bit range of tiles, as check_dev) OR row masks
+// into syndrome and AND hypothesis masks into hyp, both set on the stream ahead of them; one
+// finalize launch behind them writes located and counts.  With LSEC_LOCATE_REPAIR the patterned
+// decode follows on the stream over the k+m single-erasure table, located as its stripe_pattern.
+
+// The host ratio image.  The hypothesis test divides by g[0][j] and tells "row r untouched" from
+// "row r touched" by g[r][j] != 0, so a zero coefficient anywhere is refused.
+int locate_ratio(PlanExt *e, const lsec::gf8::Mat **out) {
+  if (ensure_coding(e)) return -1;
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  const int k = e->pub.data_strips, m = e->pub.parity_strips;
+  if (e->impl->ratio.empty()) {
+    const lsec::gf8::Mat &g = e->impl->coding;
+    if (static_cast<int>(g.size()) != m * k) return fail("lsec_locate_dev: the plan encodes %zu parity rows, m=%d", g.size() / k, m);
+    lsec::gf8::Mat q(static_cast<size_t>(m - 1) * k);
+    for (int r = 0; r < m; ++r)
+      for (int j = 0; j < k; ++j) {
+        if (g[static_cast<size_t>(r) * k + j] == 0)
+          return fail("lsec_locate_dev: coding matrix coefficient [%d][%d] is zero: a data chunk that leaves a parity row "
+                      "untouched cannot be told from that row's own corruption", r, j);
+        if (r > 0) q[static_cast<size_t>(r - 1) * k + j] = lsec::gf8::div(g[static_cast<size_t>(r) * k + j], g[j]);
+      }
+    e->impl->ratio = std::move(q);
+  }
+  *out = &e->impl->ratio;
+  return 0;
+}
+
+namespace {
+
+// the ratio image on the current device: built and uploaded once per plan and device
+int ratio_cells_dev(PlanExt *e, const CoefCell **out) {
+  const lsec::gf8::Mat *q = nullptr;
+  if (locate_ratio(e, &q)) return -1;
+  int dev = 0;
+  HIP_OK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  auto it = e->impl->ratio_cells.find(dev);
+  if (it == e->impl->ratio_cells.end()) {
+    std::vector<CoefCell> h;
+    host_cells(*q, e->pub.parity_strips - 1, e->pub.data_strips, h);
+    CoefCell *d = nullptr;
+    if (upload_cells(h, &d)) return -1;
+    it = e->impl->ratio_cells.emplace(dev, d).first;
+  }
+  *out = it->second;
+  return 0;
+}
+
+}  // namespace
+
+int locate_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned long long *hyp,
+               unsigned char *located, unsigned *counts, int flags, hipStream_t st) {
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("lsec_locate_dev needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  if (k < 1 || k > lsec::kMaxK) return fail("lsec_locate_dev: k=%d outside 1..%d (one launch's inputs, one bit of hyp each)", k, lsec::kMaxK);
+  if (m < 2 || m > 8) return fail("lsec_locate_dev: m=%d outside 2..8 (one parity row cannot locate; one launch's parity rows)", m);
+  if (flags & ~LSEC_LOCATE_REPAIR) return fail("lsec_locate_dev: flags %#x has bits other than LSEC_LOCATE_REPAIR", flags);
+  const bool repair = (flags & LSEC_LOCATE_REPAIR) != 0;
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (check_geometry(p, C)) return -1;
+  if (repair && pattern_limits(p)) return -1;
+  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
+  if (nstripes > 0 && !hyp) return fail("hyp is NULL");
+  if (nstripes > 0 && !located) return fail("located is NULL");
+  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
+  if (reinterpret_cast<uintptr_t>(hyp) % 8 != 0) return fail("hyp %p is not a multiple of 8 bytes", static_cast<void *>(hyp));
+  if (reinterpret_cast<uintptr_t>(counts) % 4 != 0) return fail("counts %p is not a multiple of 4 bytes", static_cast<void *>(counts));
+  const lsec::gf8::Mat *q = nullptr;
+  if (locate_ratio(e, &q)) return -1;  // a zero coefficient is refused here, before any device is touched
+  // the k+m single erasures in chunk order: located[s] is the stripe's pattern id, both sentinels are past the table
+  std::vector<int> singles;
+  for (int i = 0; i < n; ++i) {
+    singles.push_back(i);
+    singles.push_back(-1);
+  }
+  const PatternTable *tab = nullptr;
+  PatternTable::Dev dv;
+  if (repair && pattern_table_dev(e, singles.data(), n, nullptr, 0, &tab, &dv)) return -1;  // cached on the plan
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_cells(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("lsec_locate_dev: the plan encodes %d parity rows, m=%d", R, m);
+  const CoefCell *ratio = nullptr;
+  if (ratio_cells_dev(e, &ratio)) return -1;
+  // the call sets every element itself, stripes of an empty chunk included
+  HIP_OK(hipMemsetAsync(syndrome, 0, sizeof(unsigned) * static_cast<size_t>(nstripes), st));
+  HIP_OK(hipMemsetAsync(hyp, 0xFF, sizeof(unsigned long long) * static_cast<size_t>(nstripes), st));
+  if (counts) HIP_OK(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), st));
+  if (C > 0) {
+    lsec::LocateArgs a;
+    std::memset(static_cast<void *>(&a), 0, sizeof(a));
+    a.cells = static_cast<const CoefCell *>(cells);
+    a.ratio = ratio;
+    a.K = k;
+    a.R = R;
+    a.size = C;
+    a.packet = p->packet_size;
+    const int dw = kind == KBITSLICED ? cauchy8_bitsliced_dw(k, R, C) : 0;  // the check's shape
+    const long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
+    for (long long s0 = 0; s0 < nstripes; s0 += per) {
+      a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
+      a.syndrome = syndrome + s0;
+      a.hyp = hyp + s0;
+      for (int j = 0; j < k; ++j)
+        a.in[j] = {reinterpret_cast<uint64_t>(sh[j].base) + static_cast<uint64_t>(s0) * sh[j].stride, sh[j].stride};
+      for (int r = 0; r < R; ++r)
+        a.par[r] = {reinterpret_cast<uint64_t>(sh[k + r].base) + static_cast<uint64_t>(s0) * sh[k + r].stride, sh[k + r].stride};
+      const hipError_t err = kind == KBITSLICED ? lsec::launch_locate_bitsliced(a, st, dw) : lsec::launch_locate_bytewise(a, st);
+      if (err != hipSuccess) return fail("locate kernel launch failed: %s", hipGetErrorString(err));
+    }
+  }
+  const hipError_t err = lsec::launch_locate_finalize(syndrome, hyp, located, counts, nstripes, k, R, st);
+  if (err != hipSuccess) return fail("locate finalize launch failed: %s", hipGetErrorString(err));
+  if (repair) return enqueue_patterns(e, *tab, dv, sh, nstripes, C, located, 0, 0, st);
+  return 0;
+}
+
 }  // namespace eng
 
 using namespace eng;
@@ -1189,6 +1316,10 @@ void et_destroy_plan(lio_erasure_plan_t *p) {
     }
     for (auto &kv : e->impl->enc_dev_masks) {
       lsec::jit::unbind(kv.second);
+      (void)hipSetDevice(kv.first);
+      (void)hipFree(kv.second);
+    }
+    for (auto &kv : e->impl->ratio_cells) {
       (void)hipSetDevice(kv.first);
       (void)hipFree(kv.second);
     }
@@ -1534,6 +1665,21 @@ int lsec_test_pattern_table(lio_erasure_plan_t *plan, const int *patterns, int n
           tab.cells[rec.cells_off + static_cast<size_t>(r) * k + j].ta_lo != 0)
         return fail("lsec_test_pattern_table: entry %d row %d is not zero", pattern_id, r);
   return 0;
+}
+
+// Test hook, not in include/ (no GPU): Q[r][j] = g[r+1][j] / g[0][j] of the host ratio image that
+// lsec_locate_dev uploads (0 <= r < m-1, 0 <= j < k), or -1 with a message.
+int lsec_test_locate_ratio(lio_erasure_plan_t *plan, int r, int j) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  const int kind = kernel_kind(plan->method, plan->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED) return fail("lsec_test_locate_ratio: plan kernel %d", kind);
+  if (plan->parity_strips < 2) return fail("lsec_test_locate_ratio: m=%d", plan->parity_strips);
+  const lsec::gf8::Mat *q = nullptr;
+  if (locate_ratio(e, &q)) return -1;
+  if (r < 0 || r >= plan->parity_strips - 1 || j < 0 || j >= plan->data_strips)
+    return fail("lsec_test_locate_ratio: [%d][%d] outside %d x %d", r, j, plan->parity_strips - 1, plan->data_strips);
+  return (*q)[static_cast<size_t>(r) * plan->data_strips + j];
 }
 
 // Test hook, not in include/: the rotation of a rotated call's first stripe, as the call computes it

@@ -626,6 +626,16 @@ int lsec_check_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nst
   return check_dev(e, shards, nstripes, block_size, syndrome, bad_count, static_cast<hipStream_t>(stream));
 }
 
+int lsec_locate_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
+                    unsigned int *syndrome, unsigned long long *hyp, unsigned char *located, unsigned int *counts,
+                    int flags, void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!shards) return fail("shards is NULL");
+  if (check_shards(plan, shards, nstripes)) return -1;
+  return locate_dev(e, shards, nstripes, block_size, syndrome, hyp, located, counts, flags, static_cast<hipStream_t>(stream));
+}
+
 int lsec_decode_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
                              const int *patterns, int npatterns, const unsigned char *stripe_pattern, void *stream) {
   PlanExt *e = ext_of(plan);

@@ -81,10 +81,12 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_prepare_decode", "lsec_abi_version", "lsec_device_count", "lsec_last_error", "lsec_plan_kernel",
            "lsec_set_kernel_variant", "lsec_set_host_devices", "lsec_hbm_copy_dev", "lsec_hbm_mix_dev", "lsec_prepare_encode", "lsec_plan_jit", "lsec_device_numa",
            "lsec_set_tile_sharing", "lsec_tile_sharing", "lsec_host_unpin_drain", "lsec_hbm_decode_shape_dev",
-           "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev")
+           "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev", "lsec_locate_dev")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
+# lsec_locate_dev: the two sentinels of located[] and the flag
+LOCATE_CLEAN, LOCATE_MANY, LOCATE_REPAIR = 0xFF, 0xFE, 1
 STRIPE_OK, STRIPE_EMPTY, STRIPE_BAD_MAGIC, STRIPE_REPAIRED, STRIPE_LOST_MAGIC, STRIPE_LOST_MISMATCH = range(6)
 
 
@@ -139,6 +141,9 @@ def lib():
     L.lsec_decode_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
                                           C.c_longlong, C.c_void_p]
     L.lsec_check_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lsec_locate_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_void_p]
+    L.lsec_test_locate_ratio.argtypes = [P, C.c_int, C.c_int]
     L.lsec_test_set_pattern_split.argtypes = [C.c_int]
     L.lsec_test_set_pattern_split.restype = None
     L.lsec_test_pattern_table.argtypes = [P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
@@ -574,6 +579,27 @@ class Plan:
         self.check_dev_refs(refs, n, size, syndrome.data_ptr(), 0 if bad_count is None else bad_count.data_ptr(),
                             _stream_handle(stream))
 
+    def locate_dev_refs(self, refs, nstripes: int, block_size: int, syndrome_ptr: int, hyp_ptr: int, located_ptr: int,
+                        counts_ptr: int = 0, repair: bool = False, stream: int = 0) -> None:
+        """lsec_locate_dev: find (repair: and rebuild in place) the one corrupt chunk of each stripe.  Device
+        addresses: syndrome_ptr, nstripes uint32 (the words of lsec_check_dev); hyp_ptr, nstripes uint64 (bit
+        j: data chunk j alone explains the stripe); located_ptr, nstripes bytes (LOCATE_CLEAN, a chunk id or
+        LOCATE_MANY); counts_ptr, two uint32 (located, LOCATE_MANY; 0: not wanted).  The call sets all of them."""
+        _check(lib().lsec_locate_dev(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                     syndrome_ptr or None, hyp_ptr or None, located_ptr or None, counts_ptr or None,
+                                     LOCATE_REPAIR if repair else 0, stream), "lsec_locate_dev")
+
+    def locate_dev(self, data, parity, syndrome, hyp, located, counts=None, repair=False, stream=None) -> None:
+        """torch: locate in data [N,k,C] / parity [N,m,C]; syndrome: 32-bit device tensor [N], hyp: 64-bit [N],
+        located: uint8 [N], counts: 32-bit [2] or None."""
+        refs, n, size = self.tensor_refs(data, parity)
+        for name, t, item, count in (("syndrome", syndrome, 4, n), ("hyp", hyp, 8, n), ("located", located, 1, n),
+                                     ("counts", counts, 4, 2)):
+            if t is not None and (t.dtype.itemsize != item or not t.is_cuda or not t.is_contiguous() or t.numel() != count):
+                raise ValueError(f"{name} must be a contiguous device tensor of {count} elements of {item} bytes")
+        self.locate_dev_refs(refs, n, size, syndrome.data_ptr(), hyp.data_ptr(), located.data_ptr(),
+                             0 if counts is None else counts.data_ptr(), repair, _stream_handle(stream))
+
     def prepare_decode(self, erasures) -> None:
         _check(lib().lsec_prepare_decode(self._p, _erasure_array(erasures)), "lsec_prepare_decode")
 
@@ -687,3 +713,8 @@ def pattern_table_entry(plan: "Plan", pattern_id: int, patterns=None, lost=None,
 def host_unpin_drain() -> None:
     """lsec_host_unpin_drain: wait until registrations left to the background unpinner are dropped"""
     lib().lsec_host_unpin_drain()
+
+
+def locate_ratio(plan: "Plan", r: int, j: int) -> int:
+    """Test hook (no GPU): Q[r][j] = g[r+1][j] / g[0][j] of the host ratio image lsec_locate_dev uploads."""
+    return _check_nonneg(lib().lsec_test_locate_ratio(plan.ptr, r, j), "lsec_test_locate_ratio")

@@ -10,6 +10,9 @@ The per-stripe-pattern decodes against the single-pattern decode, interleaved on
 
 python tools/kbench.py --check [--rounds R] [--reps N]
 lsec_check_dev against lsec_encode_dev and against encode-and-compare, on the same shapes: see check_bench.
+
+python tools/kbench.py --locate [--rounds R] [--reps N]
+lsec_locate_dev against lsec_check_dev on the same shapes, clean, corrupt and repairing: see locate_bench.
 """
 import argparse
 import os
@@ -241,6 +244,103 @@ def check_bench(a):
         torch.cuda.empty_cache()
 
 
+def locate_bench(a):
+    """The locate five ways, interleaved round by round on the same k+m buffers (one per chunk, C = 1 MiB):
+      (a) lsec_check_dev on consistent stripes          the yardstick: the pass the locate kernels share
+      (b) lsec_locate_dev on consistent stripes         (a) plus the two extra memsets and the finalize launch
+      (c) lsec_locate_dev, every byte of data chunk 0   every wave takes the slow path and publishes
+          of every stripe corrupted
+      (d) lsec_locate_dev with repair, one byte of a    the scrub: each launch is preceded by the torch op that
+          data chunk corrupt in 1 % of the stripes      corrupts those bytes again (inside the timed window)
+      (e) lsec_locate_dev at block_size 0               the memsets and the finalize launch alone
+    (a)'s own min-max over the rounds is the margin (b) is judged by, widened by (e).  Results are checked
+    before timing."""
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    C, N = 1 << 20, a.pattern_stripes
+    for name in a.pattern_codes.split(","):
+        meth, k, m = CONFIGS[name][:3]
+        n = k + m
+        plan = L.Plan.for_chunk(meth, k, m, C)
+        bufs = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(n)]
+        refs = [(b.data_ptr(), C) for b in bufs]
+        plan.encode_dev_refs(refs, N, C, sh)  # consistent parity in buffers k..n-1
+        bad0 = bufs[0] ^ 0xFF  # every byte of data chunk 0 differs
+        bad_refs = [(bad0.data_ptr(), C)] + refs[1:]
+        syn = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        hyp = torch.full((N,), -1, dtype=torch.int64, device=dev)
+        loc = torch.full((N,), 0x7B, dtype=torch.uint8, device=dev)
+        counts = torch.full((2,), -1, dtype=torch.int32, device=dev)
+        one = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        hit = torch.arange(0, N, 100, device=dev)  # 1 % of the stripes
+        jd, col = k // 2, 4097
+        good = bufs[jd][hit, col].clone()
+        outs = (syn.data_ptr(), hyp.data_ptr(), loc.data_ptr(), counts.data_ptr())
+
+        def scrub():
+            bufs[jd][hit, col] = good ^ 0x5A
+            plan.locate_dev_refs(refs, N, C, *outs, True, sh)
+
+        runs = {"a": lambda: plan.check_dev_refs(refs, N, C, syn.data_ptr(), one.data_ptr(), sh),
+                "b": lambda: plan.locate_dev_refs(refs, N, C, *outs, False, sh),
+                "c": lambda: plan.locate_dev_refs(bad_refs, N, C, *outs, False, sh),
+                "d": scrub,
+                "e": lambda: plan.locate_dev_refs(refs, N, 0, *outs, False, sh)}
+        # results first
+        full = (1 << k) - 1
+        runs["b"]()
+        torch.cuda.synchronize()
+        assert int(syn.count_nonzero()) == 0 and bool((hyp == full).all()) and bool((loc == E.LOCATE_CLEAN).all()) \
+            and counts.tolist() == [0, 0], "(b) found a difference in consistent stripes"
+        runs["c"]()
+        torch.cuda.synchronize()
+        assert bool((syn == (1 << m) - 1).all()) and bool((hyp == 1).all()) and bool((loc == 0).all()) \
+            and counts.tolist() == [N, 0], "(c) did not locate chunk 0 everywhere"
+        runs["d"]()
+        torch.cuda.synchronize()
+        assert int(loc[hit].ne(jd).sum()) == 0 and counts.tolist() == [hit.numel(), 0] \
+            and torch.equal(bufs[jd][hit, col], good), "(d) did not repair"
+        runs["a"]()
+        torch.cuda.synchronize()
+        assert int(syn.count_nonzero()) == 0 and int(one) == 0, "(d) left an inconsistent stripe"
+        runs["e"]()
+        torch.cuda.synchronize()
+        assert bool((loc == E.LOCATE_CLEAN).all()) and bool((hyp == full).all())
+        times = {key: [] for key in runs}
+        for _ in range(a.rounds):
+            for key, fn in runs.items():
+                fn()  # warm
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.reps):
+                    fn()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[key].append(e0.elapsed_time(e1) / a.reps)
+        lo, hi = min(times["a"]), max(times["a"])
+        what = {"a": "lsec_check_dev, consistent", "b": "lsec_locate_dev, consistent", "c": "lsec_locate_dev, all corrupt",
+                "d": "corrupt 1 % + locate + repair", "e": "memsets + finalize alone"}
+        med = {key: sorted(ts)[len(ts) // 2] for key, ts in times.items()}
+        for key, ts in times.items():
+            db = n * C * N  # the k+m chunks a pass has to move
+            band = ""
+            if key == "b":
+                top = hi + med["e"]
+                band = ("  inside (a)'s band + (e)" if lo <= med[key] <= top else
+                        f"  {'below' if med[key] < lo else 'above'} (a)'s band + (e) by "
+                        f"{abs(med[key] - (lo if med[key] < lo else top)) / med[key]:.2%}")
+            rate = "" if key == "e" else f"  {db / med[key] / 1e6:7.1f} GB/s ({db / med[key] / 8e9:5.1%} of 8 TB/s)"
+            print(f"{name} N={N} C={C} ({key}) {what[key]:30s} median {med[key]:7.3f} ms  min {min(ts):7.3f}  max {max(ts):7.3f}"
+                  f"{rate}{band}", flush=True)
+        print(f"{name} (a) band: {lo:.3f} .. {hi:.3f} ms ({(hi - lo) / lo:.2%}) over {a.rounds} rounds of {a.reps} launches; "
+              f"(b) - (a) = {med['b'] - med['a']:+.3f} ms, (c)/(b) = {med['c'] / med['b']:.3f}, (d)/(b) = {med['d'] / med['b']:.3f}",
+              flush=True)
+        del bufs, bad0, syn, hyp, loc, counts
+        plan.close()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data-gib", type=float, default=24.0)
@@ -263,7 +363,13 @@ def main():
     ap.add_argument("--check", action="store_true",
                     help="time lsec_check_dev against lsec_encode_dev and encode-and-compare (check_bench; "
                          "--pattern-stripes, --pattern-codes) and exit")
+    ap.add_argument("--locate", action="store_true",
+                    help="time lsec_locate_dev against lsec_check_dev, clean, corrupt and repairing (locate_bench; "
+                         "--pattern-stripes, --pattern-codes) and exit")
     a = ap.parse_args()
+    if a.locate:
+        locate_bench(a)
+        return
     if a.patterns:
         patterns_bench(a)
         return
