@@ -75,18 +75,29 @@ hipError_t by_r(int R, F f) {
   }
 }
 
-// Launch shape for a K x R bytewise launch (codes in ec_kernels_impl.h).  variant 0 = the
-// automatic policy measured with tools/kbench.py (profiles/r01_v6_kbench_branchfree.txt,
-// r01_v10_kbench_xorrow.txt):
-//   R == 1 (single-erasure decode: XOR-heavy, read-bound)  8 B per lane, branchy cells
-//   K >= 16 (VALU-bound wide codes)                          16 B per lane, branch-free: 2 x 16 B
-//                                                            needs 256 VGPRs there (1 wave/SIMD);
-//                                                            RS 20+6 67 %, 16+4 79 % vs 51 / 63 %
-//   otherwise                                                2 x 16 B per lane, branch-free
+// Launch shape for a K x R bytewise launch (codes in ec_kernels_impl.h): an A/B variant when one
+// is set, else the automatic policy (bw_auto_code)
 int bytewise_shape(int K, int R) {
   if (g_bw_variant > 0) return (g_bw_variant - 1) % kBwShapes;
-  if (R == 1) return 4;
-  return K >= 16 ? 1 : 0;
+  return bw_auto_code(K, R);
+}
+
+// The grid of a tile-loop launch: nstripes stripes of `bytes` bytes of tile space each, in tiles
+// of `tile` bytes; grid_blocks > 0 overrides the default of one block per tile.  0: the tile
+// count does not fit the kernels' 32-bit tile index.  (launch_hbm_copy, which has no stripes and
+// hands its tile count to the tile queue, and the compiled networks' launches in ec_jit.cpp
+// keep their own count.)
+int tile_grid(uint64_t tile, uint64_t bytes, int nstripes, int grid_blocks = 0) {
+  const uint64_t ntiles = ((bytes + tile - 1) / tile) * static_cast<uint64_t>(nstripes);
+  if (ntiles >= (1ull << 31)) return 0;
+  return grid_blocks > 0 ? grid_blocks : default_grid(ntiles);
+}
+
+// dwords per lane of a bit-sliced launch: the wanted 2 or 4 while a packet holds whole lanes of them, else 1
+int lane_dwords(int want, int packet) {
+  int dw = want == 2 || want == 4 ? want : 1;
+  while (dw > 1 && packet % (4 * dw) != 0) dw >>= 1;
+  return dw;
 }
 
 // the device of stream st (the current device for the null stream), or -1
@@ -278,20 +289,16 @@ hipError_t launch_bytewise(const ApplyArgs &a, hipStream_t st, int grid_blocks) 
   if (a.K < 1 || a.K > kMaxK || a.R < 1 || a.R > 8 || a.size % 8 != 0) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
   const int shape = a.accumulate ? 1 : bytewise_shape(a.K, a.R);  // as dispatch_bytewise's accumulate launch
-  const uint64_t tile = static_cast<uint64_t>(kBlock) * 4 * bw_shape_vw(shape) * bw_shape_it(shape);
-  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = grid_blocks > 0 ? grid_blocks : default_grid(ntiles);
+  const int grid = tile_grid(bw_shape(shape).tile_bytes(), a.size, a.nstripes, grid_blocks);
+  if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_bytewise<decltype(r)::value>(a, st, grid, shape); });
 }
 
 hipError_t launch_bytewise_magic(const ApplyArgs &a, hipStream_t st, int grid_blocks) {
   if (a.K < 1 || a.K > kMaxK || a.R < 1 || a.R > 8 || a.size % 8 != 0 || !a.magic_acc) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const uint64_t tile = static_cast<uint64_t>(kBlock) * 16 * (a.K >= 16 ? 1 : 2);  // dispatch_bytewise_magic's IT
-  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = grid_blocks > 0 ? grid_blocks : default_grid(ntiles);
+  const int grid = tile_grid(BwShape{bytewise_magic_it(a.K), 4, true}.tile_bytes(), a.size, a.nstripes, grid_blocks);
+  if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_bytewise_magic<decltype(r)::value>(a, st, grid); });
 }
 
@@ -302,13 +309,9 @@ hipError_t launch_bitsliced(const ApplyArgs &a, hipStream_t st, int grid_blocks,
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
   // dwords per lane: the A/B variant when one is set, else the caller's preference (1, 2, 4), else 1
   const int want = g_bs_variant != 0 ? g_bs_variant : dw_pref;
-  int dw = (want == 2 || want == 4) && !a.magic_acc && !a.accumulate ? want : 1;
-  while (dw > 1 && a.packet % (4 * dw) != 0) dw >>= 1;
-  const uint64_t col_bytes = a.size / 8;
-  const uint64_t tile = kBlock * 4ull * dw;
-  const uint64_t ntiles = ((col_bytes + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = grid_blocks > 0 ? grid_blocks : default_grid(ntiles);
+  const int dw = lane_dwords(!a.magic_acc && !a.accumulate ? want : 1, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes, grid_blocks);
+  if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_bitsliced<decltype(r)::value>(a, st, grid, dw); });
 }
 
@@ -328,10 +331,8 @@ hipError_t launch_bitmatrix(const ApplyArgs &a, hipStream_t st, int grid_blocks)
       a.packet <= 0 || a.packet % 4 != 0 || a.size % (static_cast<int64_t>(a.w) * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const uint64_t col_bytes = a.size / a.w;
-  const uint64_t ntiles = ((col_bytes + kBlock * 4 - 1) / (kBlock * 4)) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = grid_blocks > 0 ? grid_blocks : default_grid(ntiles);
+  const int grid = tile_grid(kBlock * 4, a.size / a.w, a.nstripes, grid_blocks);
+  if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_bitmatrix<decltype(r)::value>(a, st, grid); });
 }
 
@@ -343,10 +344,8 @@ hipError_t launch_wordwise(const ApplyArgs &a, hipStream_t st, int grid_blocks) 
   // the mask-per-bit kernel (16 / 8 bytes per lane) beyond that
   // (lsec_set_kernel_variant's second argument 10 selects the mask-per-bit kernel: A/B runs)
   const bool transposed = g_bs_variant != 10 && (a.w == 16 || a.R <= 4);
-  const uint64_t tile = kBlock * (transposed ? 4ull * a.w : a.w == 16 ? 16ull : 8ull);
-  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = grid_blocks > 0 ? grid_blocks : default_grid(ntiles);
+  const int grid = tile_grid(kBlock * (transposed ? 4ull * a.w : a.w == 16 ? 16ull : 8ull), a.size, a.nstripes, grid_blocks);
+  if (!grid) return hipErrorInvalidValue;
   if (transposed) return by_r(a.R, [&](auto r) { return dispatch_gfw_transposed<decltype(r)::value>(a, st, grid); });
   return by_r(a.R, [&](auto r) { return dispatch_wordwise<decltype(r)::value>(a, st, grid); });
 }
@@ -356,10 +355,8 @@ hipError_t launch_gfw_bitsliced(const ApplyArgs &a, hipStream_t st, int grid_blo
       a.packet <= 0 || a.packet % 4 != 0 || a.size % (static_cast<int64_t>(a.w) * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const uint64_t col_bytes = a.size / a.w;
-  const uint64_t ntiles = ((col_bytes + kBlock * 4 - 1) / (kBlock * 4)) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = grid_blocks > 0 ? grid_blocks : default_grid(ntiles);
+  const int grid = tile_grid(kBlock * 4, a.size / a.w, a.nstripes, grid_blocks);
+  if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_gfw_bitsliced<decltype(r)::value>(a, st, grid); });
 }
 
@@ -374,11 +371,8 @@ bool pattern_args_ok(const PatternArgs &a, int rmax) {
 hipError_t launch_pattern_bytewise(const PatternArgs &a, int rmax, hipStream_t st) {
   if (!pattern_args_ok(a, rmax)) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int shape = pat_shape(a.K, rmax);
-  const uint64_t tile = static_cast<uint64_t>(kBlock) * 4 * bw_shape_vw(shape) * bw_shape_it(shape);
-  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = default_grid(ntiles);
+  const int grid = tile_grid(bw_auto(a.K, rmax).tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
   return by_r(rmax, [&](auto r) { return dispatch_pat_bytewise<decltype(r)::value>(a, st, grid); });
 }
 
@@ -386,11 +380,8 @@ hipError_t launch_pattern_bitsliced(const PatternArgs &a, int rmax, hipStream_t 
   if (!pattern_args_ok(a, rmax) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const uint64_t col_bytes = a.size / 8;
-  const uint64_t tile = kBlock * 4ull;
-  const uint64_t ntiles = ((col_bytes + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = default_grid(ntiles);
+  const int grid = tile_grid(kBlock * 4, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
   return by_r(rmax, [&](auto r) { return dispatch_pat_bitsliced<decltype(r)::value>(a, st, grid); });
 }
 
@@ -404,11 +395,8 @@ bool check_args_ok(const CheckArgs &a) {
 hipError_t launch_check_bytewise(const CheckArgs &a, hipStream_t st) {
   if (!check_args_ok(a)) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int shape = chk_shape(a.K, a.R);
-  const uint64_t tile = static_cast<uint64_t>(kBlock) * 4 * bw_shape_vw(shape) * bw_shape_it(shape);
-  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = default_grid(ntiles);
+  const int grid = tile_grid(bw_auto(a.K, a.R).tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_chk_bytewise<decltype(r)::value>(a, st, grid); });
 }
 
@@ -416,13 +404,9 @@ hipError_t launch_check_bitsliced(const CheckArgs &a, hipStream_t st, int dw_pre
   if (!check_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  int dw = dw_pref == 2 || dw_pref == 4 ? dw_pref : 1;
-  while (dw > 1 && a.packet % (4 * dw) != 0) dw >>= 1;
-  const uint64_t col_bytes = a.size / 8;
-  const uint64_t tile = kBlock * 4ull * dw;
-  const uint64_t ntiles = ((col_bytes + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = default_grid(ntiles);
+  const int dw = lane_dwords(dw_pref, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_chk_bitsliced<decltype(r)::value>(a, st, grid, dw); });
 }
 
@@ -452,36 +436,25 @@ __global__ void k_locate_finalize(const unsigned *syndrome, unsigned long long *
 hipError_t launch_locate_bytewise(const LocateArgs &a, hipStream_t st) {
   if (!locate_args_ok(a)) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int shape = chk_shape(a.K, a.R);
-  const uint64_t tile = static_cast<uint64_t>(kBlock) * 4 * bw_shape_vw(shape) * bw_shape_it(shape);
-  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = default_grid(ntiles);
-  switch (a.R) {
-#define LSEC_LOC_R(RR) case RR: return dispatch_loc_bytewise<RR>(a, st, grid);
-    LSEC_LOC_R(2) LSEC_LOC_R(3) LSEC_LOC_R(4) LSEC_LOC_R(5) LSEC_LOC_R(6) LSEC_LOC_R(7) LSEC_LOC_R(8)
-#undef LSEC_LOC_R
-    default: return hipErrorInvalidValue;
-  }
+  const int grid = tile_grid(bw_auto(a.K, a.R).tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) {
+    if constexpr (decltype(r)::value >= 2) return dispatch_loc_bytewise<decltype(r)::value>(a, st, grid);
+    else return hipErrorInvalidValue;  // (one row cannot locate: not instantiated)
+  });
 }
 
 hipError_t launch_locate_bitsliced(const LocateArgs &a, hipStream_t st, int dw_pref) {
   if (!locate_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  int dw = (dw_pref == 2 || dw_pref == 4) && a.R <= kLocWideRows ? dw_pref : 1;
-  while (dw > 1 && a.packet % (4 * dw) != 0) dw >>= 1;
-  const uint64_t col_bytes = a.size / 8;
-  const uint64_t tile = kBlock * 4ull * dw;
-  const uint64_t ntiles = ((col_bytes + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  const int grid = default_grid(ntiles);
-  switch (a.R) {
-#define LSEC_LOC_R(RR) case RR: return dispatch_loc_bitsliced<RR>(a, st, grid, dw);
-    LSEC_LOC_R(2) LSEC_LOC_R(3) LSEC_LOC_R(4) LSEC_LOC_R(5) LSEC_LOC_R(6) LSEC_LOC_R(7) LSEC_LOC_R(8)
-#undef LSEC_LOC_R
-    default: return hipErrorInvalidValue;
-  }
+  const int dw = lane_dwords(a.R <= kLocWideRows ? dw_pref : 1, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) {
+    if constexpr (decltype(r)::value >= 2) return dispatch_loc_bitsliced<decltype(r)::value>(a, st, grid, dw);
+    else return hipErrorInvalidValue;
+  });
 }
 
 hipError_t launch_locate_finalize(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
@@ -790,10 +763,9 @@ hipError_t launch_hbm_copy(void *dst, const void *src, uint64_t bytes, hipStream
 hipError_t launch_hbm_mix(const ApplyArgs &a, hipStream_t st) {
   if (a.K < 1 || a.K > kMaxK || a.R < 1 || a.R > kMaxR || a.size % 8 != 0) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const uint64_t tile = kBlock * 16 * 2;
-  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  return launch_tiled(&k_hbm_mix, default_grid(ntiles), st, a);
+  const int grid = tile_grid(kBlock * 16 * 2, a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return launch_tiled(&k_hbm_mix, grid, st, a);
 }
 
 // variant = IT | G << 4 | REMAP << 8 (IT, G in {1, 2, 4})
@@ -830,19 +802,17 @@ hipError_t launch_gather(const GatherPiece *list, int n, char *dst, hipStream_t 
 hipError_t launch_chunk_diff(const DiffArgs &a, hipStream_t st) {
   if (a.npairs < 1 || a.npairs > kMaxR || a.size % 8 != 0 || !a.flags) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const uint64_t tile = kBlock * 16 * 2;
-  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
-  return launch_kernel(&k_chunk_diff, dim3(default_grid(ntiles)), dim3(kBlock), st, a);
+  const int grid = tile_grid(kBlock * 16 * 2, a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return launch_kernel(&k_chunk_diff, dim3(grid), dim3(kBlock), st, a);
 }
 
 hipError_t launch_stripe_magic(const MagicArgs &a, hipStream_t st) {
   if (a.nshards < 1 || a.nshards > kMaxMagicShards || a.size % 8 != 0) return hipErrorInvalidValue;
-  if (a.nstripes <= 0) return hipSuccess;
-  const uint64_t tile = kBlock * 16 * 2;
-  const uint64_t ntiles = ((a.size + tile - 1) / tile) * static_cast<uint64_t>(a.nstripes);
-  if (ntiles >= (1ull << 31) || a.size == 0) return a.size == 0 ? hipSuccess : hipErrorInvalidValue;
-  return launch_kernel(&k_stripe_magic, dim3(default_grid(ntiles)), dim3(kBlock), st, a);
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int grid = tile_grid(kBlock * 16 * 2, a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return launch_kernel(&k_stripe_magic, dim3(grid), dim3(kBlock), st, a);
 }
 
 hipError_t launch_magic_finalize(const unsigned long long *acc, int nstripes, int64_t total_len, uint8_t *magic,

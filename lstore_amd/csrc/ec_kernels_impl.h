@@ -173,11 +173,12 @@ __device__ __forceinline__ void for_tiles(uint32_t ntiles, unsigned *q, uint32_t
     for (int e = 0; e <= 8; ++e) atomicExch(q + kTileQueueLine * e, 0u);
 }
 
-// A tile-loop kernel over ApplyArgs, launched with a work-sharing tile queue slot and its
-// persistent grid when tile sharing is on (ec_kernels.h), else on `grid` blocks over static eighths.
-template <typename Kern>
-hipError_t launch_tiled(Kern *k, int grid, hipStream_t st, ApplyArgs a) {
-  a.stamps = launch_stamps(&a.nstamps);
+// A tile-loop kernel over ApplyArgs, PatternArgs, CheckArgs or LocateArgs, launched with a
+// work-sharing tile queue slot and its persistent grid when tile sharing is on (ec_kernels.h),
+// else on `grid` blocks over static eighths.
+template <typename Kern, typename Args>
+hipError_t launch_tiled(Kern *k, int grid, hipStream_t st, Args a) {
+  if constexpr (std::is_same<Args, ApplyArgs>::value) a.stamps = launch_stamps(&a.nstamps);
   // `grid` is the tile count here: tiles per stripe = grid / nstripes
   a.tile_phase = tile_phase_on() && a.nstripes > 0 && grid % a.nstripes == 0 ? static_cast<uint32_t>(grid / a.nstripes / 8) : 0;
   unsigned *slot = tile_queue_slot(st, static_cast<uint64_t>(grid));
@@ -233,6 +234,33 @@ struct BwTile {
   static constexpr int kStep = kBlock * 4 * VW;
   static constexpr int kBytes = kStep * IT;
 };
+
+// One lane unit of a ragged last tile, at byte o of a chunk of C bytes.  C is a multiple of 8,
+// so a 16-byte unit may be half full: its two valid dwords are read (the rest is 0) or stored;
+// a unit wholly past C reads as 0 and is not stored.
+template <int VW>
+__device__ __forceinline__ typename VecT<VW>::type load_ragged(uint64_t p, int64_t o, int64_t C) {
+  typename VecT<VW>::type v = 0u;
+  if (o + 4 * VW <= C) {
+    v = *gptr<typename VecT<VW>::type>(p + o);
+  } else if (o < C) {
+    const u32x2 h = *gptr<u32x2>(p + o);
+    v[0] = h.x;
+    v[1] = h.y;
+  }
+  return v;
+}
+template <bool ACC, int VW>
+__device__ __forceinline__ void store_ragged(uint64_t q, int64_t o, int64_t C, typename VecT<VW>::type v) {
+  if (o + 4 * VW <= C) {
+    put<ACC, typename VecT<VW>::type>(q + o, v);
+  } else if (o < C) {
+    u32x2 h;
+    h.x = v[0];
+    h.y = v[1];
+    put<ACC, u32x2>(q + o, h);
+  }
+}
 
 template <int R, int IT, int VW>
 __device__ __forceinline__ void bw_accumulate(typename VecT<VW>::type (&acc)[IT][R],
@@ -405,6 +433,69 @@ __device__ __forceinline__ void bw_magic_out(MagicLane &ml, int K, const typenam
   }
 }
 
+// (on a lambda: inlined before anything else is optimised, as a __forceinline__ function is)
+#define LSEC_INLINE __attribute__((always_inline))
+
+// The input stage of a full bytewise tile: acc[it][r] ^= cells[r][j] * (input j's IT lane units),
+// j = 0 .. K-1.  addr(j) is the address of the lane's first unit of input j.  KC > 0: K fixed at
+// compile time, all K*IT loads in flight before any arithmetic; else four inputs at a time.
+// extra() issues the caller's own loads (the check's stored parity) where they overlap the
+// inputs': behind the data loads with K fixed, ahead of the first group otherwise.
+// BF, X0 as bw_accumulate_bf.  The patterned, check and locate kernels call it; the encode's
+// bytewise_tiles keeps the same stage written out, with the fused stripe magic after each group.
+template <int R, int KC, int IT, int VW, bool BF, bool X0, typename Addr, typename Extra>
+__device__ __forceinline__ void bw_inputs(typename VecT<VW>::type (&acc)[IT][R], ConstCell *cells, int K, Addr &&addr,
+                                          Extra &&extra) {
+  typedef typename VecT<VW>::type V;
+  constexpr int kStep = BwTile<IT, VW>::kStep;
+  if constexpr (KC > 0) {
+    V v[KC][IT];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+      const uint64_t p = addr(j);
+#pragma unroll
+      for (int it = 0; it < IT; ++it) v[j][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
+    }
+    extra();
+    if constexpr (BF) {
+#pragma unroll
+      for (int j = 0; j + 1 < KC; j += 2) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[j], v[j + 1], cells, K, j);
+      if constexpr (KC % 2) bw_accumulate_bf<R, IT, VW, false, X0>(acc, v[KC - 1], v[KC - 1], cells, K, KC - 1);
+    } else {
+#pragma unroll
+      for (int j = 0; j < KC; ++j) bw_accumulate<R, IT, VW>(acc, v[j], cells, K, j);
+    }
+  } else {
+    extra();
+    for (int j0 = 0; j0 < K; j0 += 4) {
+      V v[4][IT];
+      const int nj = min(4, K - j0);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        if (jj < nj) {
+          const uint64_t p = addr(j0 + jj);
+#pragma unroll
+          for (int it = 0; it < IT; ++it) v[jj][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
+        }
+      }
+      if constexpr (BF) {
+        if (nj >= 2) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[0], v[1], cells, K, j0);
+        if (nj == 4) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[2], v[3], cells, K, j0 + 2);
+        if (nj == 1 || nj == 3) bw_accumulate_bf<R, IT, VW, false, X0>(acc, v[nj - 1], v[nj - 1], cells, K, j0 + nj - 1);
+      } else {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+          if (jj < nj) bw_accumulate<R, IT, VW>(acc, v[jj], cells, K, j0 + jj);
+      }
+    }
+  }
+}
+
+// extra() of a caller with no loads of its own
+struct NoLoads {
+  __device__ __forceinline__ void operator()() const {}
+};
+
 // BF = branch-free coefficient path (bw_accumulate_bf).
 // MG = also accumulate the stripe magic of inputs + outputs (encode + je_cksum_calc fused).
 // X0 = row 0 is a plain XOR (see bw_accumulate_bf).
@@ -435,8 +526,10 @@ __device__ __forceinline__ void bytewise_tiles(const ApplyArgs &a) {
     MagicLane ml;  // fused magic partial sums (MG only)
 
     if (full) {
+      // bw_inputs, load_ragged and store_ragged written out: called from here they moved the register
+      // tables of this kernel's forms, 18 of them to a lower occupancy (the branchy forms of two or more
+      // rows: <4, 4, 1, false, 2> 48 -> 86 VGPRs; profiles/tile_bodies_refactor_resources.txt)
       if constexpr (KC > 0) {
-        // all K*IT loads in flight before any arithmetic
         V v[KC][IT];
 #pragma unroll
         for (int j = 0; j < KC; ++j) {
@@ -484,12 +577,11 @@ __device__ __forceinline__ void bytewise_tiles(const ApplyArgs &a) {
         for (int it = 0; it < IT; ++it) put_nt<ACC, V>(q + it * kStep, acc[it][r]);
       }
     } else {
-      // ragged last tile: C is a multiple of 8, so a 16-byte lane unit may be half full
       for (int j = 0; j < K; ++j) {
         const uint64_t p = a.in[j].base + s * a.in[j].stride;
         V v[IT];
 #pragma unroll
-        for (int it = 0; it < IT; ++it) {
+        for (int it = 0; it < IT; ++it) {  // (load_ragged, written out)
           const int64_t o = off0 + it * kStep;
           v[it] = 0u;
           if (o + kLane <= C) {
@@ -510,7 +602,7 @@ __device__ __forceinline__ void bytewise_tiles(const ApplyArgs &a) {
       for (int r = 0; r < R; ++r) {
         const uint64_t q = a.out[r].base + s * a.out[r].stride;
 #pragma unroll
-        for (int it = 0; it < IT; ++it) {
+        for (int it = 0; it < IT; ++it) {  // (store_ragged, written out)
           const int64_t o = off0 + it * kStep;
           if (o + kLane <= C) {
             put<ACC, V>(q + o, acc[it][r]);
@@ -550,6 +642,39 @@ __global__ __launch_bounds__(kBlock) void k_gf8_bytewise(ApplyArgs a) {
 }
 
 // ------------------------------------------------------------------ bitsliced
+// e <- 2*e on the 8 bit slices of GF(2^8) (word x of e = bit x of the lane's elements): a
+// renaming of the slices, the top one XORed into the taps of x^8 = x^4+x^3+x^2+1.
+template <typename V>
+__device__ __forceinline__ void gf8_double_sliced(V (&e)[8]) {
+  const V top = e[7];
+  e[7] = e[6];
+  e[6] = e[5];
+  e[5] = e[4];
+  e[4] = e[3] ^ top;
+  e[3] = e[2] ^ top;
+  e[2] = e[1] ^ top;
+  e[1] = e[0];
+  e[0] = top;
+}
+
+// acc[r] ^= c[r] * e for the rows r = R0 .. R-1, c*e = sum_{t: c_t = 1} 2^t e; e is used up.
+// cm is the OR of those rows' coefficients: no doublings past its highest bit (e.g. the XOR
+// rows of a single-erasure decode stop after bit 0).  The branches are wave-uniform.
+template <int R0, int R, typename V>
+__device__ __forceinline__ void gf8_sliced_mul_acc(V (&acc)[R][8], V (&e)[8], const uint32_t (&c)[R], uint32_t cm) {
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+#pragma unroll
+    for (int r = R0; r < R; ++r)
+      if ((c[r] >> b) & 1u) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) acc[r][x] ^= e[x];
+      }
+    if ((cm >> (b + 1)) == 0) break;
+    if (b < 7) gf8_double_sliced(e);
+  }
+}
+
 // A lane owns DW consecutive dwords of packet-column space in one super-packet and reads
 // the same columns of all 8 packets of every input shard.  MG: also the stripe magic of the
 // inputs and outputs (encode + je_cksum_calc in one pass, as the bytewise kernel does).
@@ -595,27 +720,7 @@ __global__ __launch_bounds__(kBlock) void k_gf8_bitsliced(ApplyArgs a) {
         c[r] = cells[r * K + j].coef;
         cm |= c[r];
       }
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-          if ((c[r] >> b) & 1u) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) acc[r][x] ^= e[x];
-          }
-        if ((cm >> (b + 1)) == 0) break;  // e.g. the XOR rows of a single-erasure decode
-        if (b < 7) {  // e <- 2*e in bit-sliced form
-          const V top = e[7];
-          e[7] = e[6];
-          e[6] = e[5];
-          e[5] = e[4];
-          e[4] = e[3] ^ top;
-          e[3] = e[2] ^ top;
-          e[2] = e[1] ^ top;
-          e[1] = e[0];
-          e[0] = top;
-        }
-      }
+      gf8_sliced_mul_acc<0>(acc, e, c, cm);
     }
     if (valid) {
 #pragma unroll
@@ -858,6 +963,8 @@ __global__ __launch_bounds__(kBlock) void k_gfw_wordwise(ApplyArgs a) {
 // GF(2^W) coefficient matrix (what jerasure_bitmatrix_encode applies), in W XORs per set
 // coefficient bit instead of one per set bitmatrix bit, under R*W uniform branches per input
 // instead of R*W*W.  Coefficients come from the wordwise image (product b = 0 of a cell).
+// (The bit loops below are gf8_sliced_mul_acc's at W slices.  They stay written out: folded
+// into it, k_gfw_bitsliced<4, 32> went from 171 to 194 VGPRs.)
 template <int W>
 __device__ __forceinline__ void times_x_sliced(uint32_t (&e)[W]) {
   const uint32_t top = e[W - 1];
@@ -1078,25 +1185,47 @@ __global__ __launch_bounds__(kBlock) void k_gfw_transposed(ApplyArgs a) {
                             X(18) X(19) X(22) X(23) X(28) X(29) X(30) X(31) X(32)
 
 // ------------------------------------------------------------------ per-R dispatch
+// the K with fixed-K forms of the bytewise kernels (the encode's, the check's and the locate's)
+#define LSEC_FIXED_K(X) X(4) X(6) X(8) X(10) X(12) X(16) X(20)
+
+// Bytewise launch shapes (tile per lane): IT steps of VW dwords, BF the coefficient path.  By code:
+//   0 -> (2, 4) 32 B/lane, branch-free   1 -> (1, 4) 16 B/lane, branch-free
+//   2 -> (2, 2) 16 B/lane in 8 B pieces, branch-free   3 -> (1, 2) 8 B/lane, branch-free
+//   4 -> (1, 2) 8 B/lane, per-cell branches (single-output decodes: mostly XORs of
+//        coefficient-1 inputs, which the branch turns into one v_xor instead of 3 perms)
+struct BwShape {
+  int it, vw;
+  bool bf;
+  constexpr uint64_t tile_bytes() const { return static_cast<uint64_t>(kBlock) * 4 * vw * it; }
+};
+constexpr int kBwShapes = 5;
+constexpr BwShape bw_shape(int code) {
+  return code == 0 ? BwShape{2, 4, true} : code == 1 ? BwShape{1, 4, true} : code == 2 ? BwShape{2, 2, true}
+       : code == 3 ? BwShape{1, 2, true} : BwShape{1, 2, false};
+}
+// The automatic shape of a K x R launch, as a code (measured with tools/kbench.py:
+// profiles/r01_v6_kbench_branchfree.txt, r01_v10_kbench_xorrow.txt); the encode, the patterned
+// decode, the check and the locate all take it, so their tiles and vector widths agree:
+//   R == 1 (single-erasure decode: XOR-heavy, read-bound)  8 B per lane, branchy cells
+//   K >= 16 (VALU-bound wide codes)                          16 B per lane, branch-free: 2 x 16 B
+//                                                            needs 256 VGPRs there (1 wave/SIMD);
+//                                                            RS 20+6 67 %, 16+4 79 % vs 51 / 63 %
+//   otherwise                                                2 x 16 B per lane, branch-free
+constexpr int bw_auto_code(int K, int R) { return R == 1 ? 4 : K >= 16 ? 1 : 0; }
+constexpr BwShape bw_auto(int K, int R) { return bw_shape(bw_auto_code(K, R)); }
+// encode + magic is branch-free at 16 B units for every R: the rule's steps for two or more rows
+constexpr int bytewise_magic_it(int K) { return bw_auto(K, 2).it; }
+
 template <int R, int IT, bool BF, int VW>
 hipError_t bytewise_k(const ApplyArgs &a, hipStream_t st, int grid) {
   switch (a.K) {
 #define LSEC_BW_K(KK) \
   case KK: return launch_tiled(&k_gf8_bytewise<R, KK, IT, BF, VW>, grid, st, a);
-    LSEC_BW_K(4) LSEC_BW_K(6) LSEC_BW_K(8) LSEC_BW_K(10) LSEC_BW_K(12) LSEC_BW_K(16) LSEC_BW_K(20)
+    LSEC_FIXED_K(LSEC_BW_K)
 #undef LSEC_BW_K
     default: return launch_tiled(&k_gf8_bytewise<R, 0, IT, BF, VW>, grid, st, a);
   }
 }
-
-// Bytewise launch shapes (tile per lane):  code -> (IT, VW, coefficient path)
-//   0 -> (2, 4) 32 B/lane, branch-free   1 -> (1, 4) 16 B/lane, branch-free
-//   2 -> (2, 2) 16 B/lane in 8 B pieces, branch-free   3 -> (1, 2) 8 B/lane, branch-free
-//   4 -> (1, 2) 8 B/lane, per-cell branches (single-output decodes: mostly XORs of
-//        coefficient-1 inputs, which the branch turns into one v_xor instead of 3 perms)
-constexpr int kBwShapes = 5;
-inline int bw_shape_it(int shape) { return (shape == 0 || shape == 2) ? 2 : 1; }
-inline int bw_shape_vw(int shape) { return shape <= 1 ? 4 : 2; }
 
 template <int R>
 hipError_t dispatch_bytewise(const ApplyArgs &a, hipStream_t st, int grid, int shape) {
@@ -1112,19 +1241,17 @@ hipError_t dispatch_bytewise(const ApplyArgs &a, hipStream_t st, int grid, int s
   }
 }
 
-// encode + magic: 2 x 16 B per lane, 16 B for K >= 16 (as bytewise_shape; keep in step with
-// bytewise_magic_it in ec_kernels.hip)
+// encode + magic: 2 x 16 B per lane, 16 B for K >= 16 (bytewise_magic_it)
 template <int R>
 hipError_t dispatch_bytewise_magic(const ApplyArgs &a, hipStream_t st, int grid) {
   switch (a.K) {
-#define LSEC_BWM_K(KK, IT) \
-  case KK: return launch_tiled(&k_gf8_bytewise<R, KK, IT, true, 4, true>, grid, st, a);
-    LSEC_BWM_K(4, 2) LSEC_BWM_K(6, 2) LSEC_BWM_K(8, 2) LSEC_BWM_K(10, 2) LSEC_BWM_K(12, 2) LSEC_BWM_K(16, 1) LSEC_BWM_K(20, 1)
+#define LSEC_BWM_K(KK) \
+  case KK: return launch_tiled(&k_gf8_bytewise<R, KK, bytewise_magic_it(KK), true, 4, true>, grid, st, a);
+    LSEC_FIXED_K(LSEC_BWM_K)
 #undef LSEC_BWM_K
     default:
-      if (a.K >= 16) return launch_tiled(&k_gf8_bytewise<R, 0, 1, true, 4, true>, grid, st, a);
-      else return launch_tiled(&k_gf8_bytewise<R, 0, 2, true, 4, true>, grid, st, a);
-      break;
+      if (bytewise_magic_it(a.K) == 1) return launch_tiled(&k_gf8_bytewise<R, 0, 1, true, 4, true>, grid, st, a);
+      return launch_tiled(&k_gf8_bytewise<R, 0, 2, true, 4, true>, grid, st, a);
   }
 }
 
@@ -1218,26 +1345,6 @@ __device__ __forceinline__ uint32_t stripe_pattern_id(const PatternArgs &a, uint
   return (a.rot0 + (s % a.rot_n) * a.rot_step) % a.rot_n;  // rot0, rot_step < rot_n <= kPatMaxShards: 32 bits do
 }
 
-template <typename Kern>
-hipError_t launch_tiled(Kern *k, int grid, hipStream_t st, PatternArgs a) {
-  // `grid` is the tile count here, as in the ApplyArgs form above
-  a.tile_phase = tile_phase_on() && a.nstripes > 0 && grid % a.nstripes == 0 ? static_cast<uint32_t>(grid / a.nstripes / 8) : 0;
-  unsigned *slot = tile_queue_slot(st, static_cast<uint64_t>(grid));
-  a.tiles = nullptr;
-  a.tiles_pre = 0;
-  if (slot) {
-    const int pg = persistent_grid(reinterpret_cast<const void *>(k), grid, st);
-    if (pg > 0) {
-      a.tiles = slot;
-      a.tiles_pre = tiles_prefix(static_cast<uint32_t>(grid));
-      grid = static_cast<int>(8 * a.tiles_pre) + pg;
-    }
-  }
-  const hipError_t e = launch_kernel_shm(k, dim3(grid), dim3(kBlock), occupancy_lds_bytes(a.size), st, a);
-  tile_queue_release(st, slot);
-  return e;
-}
-
 // BF as k_gf8_bytewise: the branch-free coefficient path, or per-cell branches (R = 1).  KC > 0:
 // K fixed at compile time, so a full tile has all its K*IT loads in flight before any arithmetic,
 // as the single-pattern kernel's fixed-K forms have (with four inputs at a time the one-row
@@ -1274,47 +1381,13 @@ __global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
       for (int r = 0; r < R; ++r) acc[it][r] = 0u;
 
     if (full) {
-      if constexpr (KC > 0) {
-        V v[KC][IT];
-#pragma unroll
-        for (int j = 0; j < KC; ++j) {
-          const ShardRef in = a.sh[rec->in_sel[j]];
-          const uint64_t q = in.base + s * in.stride + off0;
-#pragma unroll
-          for (int it = 0; it < IT; ++it) v[j][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
-        }
-        if constexpr (BF) {
-#pragma unroll
-          for (int j = 0; j + 1 < KC; j += 2) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[j], v[j + 1], cells, K, j);
-          if constexpr (KC % 2) bw_accumulate_bf<R, IT, VW, false, false>(acc, v[KC - 1], v[KC - 1], cells, K, KC - 1);
-        } else {
-#pragma unroll
-          for (int j = 0; j < KC; ++j) bw_accumulate<R, IT, VW>(acc, v[j], cells, K, j);
-        }
-      } else {
-        for (int j0 = 0; j0 < K; j0 += 4) {
-          V v[4][IT];
-          const int nj = min(4, K - j0);
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            if (jj < nj) {
-              const ShardRef in = a.sh[rec->in_sel[j0 + jj]];
-              const uint64_t q = in.base + s * in.stride + off0;
-#pragma unroll
-              for (int it = 0; it < IT; ++it) v[jj][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
-            }
-          }
-          if constexpr (BF) {
-            if (nj >= 2) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[0], v[1], cells, K, j0);
-            if (nj == 4) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[2], v[3], cells, K, j0 + 2);
-            if (nj == 1 || nj == 3) bw_accumulate_bf<R, IT, VW, false, false>(acc, v[nj - 1], v[nj - 1], cells, K, j0 + nj - 1);
-          } else {
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-              if (jj < nj) bw_accumulate<R, IT, VW>(acc, v[jj], cells, K, j0 + jj);
-          }
-        }
-      }
+      bw_inputs<R, KC, IT, VW, BF, false>(
+          acc, cells, K,
+          [&](int j) LSEC_INLINE {
+            const ShardRef in = a.sh[rec->in_sel[j]];
+            return in.base + s * in.stride + off0;
+          },
+          NoLoads());
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
@@ -1325,23 +1398,12 @@ __global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
         }
       }
     } else {
-      // ragged last tile: C is a multiple of 8, so a 16-byte lane unit may be half full
       for (int j = 0; j < K; ++j) {
         const ShardRef in = a.sh[rec->in_sel[j]];
         const uint64_t q = in.base + s * in.stride;
         V v[IT];
 #pragma unroll
-        for (int it = 0; it < IT; ++it) {
-          const int64_t o = off0 + it * kStep;
-          v[it] = 0u;
-          if (o + kLane <= C) {
-            v[it] = *gptr<V>(q + o);
-          } else if (o < C) {
-            const u32x2 h = *gptr<u32x2>(q + o);
-            v[it][0] = h.x;
-            v[it][1] = h.y;
-          }
-        }
+        for (int it = 0; it < IT; ++it) v[it] = load_ragged<VW>(q, off0 + it * kStep, C);
         bw_acc1<R, IT, VW, BF, false>(acc, v, cells, K, j);
       }
 #pragma unroll
@@ -1350,17 +1412,7 @@ __global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
           const ShardRef out = a.sh[rec->out_sel[r]];
           const uint64_t q = out.base + s * out.stride;
 #pragma unroll
-          for (int it = 0; it < IT; ++it) {
-            const int64_t o = off0 + it * kStep;
-            if (o + kLane <= C) {
-              put<false, V>(q + o, acc[it][r]);
-            } else if (o < C) {
-              u32x2 h;
-              h.x = acc[it][r][0];
-              h.y = acc[it][r][1];
-              put<false, u32x2>(q + o, h);
-            }
-          }
+          for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
         }
       }
     }
@@ -1411,27 +1463,7 @@ __global__ __launch_bounds__(kBlock) void k_pat_bitsliced(PatternArgs a) {
         c[r] = cells[r * K + j].coef;
         cm |= c[r];
       }
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-          if ((c[r] >> b) & 1u) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) acc[r][x] ^= e[x];
-          }
-        if ((cm >> (b + 1)) == 0) break;
-        if (b < 7) {  // e <- 2*e in bit-sliced form
-          const uint32_t top = e[7];
-          e[7] = e[6];
-          e[6] = e[5];
-          e[5] = e[4];
-          e[4] = e[3] ^ top;
-          e[3] = e[2] ^ top;
-          e[2] = e[1] ^ top;
-          e[1] = e[0];
-          e[0] = top;
-        }
-      }
+      gf8_sliced_mul_acc<0>(acc, e, c, cm);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -1445,23 +1477,20 @@ __global__ __launch_bounds__(kBlock) void k_pat_bitsliced(PatternArgs a) {
   }, a.tile_phase);
 }
 
-// Launch shapes of the patterned bytewise kernel, by the table's row count and K as
-// bytewise_shape picks them for the single-pattern kernel: R == 1 -> 8 B per lane with per-cell
-// branches, K >= 16 -> 16 B per lane, else 2 x 16 B per lane (both branch-free).  The one-row
-// kernel has fixed-K forms for K = 6 and 10; tables of two or more rows run with K at run time:
-// their fixed-K forms, with every input's 2 x 16 B in flight on top of the accumulators, took
-// 186 (K = 6) and 256 (K = 10) VGPRs and measured slower (RS(10+4), three erasures: 17.5 ms
-// against 10.2; profiles/patterns_fixedk_ab.txt).
-inline int pat_shape(int K, int R) { return R == 1 ? 4 : K >= 16 ? 1 : 0; }
-
+// The patterned bytewise kernel takes the automatic shape (bw_auto) of the table's row count and
+// K.  The one-row kernel has fixed-K forms for K = 6 and 10; tables of two or more rows run with
+// K at run time: their fixed-K forms, with every input's 2 x 16 B in flight on top of the
+// accumulators, took 186 (K = 6) and 256 (K = 10) VGPRs and measured slower (RS(10+4), three
+// erasures: 17.5 ms against 10.2; profiles/patterns_fixedk_ab.txt).
 template <int R>
 hipError_t dispatch_pat_bytewise(const PatternArgs &a, hipStream_t st, int grid) {
   if constexpr (R == 1) {
-    if (a.K == 6) return launch_tiled(&k_pat_bytewise<1, 6, 1, 2, false>, grid, st, a);
-    if (a.K == 10) return launch_tiled(&k_pat_bytewise<1, 10, 1, 2, false>, grid, st, a);
-    return launch_tiled(&k_pat_bytewise<1, 0, 1, 2, false>, grid, st, a);
+    constexpr BwShape sh = bw_auto(0, 1);
+    if (a.K == 6) return launch_tiled(&k_pat_bytewise<1, 6, sh.it, sh.vw, sh.bf>, grid, st, a);
+    if (a.K == 10) return launch_tiled(&k_pat_bytewise<1, 10, sh.it, sh.vw, sh.bf>, grid, st, a);
+    return launch_tiled(&k_pat_bytewise<1, 0, sh.it, sh.vw, sh.bf>, grid, st, a);
   } else {
-    if (pat_shape(a.K, R) == 1) return launch_tiled(&k_pat_bytewise<R, 0, 1, 4, true>, grid, st, a);
+    if (bw_auto(a.K, R).it == 1) return launch_tiled(&k_pat_bytewise<R, 0, 1, 4, true>, grid, st, a);
     return launch_tiled(&k_pat_bytewise<R, 0, 2, 4, true>, grid, st, a);
   }
 }
@@ -1486,26 +1515,6 @@ LSEC_DECLARE_PAT_R(5) LSEC_DECLARE_PAT_R(6) LSEC_DECLARE_PAT_R(7) LSEC_DECLARE_P
 // encode stores: k + m chunk reads per stripe and no writes unless a stripe is inconsistent.
 // There is no barrier and no LDS in the tile body: a wave reduces its rows with a wave-wide vote
 // and publishes on its own.
-// (CheckArgs, or LocateArgs, which extends it)
-template <typename Kern, typename Args, typename = typename std::enable_if<std::is_base_of<CheckArgs, Args>::value>::type>
-hipError_t launch_tiled(Kern *k, int grid, hipStream_t st, Args a) {
-  // `grid` is the tile count here, as in the ApplyArgs form above
-  a.tile_phase = tile_phase_on() && a.nstripes > 0 && grid % a.nstripes == 0 ? static_cast<uint32_t>(grid / a.nstripes / 8) : 0;
-  unsigned *slot = tile_queue_slot(st, static_cast<uint64_t>(grid));
-  a.tiles = nullptr;
-  a.tiles_pre = 0;
-  if (slot) {
-    const int pg = persistent_grid(reinterpret_cast<const void *>(k), grid, st);
-    if (pg > 0) {
-      a.tiles = slot;
-      a.tiles_pre = tiles_prefix(static_cast<uint32_t>(grid));
-      grid = static_cast<int>(8 * a.tiles_pre) + pg;
-    }
-  }
-  const hipError_t e = launch_kernel_shm(k, dim3(grid), dim3(kBlock), occupancy_lds_bytes(a.size), st, a);
-  tile_queue_release(st, slot);
-  return e;
-}
 
 // d |= x ^ y in one VALU op (v_bitop3_b32, truth table (a ^ b) | c = 0xBE)
 __device__ __forceinline__ uint32_t or_diff(uint32_t x, uint32_t y, uint32_t d) {
@@ -1636,27 +1645,7 @@ __device__ __forceinline__ void loc_bitsliced_wave(const LocateArgs &a, uint32_t
     V e[8];
 #pragma unroll
     for (int x = 0; x < 8; ++x) e[x] = acc[0][x];
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-#pragma unroll
-      for (int r = 1; r < R; ++r)
-        if ((c[r] >> b) & 1u) {
-#pragma unroll
-          for (int x = 0; x < 8; ++x) acc[r][x] ^= e[x];
-        }
-      if ((cm >> (b + 1)) == 0) break;
-      if (b < 7) {  // e <- 2*e in bit-sliced form
-        const V top = e[7];
-        e[7] = e[6];
-        e[6] = e[5];
-        e[5] = e[4];
-        e[4] = e[3] ^ top;
-        e[3] = e[2] ^ top;
-        e[2] = e[1] ^ top;
-        e[1] = e[0];
-        e[0] = top;
-      }
-    }
+    gf8_sliced_mul_acc<1>(acc, e, c, cm);  // (c[0] is not read)
     V bad = 0u;
 #pragma unroll
     for (int r = 1; r < R; ++r)
@@ -1668,21 +1657,6 @@ __device__ __forceinline__ void loc_bitsliced_wave(const LocateArgs &a, uint32_t
     if (__ballot(b1 != 0) != 0) hyp &= ~(1ull << j);
   }
   loc_publish(a, s, rows, hyp);
-}
-
-// one lane unit of a ragged last tile: C is a multiple of 8, so a 16-byte unit may be half full
-// (its two valid dwords are read, the rest is 0), and a unit wholly past C is 0
-template <int VW>
-__device__ __forceinline__ typename VecT<VW>::type chk_load_ragged(uint64_t p, int64_t o, int64_t C) {
-  typename VecT<VW>::type v = 0u;
-  if (o + 4 * VW <= C) {
-    v = *gptr<typename VecT<VW>::type>(p + o);
-  } else if (o < C) {
-    const u32x2 h = *gptr<u32x2>(p + o);
-    v[0] = h.x;
-    v[1] = h.y;
-  }
-  return v;
 }
 
 // BF, X0, KC as bytewise_tiles.  A full tile with K fixed has its K*IT data loads and its R*IT
@@ -1713,57 +1687,16 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
       for (int r = 0; r < R; ++r) acc[it][r] = 0u;
 
     if (full) {
-      if constexpr (KC > 0) {
-        V v[KC][IT];
+      bw_inputs<R, KC, IT, VW, BF, X0>(
+          acc, cells, K, [&](int j) LSEC_INLINE { return a.in[j].base + s * a.in[j].stride + off0; },
+          [&]() LSEC_INLINE {
 #pragma unroll
-        for (int j = 0; j < KC; ++j) {
-          const uint64_t p = a.in[j].base + s * a.in[j].stride + off0;
+            for (int r = 0; r < R; ++r) {
+              const uint64_t q = a.par[r].base + s * a.par[r].stride + off0;
 #pragma unroll
-          for (int it = 0; it < IT; ++it) v[j][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          const uint64_t q = a.par[r].base + s * a.par[r].stride + off0;
-#pragma unroll
-          for (int it = 0; it < IT; ++it) pv[r][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
-        }
-        if constexpr (BF) {
-#pragma unroll
-          for (int j = 0; j + 1 < KC; j += 2) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[j], v[j + 1], cells, K, j);
-          if constexpr (KC % 2) bw_accumulate_bf<R, IT, VW, false, X0>(acc, v[KC - 1], v[KC - 1], cells, K, KC - 1);
-        } else {
-#pragma unroll
-          for (int j = 0; j < KC; ++j) bw_accumulate<R, IT, VW>(acc, v[j], cells, K, j);
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          const uint64_t q = a.par[r].base + s * a.par[r].stride + off0;
-#pragma unroll
-          for (int it = 0; it < IT; ++it) pv[r][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
-        }
-        for (int j0 = 0; j0 < K; j0 += 4) {
-          V v[4][IT];
-          const int nj = min(4, K - j0);
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            if (jj < nj) {
-              const uint64_t p = a.in[j0 + jj].base + s * a.in[j0 + jj].stride + off0;
-#pragma unroll
-              for (int it = 0; it < IT; ++it) v[jj][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
+              for (int it = 0; it < IT; ++it) pv[r][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
             }
-          }
-          if constexpr (BF) {
-            if (nj >= 2) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[0], v[1], cells, K, j0);
-            if (nj == 4) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[2], v[3], cells, K, j0 + 2);
-            if (nj == 1 || nj == 3) bw_accumulate_bf<R, IT, VW, false, X0>(acc, v[nj - 1], v[nj - 1], cells, K, j0 + nj - 1);
-          } else {
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-              if (jj < nj) bw_accumulate<R, IT, VW>(acc, v[jj], cells, K, j0 + jj);
-          }
-        }
-      }
+          });
     } else {
       // ragged last tile: zero-filled inputs give zero parity there, and the stored parity is
       // zero-filled the same way, so bytes past C never show as a difference
@@ -1771,14 +1704,14 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
         const uint64_t p = a.in[j].base + s * a.in[j].stride;
         V v[IT];
 #pragma unroll
-        for (int it = 0; it < IT; ++it) v[it] = chk_load_ragged<VW>(p, off0 + it * kStep, C);
+        for (int it = 0; it < IT; ++it) v[it] = load_ragged<VW>(p, off0 + it * kStep, C);
         bw_acc1<R, IT, VW, BF, X0>(acc, v, cells, K, j);
       }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const uint64_t q = a.par[r].base + s * a.par[r].stride;
 #pragma unroll
-        for (int it = 0; it < IT; ++it) pv[r][it] = chk_load_ragged<VW>(q, off0 + it * kStep, C);
+        for (int it = 0; it < IT; ++it) pv[r][it] = load_ragged<VW>(q, off0 + it * kStep, C);
       }
     }
     uint32_t d[R];
@@ -1867,27 +1800,7 @@ __device__ __forceinline__ void chk_bitsliced_tiles(const Args &a) {
         c[r] = cells[r * K + j].coef;
         cm |= c[r];
       }
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-          if ((c[r] >> b) & 1u) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) acc[r][x] ^= e[x];
-          }
-        if ((cm >> (b + 1)) == 0) break;
-        if (b < 7) {  // e <- 2*e in bit-sliced form
-          const V top = e[7];
-          e[7] = e[6];
-          e[6] = e[5];
-          e[5] = e[4];
-          e[4] = e[3] ^ top;
-          e[3] = e[2] ^ top;
-          e[2] = e[1] ^ top;
-          e[1] = e[0];
-          e[0] = top;
-        }
-      }
+      gf8_sliced_mul_acc<0>(acc, e, c, cm);
     }
     uint32_t d[R];
 #pragma unroll
@@ -1931,40 +1844,46 @@ __global__ __launch_bounds__(kBlock) void k_loc_bitsliced(LocateArgs a) {
   chk_bitsliced_tiles<R, DW>(a);
 }
 
-// The check's launch shape is the encode's automatic one for the same K x R (bytewise_shape in
-// ec_kernels.hip, without its A/B variants): R == 1 -> 8 B per lane with per-cell branches,
-// K >= 16 -> 16 B per lane, else 2 x 16 B per lane (both branch-free), so tile sizes and vector
-// widths match lsec_encode_dev's; fixed-K forms for the K the encode has them for.
-inline int chk_shape(int K, int R) { return R == 1 ? 4 : K >= 16 ? 1 : 0; }
+// The check's launch shape is the encode's automatic one for the same K x R (bw_auto, without
+// bytewise_shape's A/B variants), so tile sizes and vector widths match lsec_encode_dev's;
+// fixed-K forms for the K the encode has them for.
 // A fixed-K form holds K data units, R stored-parity units and R accumulators per step: past 160
 // such dwords (RS(12+8) at 2 x 16 B: 224) it would fill the register file (256 VGPRs and copies in
 // AGPRs), so those stripes run with K at run time, four inputs in flight at a time.
 constexpr bool chk_fixed_k(int K, int R, int IT, int VW) { return (K + 2 * R) * IT * VW <= 160; }
 
+// the check kernel of CheckArgs, the locate kernel of LocateArgs
+template <int R, int KC, int IT, bool BF, int VW, typename Args>
+hipError_t chk_or_loc_kernel(const Args &a, hipStream_t st, int grid) {
+  if constexpr (std::is_same<Args, LocateArgs>::value) return launch_tiled(&k_loc_bytewise<R, KC, IT, BF, VW>, grid, st, a);
+  else return launch_tiled(&k_chk_bytewise<R, KC, IT, BF, VW>, grid, st, a);
+}
+
+template <int R, typename Args>
+hipError_t chk_bytewise_k(const Args &a, hipStream_t st, int grid) {
+  switch (a.K) {
+#define LSEC_CHK_K(KK)                                                                          \
+  case KK: {                                                                                    \
+    constexpr BwShape sh = bw_auto(KK, R);                                                      \
+    if constexpr (chk_fixed_k(KK, R, sh.it, sh.vw))                                             \
+      return chk_or_loc_kernel<R, KK, sh.it, sh.bf, sh.vw>(a, st, grid);                      \
+    break;                                                                                      \
+  }
+    LSEC_FIXED_K(LSEC_CHK_K)
+#undef LSEC_CHK_K
+    default: break;
+  }
+  if constexpr (R == 1) {
+    return chk_or_loc_kernel<1, 0, 1, false, 2>(a, st, grid);
+  } else {
+    if (bw_auto(a.K, R).it == 1) return chk_or_loc_kernel<R, 0, 1, true, 4>(a, st, grid);
+    return chk_or_loc_kernel<R, 0, 2, true, 4>(a, st, grid);
+  }
+}
+
 template <int R>
 hipError_t dispatch_chk_bytewise(const CheckArgs &a, hipStream_t st, int grid) {
-  if constexpr (R == 1) {
-    switch (a.K) {
-#define LSEC_CHK_K(KK) \
-  case KK: return launch_tiled(&k_chk_bytewise<1, KK, 1, false, 2>, grid, st, a);
-      LSEC_CHK_K(4) LSEC_CHK_K(6) LSEC_CHK_K(8) LSEC_CHK_K(10) LSEC_CHK_K(12) LSEC_CHK_K(16) LSEC_CHK_K(20)
-#undef LSEC_CHK_K
-      default: return launch_tiled(&k_chk_bytewise<1, 0, 1, false, 2>, grid, st, a);
-    }
-  } else {
-    switch (a.K) {
-#define LSEC_CHK_K(KK, IT)                      \
-  case KK:                                      \
-    if constexpr (chk_fixed_k(KK, R, IT, 4))    \
-      return launch_tiled(&k_chk_bytewise<R, KK, IT, true, 4>, grid, st, a); \
-    break;
-      LSEC_CHK_K(4, 2) LSEC_CHK_K(6, 2) LSEC_CHK_K(8, 2) LSEC_CHK_K(10, 2) LSEC_CHK_K(12, 2) LSEC_CHK_K(16, 1) LSEC_CHK_K(20, 1)
-#undef LSEC_CHK_K
-      default: break;
-    }
-    if (chk_shape(a.K, R) == 1) return launch_tiled(&k_chk_bytewise<R, 0, 1, true, 4>, grid, st, a);
-    return launch_tiled(&k_chk_bytewise<R, 0, 2, true, 4>, grid, st, a);
-  }
+  return chk_bytewise_k<R>(a, st, grid);
 }
 
 template <int R>
@@ -1983,18 +1902,7 @@ constexpr int kLocWideRows = 4;
 template <int R>
 hipError_t dispatch_loc_bytewise(const LocateArgs &a, hipStream_t st, int grid) {
   static_assert(R >= 2, "locating needs two parity rows");
-  switch (a.K) {
-#define LSEC_LOC_K(KK, IT)                      \
-  case KK:                                      \
-    if constexpr (chk_fixed_k(KK, R, IT, 4))    \
-      return launch_tiled(&k_loc_bytewise<R, KK, IT, true, 4>, grid, st, a); \
-    break;
-    LSEC_LOC_K(4, 2) LSEC_LOC_K(6, 2) LSEC_LOC_K(8, 2) LSEC_LOC_K(10, 2) LSEC_LOC_K(12, 2) LSEC_LOC_K(16, 1) LSEC_LOC_K(20, 1)
-#undef LSEC_LOC_K
-    default: break;
-  }
-  if (chk_shape(a.K, R) == 1) return launch_tiled(&k_loc_bytewise<R, 0, 1, true, 4>, grid, st, a);
-  return launch_tiled(&k_loc_bytewise<R, 0, 2, true, 4>, grid, st, a);
+  return chk_bytewise_k<R>(a, st, grid);
 }
 
 template <int R>
@@ -2038,5 +1946,7 @@ LSEC_DECLARE_CHK_R(5) LSEC_DECLARE_CHK_R(6) LSEC_DECLARE_CHK_R(7) LSEC_DECLARE_C
 LSEC_DECLARE_R(1) LSEC_DECLARE_R(2) LSEC_DECLARE_R(3) LSEC_DECLARE_R(4)
 LSEC_DECLARE_R(5) LSEC_DECLARE_R(6) LSEC_DECLARE_R(7) LSEC_DECLARE_R(8)
 #endif
+
+#undef LSEC_INLINE
 
 }  // namespace lsec

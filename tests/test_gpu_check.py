@@ -29,11 +29,13 @@ CODES = {
     "raid4_61": (L.RAID4, 6, 1, 0),           # R = 1: 8 B per lane, per-cell branches
     "r6_62": (L.REED_SOL_R6_OP, 6, 2, 0),
     "rs128": (L.REED_SOL_VAN, 12, 8, 0),      # bit 7 must be reachable; K at run time
+    "rs52": (L.REED_SOL_VAN, 5, 2, 0),        # K at run time, odd: the four-at-a-time input loop ends in one input
+    "rs73": (L.REED_SOL_VAN, 7, 3, 0),        # ... and in three
     "cg63": (L.CAUCHY_GOOD, 6, 3, 8),         # bit-sliced
     "co42": (L.CAUCHY_ORIG, 4, 2, 8),
     "cg164": (L.CAUCHY_GOOD, 16, 4, 8),       # bit-sliced at the encode's 4 (2 at packet 8) dwords per lane
 }
-BYTEWISE = ("rs63", "rs164", "raid4_61", "r6_62", "rs128")
+BYTEWISE = ("rs63", "rs164", "raid4_61", "r6_62", "rs128", "rs52", "rs73")
 SLICED = ("cg63", "co42", "cg164")
 # a single half lane, one lane, one full 8 KiB tile, a tile + a half-lane tail, three tiles, three tiles + a tail
 BYTEWISE_SIZES = (8, 16, 8192, 8200, 24576, 24584)

@@ -26,8 +26,8 @@ import test_gpu_check as TC
 
 pytestmark = pytest.mark.gpu
 
-CODES = {c: TC.CODES[c] for c in ("rs63", "rs164", "r6_62", "rs128", "cg63", "co42", "cg164")}
-BYTEWISE = ("rs63", "rs164", "r6_62", "rs128")
+CODES = {c: TC.CODES[c] for c in ("rs63", "rs164", "r6_62", "rs128", "rs52", "rs73", "cg63", "co42", "cg164")}
+BYTEWISE = ("rs63", "rs164", "r6_62", "rs128", "rs52", "rs73")
 # test_gpu_check.py explains the shapes: a half lane, a lane, one 8 KiB tile, a tile + a half-lane tail,
 # three tiles + a tail; bit-sliced one super-packet, a ragged column tile, 1.5 tiles (k >= 16: 4 dwords per lane)
 BYTEWISE_SIZES = (8, 16, 8192, 8200, 24584)

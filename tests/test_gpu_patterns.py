@@ -175,6 +175,24 @@ def test_rs104_zero_to_four_erasures(cuda):
         run_patterned(torch, p, full, ones, seeded_ids(nstr, len(ones), 3))
 
 
+# ---------------------------------------------------------------- 2b: odd K, the tail of the run-time-K input loop
+@pytest.mark.parametrize("k,m", [(5, 2), (7, 3)])
+def test_odd_k_runtime_input_tail(cuda, k, m):
+    """K = 5 and 7 at run time: the full tiles' four-at-a-time input loop ends in a group of one and
+    of three inputs.  C = 8200 is one full 8 KiB tile plus a half-filled lane for the tables of up to
+    two erasures, and four full 2 KiB tiles plus 8 bytes for the one-row kernel."""
+    import torch
+
+    size, nstr, n = 8200, 19, k + m
+    pats = [[], [0], [k - 1], [k], [n - 1], [0, k - 1], [1, k], [k, n - 1]]
+    full = reference_stripes(L.REED_SOL_VAN, k, m, size, nstr)
+    with make_plan(L.REED_SOL_VAN, k, m, size) as p:
+        run_patterned(torch, p, full, pats, seeded_ids(nstr, len(pats), 10))
+        # a table of single erasures only: the one-row branchy kernel
+        ones = [[0], [k // 2], [k - 1], [k]]
+        run_patterned(torch, p, full, ones, seeded_ids(nstr, len(ones), 11))
+
+
 # ---------------------------------------------------------------- 3: r6 and raid4
 def test_r6_and_raid4(cuda):
     import torch
