@@ -249,6 +249,55 @@ int lsec_locate_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int ns
                     long long block_size, unsigned int *syndrome, unsigned long long *hyp,
                     unsigned char *located, unsigned int *counts, int flags, void *stream);
 
+/* Check, locate and repair over the PHYSICAL devices of a rotated LUN, one pass: the scrub of a
+ * LUN whose stripes do not share a chunk-to-device map, and the answer to its question, which
+ * disk is going bad.  Purely additive too: the version stays 3, a caller detects the calls by
+ * their symbols.
+ *
+ * - devs[i] (i < k+m) is physical device i, exactly as for lsec_decode_dev_rotated.  With
+ *   rot_s = ((first_stripe + s) * n_shift) mod (k+m), logical chunk c of stripe s is read from
+ *   devs[(c - rot_s) mod (k+m)].  n_shift >= k+m is taken mod k+m; n_shift < 0 and
+ *   first_stripe < 0 return -1; first_stripe may be anything up to 2^63 - 1.
+ * - syndrome, bad_count, hyp, located and counts are exactly what lsec_check_dev /
+ *   lsec_locate_dev produce for the logical view of each stripe: bits and ids are logical (parity
+ *   row r, data chunk j, k + r), the sentinels are the same, and n_shift == 0 behaves exactly as
+ *   the unrotated calls.
+ * - located_dev is optional (may be NULL): nstripes bytes, no alignment requirement.
+ *   located_dev[s] is the physical device holding the located chunk, (located[s] - rot_s) mod
+ *   (k+m); LSEC_LOCATE_CLEAN and LSEC_LOCATE_MANY pass through unchanged.
+ * - dev_faults is optional (may be NULL): k+m 32-bit words, 4-byte aligned.  dev_faults[i] is the
+ *   number of stripes of this call whose located chunk lives on device i; clean and
+ *   LSEC_LOCATE_MANY stripes count nowhere.
+ * - The calls set every output themselves (memsets on `stream` ahead of the kernels) and do not
+ *   add to what was there.  Nothing is allocated per call and no scratch is shared between streams.
+ * - flags & LSEC_LOCATE_REPAIR: behind the locate, on the same stream, every located chunk is
+ *   rebuilt in place, with the bytes lsec_decode_dev_rotated writes for that stripe with
+ *   lost = {located_dev[s]}.  Clean and LSEC_LOCATE_MANY stripes are neither read again nor
+ *   written.  Without the flag the devices are only read.
+ * - Plans and limits are those of lsec_check_dev / lsec_locate_dev: lsec_plan_kernel 1 and 2,
+ *   k <= 64, m 1..8 for the check and 2..8 for the locate, no zero coefficient in the coding
+ *   matrix.  LSEC_LOCATE_REPAIR adds no further limit: the repair works each stripe's rotation
+ *   out in the kernel over one k+m single-erasure table, so RS(16+4) at n_shift = 1 repairs.
+ * - Layout, alignment and block_size rules are those of lsec_check_dev; syndrome, counts and
+ *   dev_faults must be 4-byte aligned, hyp 8-byte aligned.  None of the outputs may overlap the
+ *   devices.
+ * - nstripes == 0 validates the arguments, returns 0 and touches no GPU (the outputs may then be
+ *   NULL); with LSEC_LOCATE_REPAIR it also prepares the single-erasure tables, as lsec_locate_dev
+ *   does (on a host without a GPU the tables are built and dropped: there is nowhere to upload).
+ * - Every refusal returns -1 with a message for lsec_last_error that names the limit, and nothing
+ *   is enqueued.  There is no fallback.
+ * Enqueued on `stream`; return without synchronising.  0 / -1. */
+int lsec_check_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                           long long block_size, int n_shift, long long first_stripe,
+                           unsigned int *syndrome, unsigned int *bad_count, void *stream);
+
+int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                            long long block_size, int n_shift, long long first_stripe,
+                            unsigned int *syndrome, unsigned long long *hyp,
+                            unsigned char *located, unsigned char *located_dev,
+                            unsigned int *counts, unsigned int *dev_faults,
+                            int flags, void *stream);
+
 /* Per-stripe "magic": the 4-byte little-endian zlib adler32 over the concatenation of a
  * stripe's k+m chunks that LStore's erasure segment stores in front of every chunk
  * (je_cksum_calc, src/lio/segment/jerasure.c:169-182; checked by je_cksum_compare, :188-194).

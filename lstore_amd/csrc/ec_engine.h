@@ -154,6 +154,12 @@ int check_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, uns
 int locate_ratio(PlanExt *e, const lsec::gf8::Mat **out);  // the host ratio image; no device is touched
 int locate_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned long long *hyp,
                unsigned char *located, unsigned *counts, int flags, hipStream_t st);
+// both over the k+m physical devices of a rotated LUN (devs[i]: device i, as decode_dev_rotated's)
+int check_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                      unsigned *syndrome, unsigned *bad_count, hipStream_t st);
+int locate_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                       unsigned *syndrome, unsigned long long *hyp, unsigned char *located, unsigned char *located_dev,
+                       unsigned *counts, unsigned *dev_faults, int flags, hipStream_t st);
 // stripes that do not share an erasure pattern, one launch per 32-bit range of tiles
 int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift, PatternTable &tab);
 uint32_t pattern_rot0(int n, int n_shift, long long first_stripe);

@@ -209,6 +209,58 @@ hipError_t launch_locate_bitsliced(const LocateArgs &a, hipStream_t stream, int 
 hipError_t launch_locate_finalize(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
                                   unsigned *counts, int nstripes, int K, int R, hipStream_t stream);
 
+// Check, locate and repair over the physical devices of a rotated LUN (lsec_check_dev_rotated /
+// lsec_locate_dev_rotated).  The arithmetic, the tile loops and the launch shapes are the check's
+// and the locate's; what differs is where a tile takes its shard refs from.  With
+// rot_s = (rot0 + s * rot_step) mod rot_n the rotation of stripe s, logical chunk c (data chunk j:
+// c = j, parity row r: c = K + r) is read from sh[(c - rot_s) mod rot_n].  s is uniform over the
+// workgroup, so rot_s and the index stay scalar and the refs come by dynamic-offset scalar loads
+// from the kernel arguments, as the patterned decode takes its refs.  Argument structs of their
+// own: CheckArgs, LocateArgs and PatternArgs keep their layout.
+constexpr int kRotMaxShards = kMaxK + 8;  // k <= kMaxK data chunks, m <= 8 parity rows
+struct CheckRotArgs {
+  const CoefCell *cells;  // as CheckArgs, up to tile_phase
+  int K, R;
+  int nstripes;
+  int packet;
+  int64_t size;
+  unsigned *syndrome;
+  unsigned *bad_count;
+  unsigned *tiles;
+  uint32_t tiles_pre;
+  uint32_t tile_phase;
+  uint32_t rot0, rot_step, rot_n;  // rot0, rot_step < rot_n = K + R
+  ShardRef sh[kRotMaxShards];      // the K + R physical devices
+};
+
+struct LocateRotArgs : CheckRotArgs {
+  const CoefCell *ratio;      // as LocateArgs
+  unsigned long long *hyp;
+};
+
+hipError_t launch_check_rot_bytewise(const CheckRotArgs &a, hipStream_t stream);
+hipError_t launch_check_rot_bitsliced(const CheckRotArgs &a, hipStream_t stream, int dw_pref = 0);
+hipError_t launch_locate_rot_bytewise(const LocateRotArgs &a, hipStream_t stream);
+hipError_t launch_locate_rot_bitsliced(const LocateRotArgs &a, hipStream_t stream, int dw_pref = 0);
+// launch_locate_finalize's verdict, and with it the physical device of each located chunk:
+// located_dev[s] (may be null) = (located[s] - rot_s) mod rot_n, both sentinels passed through, and
+// one atomic add per located stripe into dev_faults[located_dev[s]] (may be null; rot_n words,
+// zeroed by the caller).
+hipError_t launch_locate_finalize_rot(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
+                                      unsigned char *located_dev, unsigned *counts, unsigned *dev_faults, int nstripes,
+                                      int K, int R, uint32_t rot0, uint32_t rot_step, uint32_t rot_n, hipStream_t stream);
+
+// The rotated single-erasure repair: the patterned decode over the k+m single-erasure table of
+// logical chunks (record c rebuilds logical chunk c from its logical survivors), each stripe's
+// pattern id read from stripe_pattern (the locate's `located`), and every selection of the record
+// turned into a physical device per stripe: sh index = (sel - rot_s) mod rot_n, rot_s from rot0 /
+// rot_step / rot_n as above.  So n records serve every rotation, where a table of (rotation x
+// chunk) records would pass kPatMaxPatterns at RS(16+4).  The type only selects the kernels.
+struct PatternRotArgs : PatternArgs {};
+// one output row per pattern (single erasures)
+hipError_t launch_pattern_rot_bytewise(const PatternRotArgs &a, hipStream_t stream);
+hipError_t launch_pattern_rot_bitsliced(const PatternRotArgs &a, hipStream_t stream);
+
 // Work-sharing tiles.  The streaming kernels deal each XCD a contiguous eighth of the tiles
 // (xcd_remap), but the XCDs do not run at one rate: on the headline's memory shape the odd ones
 // take ~15 % longer per tile, every launch, so the even ones idle for the last 6-8 % of it

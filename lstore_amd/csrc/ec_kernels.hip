@@ -465,6 +465,126 @@ hipError_t launch_locate_finalize(const unsigned *syndrome, unsigned long long *
                        nstripes, K, R);
 }
 
+// ------------------------------------------------------------------ rotated check / locate / repair
+namespace {
+bool rot_fields_ok(uint32_t rot0, uint32_t rot_step, uint32_t rot_n, int nshards) {
+  return rot_n >= 1 && rot_n == static_cast<uint32_t>(nshards) && rot0 < rot_n && rot_step < rot_n;
+}
+
+bool check_rot_args_ok(const CheckRotArgs &a) {
+  return a.K >= 1 && a.K <= kMaxK && a.R >= 1 && a.R <= 8 && a.cells && a.syndrome && a.size % 8 == 0 &&
+         reinterpret_cast<uintptr_t>(a.syndrome) % 4 == 0 && reinterpret_cast<uintptr_t>(a.bad_count) % 4 == 0 &&
+         rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.K + a.R);
+}
+
+bool locate_rot_args_ok(const LocateRotArgs &a) {
+  return check_rot_args_ok(a) && a.R >= 2 && a.ratio && a.hyp && reinterpret_cast<uintptr_t>(a.hyp) % 8 == 0;
+}
+
+// k_locate_finalize's verdict, and the device it points at: stripe s has rotation
+// (rot0 + s * rot_step) mod rot_n, and logical chunk c of it lives on device (c - rotation) mod rot_n
+__global__ void k_locate_finalize_rot(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
+                                      unsigned char *located_dev, unsigned *counts, unsigned *dev_faults, int nstripes,
+                                      int K, int R, uint32_t rot0, uint32_t rot_step, uint32_t rot_n) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nstripes) return;
+  const unsigned syn = syndrome[s];
+  const unsigned long long h = hyp[s] & (K >= 64 ? ~0ull : (1ull << K) - 1);
+  hyp[s] = h;
+  unsigned loc;
+  if (syn == 0) loc = kLocateClean;
+  else if (__popc(syn) == 1) loc = static_cast<unsigned>(K + __ffs(static_cast<int>(syn)) - 1);  // one parity row alone
+  else if (syn == (1u << R) - 1 && __popcll(h) == 1) loc = static_cast<unsigned>(__ffsll(h) - 1);
+  else loc = kLocateMany;
+  located[s] = static_cast<unsigned char>(loc);
+  if (counts && syn != 0) atomicAdd(counts + (loc == kLocateMany ? 1 : 0), 1u);
+  unsigned dev = loc;  // the sentinels pass through
+  if (loc < rot_n) {
+    const uint32_t rot = (rot0 + (static_cast<uint32_t>(s) % rot_n) * rot_step) % rot_n;
+    dev = (loc + rot_n - rot) % rot_n;
+    if (dev_faults) atomicAdd(dev_faults + dev, 1u);
+  }
+  if (located_dev) located_dev[s] = static_cast<unsigned char>(dev);
+}
+}  // namespace
+
+hipError_t launch_check_rot_bytewise(const CheckRotArgs &a, hipStream_t st) {
+  if (!check_rot_args_ok(a)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int grid = tile_grid(bw_auto(a.K, a.R).tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_chkrot_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_check_rot_bitsliced(const CheckRotArgs &a, hipStream_t st, int dw_pref) {
+  if (!check_rot_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int dw = lane_dwords(dw_pref, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_chkrot_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+}
+
+hipError_t launch_locate_rot_bytewise(const LocateRotArgs &a, hipStream_t st) {
+  if (!locate_rot_args_ok(a)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int grid = tile_grid(bw_auto(a.K, a.R).tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) {
+    if constexpr (decltype(r)::value >= 2) return dispatch_locrot_bytewise<decltype(r)::value>(a, st, grid);
+    else return hipErrorInvalidValue;  // (one row cannot locate: not instantiated)
+  });
+}
+
+hipError_t launch_locate_rot_bitsliced(const LocateRotArgs &a, hipStream_t st, int dw_pref) {
+  if (!locate_rot_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int dw = lane_dwords(a.R <= kLocWideRows ? dw_pref : 1, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) {
+    if constexpr (decltype(r)::value >= 2) return dispatch_locrot_bitsliced<decltype(r)::value>(a, st, grid, dw);
+    else return hipErrorInvalidValue;
+  });
+}
+
+hipError_t launch_locate_finalize_rot(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
+                                      unsigned char *located_dev, unsigned *counts, unsigned *dev_faults, int nstripes,
+                                      int K, int R, uint32_t rot0, uint32_t rot_step, uint32_t rot_n, hipStream_t st) {
+  if (!syndrome || !hyp || !located || K < 1 || K > kMaxK || R < 2 || R > 8 || !rot_fields_ok(rot0, rot_step, rot_n, K + R))
+    return hipErrorInvalidValue;
+  if (nstripes <= 0) return hipSuccess;
+  return launch_kernel(&k_locate_finalize_rot, dim3((nstripes + 255) / 256), dim3(256), st, syndrome, hyp, located,
+                       located_dev, counts, dev_faults, nstripes, K, R, rot0, rot_step, rot_n);
+}
+
+namespace {
+// the single-erasure table over logical chunks: one record per chunk, the pattern ids from stripe_pattern
+bool pattern_rot_args_ok(const PatternRotArgs &a) {
+  return pattern_args_ok(a, 1) && a.stripe_pattern && a.npat == static_cast<uint32_t>(a.nshards) &&
+         rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.nshards);
+}
+}  // namespace
+
+hipError_t launch_pattern_rot_bytewise(const PatternRotArgs &a, hipStream_t st) {
+  if (!pattern_rot_args_ok(a)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int grid = tile_grid(bw_auto(a.K, 1).tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return dispatch_patrot_bytewise(a, st, grid);
+}
+
+hipError_t launch_pattern_rot_bitsliced(const PatternRotArgs &a, hipStream_t st) {
+  if (!pattern_rot_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int grid = tile_grid(kBlock * 4, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return dispatch_patrot_bitsliced(a, st, grid);
+}
+
 // ------------------------------------------------------------------ stripe magic (adler32)
 namespace {
 

@@ -173,7 +173,7 @@ __device__ __forceinline__ void for_tiles(uint32_t ntiles, unsigned *q, uint32_t
     for (int e = 0; e <= 8; ++e) atomicExch(q + kTileQueueLine * e, 0u);
 }
 
-// A tile-loop kernel over ApplyArgs, PatternArgs, CheckArgs or LocateArgs, launched with a
+// A tile-loop kernel over ApplyArgs, PatternArgs, CheckArgs, LocateArgs or a rotated form, launched with a
 // work-sharing tile queue slot and its persistent grid when tile sharing is on (ec_kernels.h),
 // else on `grid` blocks over static eighths.
 template <typename Kern, typename Args>
@@ -1345,13 +1345,43 @@ __device__ __forceinline__ uint32_t stripe_pattern_id(const PatternArgs &a, uint
   return (a.rot0 + (s % a.rot_n) * a.rot_step) % a.rot_n;  // rot0, rot_step < rot_n <= kPatMaxShards: 32 bits do
 }
 
+// (n - rot_s) of stripe s under the rotation fields of CheckRotArgs / PatternRotArgs, 1..n: logical
+// chunk c of the stripe is shard (c + back) mod n.  s is uniform over the workgroup; readfirstlane
+// says so to the compiler, and every index derived from it stays in scalar registers.
+template <typename Args>
+__device__ __forceinline__ uint32_t rot_back(const Args &a, uint32_t s) {
+  return __builtin_amdgcn_readfirstlane(a.rot_n - (a.rot0 + (s % a.rot_n) * a.rot_step) % a.rot_n);
+}
+
+// Where a patterned tile takes a shard ref from: the record's selection itself (PatternArgs), or
+// the physical device holding that logical chunk in stripe s (PatternRotArgs, ec_kernels.h).
+template <typename Args>
+struct PatShards {
+  static constexpr bool kRot = std::is_same<Args, PatternRotArgs>::value;
+  const Args &a;
+  uint32_t back = 0;
+  __device__ __forceinline__ PatShards(const Args &a_, uint32_t s) : a(a_) {
+    if constexpr (kRot) back = rot_back(a, s);
+  }
+  __device__ __forceinline__ ShardRef at(uint32_t sel) const {
+    if constexpr (kRot) {
+      uint32_t i = sel + back;
+      if (i >= a.rot_n) i -= a.rot_n;
+      return a.sh[i];
+    } else {
+      return a.sh[sel];
+    }
+  }
+};
+
 // BF as k_gf8_bytewise: the branch-free coefficient path, or per-cell branches (R = 1).  KC > 0:
 // K fixed at compile time, so a full tile has all its K*IT loads in flight before any arithmetic,
 // as the single-pattern kernel's fixed-K forms have (with four inputs at a time the one-row
 // kernel ran at 0.56 of 8 TB/s against their 0.75: profiles/patterns_kbench_runtime_k.txt).
-// Instantiated for the one-row kernel only (dispatch_pat_bytewise).
-template <int R, int KC, int IT, int VW, bool BF>
-__global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
+// Instantiated for the one-row kernel only (dispatch_pat_bytewise).  Args: PatternArgs, or
+// PatternRotArgs for the rotated single-erasure repair (the same tile body up to PatShards).
+template <int R, int KC, int IT, int VW, bool BF, typename Args>
+__device__ __forceinline__ void pat_bytewise_tiles(const Args &a) {
   typedef typename VecT<VW>::type V;
   constexpr int kStep = BwTile<IT, VW>::kStep;
   constexpr int kTile = BwTile<IT, VW>::kBytes;
@@ -1371,6 +1401,7 @@ __global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
     const uint32_t nout = rec->nout;
     if (nout == 0) return;  // nothing to rebuild
     ConstCell *cells = images + rec->cells_off;
+    const PatShards<Args> sh(a, s);
     const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
     const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
 
@@ -1384,14 +1415,14 @@ __global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
       bw_inputs<R, KC, IT, VW, BF, false>(
           acc, cells, K,
           [&](int j) LSEC_INLINE {
-            const ShardRef in = a.sh[rec->in_sel[j]];
+            const ShardRef in = sh.at(rec->in_sel[j]);
             return in.base + s * in.stride + off0;
           },
           NoLoads());
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
-          const ShardRef out = a.sh[rec->out_sel[r]];
+          const ShardRef out = sh.at(rec->out_sel[r]);
           const uint64_t q = out.base + s * out.stride + off0;
 #pragma unroll
           for (int it = 0; it < IT; ++it) put_nt<false, V>(q + it * kStep, acc[it][r]);
@@ -1399,7 +1430,7 @@ __global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
       }
     } else {
       for (int j = 0; j < K; ++j) {
-        const ShardRef in = a.sh[rec->in_sel[j]];
+        const ShardRef in = sh.at(rec->in_sel[j]);
         const uint64_t q = in.base + s * in.stride;
         V v[IT];
 #pragma unroll
@@ -1409,7 +1440,7 @@ __global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if (static_cast<uint32_t>(r) < nout) {
-          const ShardRef out = a.sh[rec->out_sel[r]];
+          const ShardRef out = sh.at(rec->out_sel[r]);
           const uint64_t q = out.base + s * out.stride;
 #pragma unroll
           for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
@@ -1419,9 +1450,19 @@ __global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
   }, a.tile_phase);
 }
 
+template <int R, int KC, int IT, int VW, bool BF>
+__global__ __launch_bounds__(kBlock) void k_pat_bytewise(PatternArgs a) {
+  pat_bytewise_tiles<R, KC, IT, VW, BF>(a);
+}
+
+template <int R, int KC, int IT, int VW, bool BF>
+__global__ __launch_bounds__(kBlock) void k_patrot_bytewise(PatternRotArgs a) {
+  pat_bytewise_tiles<R, KC, IT, VW, BF>(a);
+}
+
 // k_gf8_bitsliced's lanes (one dword of packet-column space per lane) under a pattern record
-template <int R>
-__global__ __launch_bounds__(kBlock) void k_pat_bitsliced(PatternArgs a) {
+template <int R, typename Args>
+__device__ __forceinline__ void pat_bitsliced_tiles(const Args &a) {
   const int K = a.K;
   const uint32_t P = static_cast<uint32_t>(a.packet);
   const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
@@ -1439,6 +1480,7 @@ __global__ __launch_bounds__(kBlock) void k_pat_bitsliced(PatternArgs a) {
     const uint32_t nout = rec->nout;
     if (nout == 0) return;
     ConstCell *cells = images + rec->cells_off;
+    const PatShards<Args> sh(a, s);
     const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * 4;
     if (colb >= col_bytes) return;  // lanes past the end of a ragged last tile
     const uint32_t sp = colb / P;
@@ -1451,7 +1493,7 @@ __global__ __launch_bounds__(kBlock) void k_pat_bitsliced(PatternArgs a) {
       for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
 
     for (int j = 0; j < K; ++j) {
-      const ShardRef in = a.sh[rec->in_sel[j]];
+      const ShardRef in = sh.at(rec->in_sel[j]);
       const uint64_t q = in.base + s * in.stride + off;
       uint32_t e[8];
 #pragma unroll
@@ -1468,13 +1510,23 @@ __global__ __launch_bounds__(kBlock) void k_pat_bitsliced(PatternArgs a) {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
-        const ShardRef out = a.sh[rec->out_sel[r]];
+        const ShardRef out = sh.at(rec->out_sel[r]);
         const uint64_t q = out.base + s * out.stride + off;
 #pragma unroll
         for (int x = 0; x < 8; ++x) put_nt<false, uint32_t>(q + x * P, acc[r][x]);
       }
     }
   }, a.tile_phase);
+}
+
+template <int R>
+__global__ __launch_bounds__(kBlock) void k_pat_bitsliced(PatternArgs a) {
+  pat_bitsliced_tiles<R>(a);
+}
+
+template <int R>
+__global__ __launch_bounds__(kBlock) void k_patrot_bitsliced(PatternRotArgs a) {
+  pat_bitsliced_tiles<R>(a);
 }
 
 // The patterned bytewise kernel takes the automatic shape (bw_auto) of the table's row count and
@@ -1499,6 +1551,23 @@ template <int R>
 hipError_t dispatch_pat_bitsliced(const PatternArgs &a, hipStream_t st, int grid) {
   return launch_tiled(&k_pat_bitsliced<R>, grid, st, a);
 }
+
+// The rotated single-erasure repair: the one-row kernels in dispatch_pat_bytewise<1>'s shapes.
+// Defined in ec_patterns_rot_inst.hip alone.
+hipError_t dispatch_patrot_bytewise(const PatternRotArgs &a, hipStream_t st, int grid);
+hipError_t dispatch_patrot_bitsliced(const PatternRotArgs &a, hipStream_t st, int grid);
+#ifdef LSEC_INSTANTIATING_PATROT
+hipError_t dispatch_patrot_bytewise(const PatternRotArgs &a, hipStream_t st, int grid) {
+  constexpr BwShape sh = bw_auto(0, 1);
+  if (a.K == 6) return launch_tiled(&k_patrot_bytewise<1, 6, sh.it, sh.vw, sh.bf>, grid, st, a);
+  if (a.K == 10) return launch_tiled(&k_patrot_bytewise<1, 10, sh.it, sh.vw, sh.bf>, grid, st, a);
+  return launch_tiled(&k_patrot_bytewise<1, 0, sh.it, sh.vw, sh.bf>, grid, st, a);
+}
+
+hipError_t dispatch_patrot_bitsliced(const PatternRotArgs &a, hipStream_t st, int grid) {
+  return launch_tiled(&k_patrot_bitsliced<1>, grid, st, a);
+}
+#endif
 
 // instantiated per R in ec_patterns_inst.hip
 #define LSEC_DECLARE_PAT_R(RR)                                                                  \
@@ -1525,8 +1594,8 @@ __device__ __forceinline__ uint32_t or_diff(uint32_t x, uint32_t y, uint32_t d) 
 // r.  One vote decides the common case -- no lane of the wave saw a difference: nothing is issued
 // -- and only a wave that did votes per row and has its first active lane publish.  The atomic's
 // return value tells the one wave that made the word nonzero, which counts the stripe.
-template <int R>
-__device__ __forceinline__ void chk_publish(const CheckArgs &a, uint32_t s, const uint32_t (&d)[R]) {
+template <int R, typename Args>
+__device__ __forceinline__ void chk_publish(const Args &a, uint32_t s, const uint32_t (&d)[R]) {
   uint32_t any = 0;
 #pragma unroll
   for (int r = 0; r < R; ++r) any |= d[r];
@@ -1549,7 +1618,8 @@ __device__ __forceinline__ void chk_publish(const CheckArgs &a, uint32_t s, cons
 // run-time loop, so its code does not grow with K and its registers are the ones the inputs
 // held -- and reduces each test with a vote into bit j of a mask that starts all ones.  A column
 // with S_0 = 0 and some S_r != 0 fails every j by the same comparison.
-__device__ __forceinline__ void loc_publish(const LocateArgs &a, uint32_t s, uint32_t rows, uint64_t hyp) {
+template <typename Args>
+__device__ __forceinline__ void loc_publish(const Args &a, uint32_t s, uint32_t rows, uint64_t hyp) {
   const uint32_t first = static_cast<uint32_t>(__builtin_ctzll(__ballot(1)));
   if ((threadIdx.x & 63u) == first) {
     atomicOr(a.syndrome + s, rows);
@@ -1566,8 +1636,8 @@ __device__ __forceinline__ uint32_t loc_rows(const uint32_t (&d)[R]) {
 }
 
 // bytewise: Q[r-1][j] * S_0 through the ratio cells' v_perm tables, as gf_mul_acc multiplies
-template <int R, int IT, int VW>
-__device__ __forceinline__ void loc_bytewise_wave(const LocateArgs &a, uint32_t s, const uint32_t (&d)[R],
+template <int R, int IT, int VW, typename Args>
+__device__ __forceinline__ void loc_bytewise_wave(const Args &a, uint32_t s, const uint32_t (&d)[R],
                                                   typename VecT<VW>::type (&acc)[IT][R],
                                                   const typename VecT<VW>::type (&pv)[R][IT]) {
   typedef typename VecT<VW>::type V;
@@ -1609,8 +1679,8 @@ __device__ __forceinline__ void loc_bytewise_wave(const LocateArgs &a, uint32_t 
 // Q[r-1][-1] = 0, so a hypothesis costs one pass of the loop and no registers beside the doubled
 // copy of S_0 -- the registers of the tile body's `e`.  AHEAD: the tile body kept the stored rows
 // (pv) and acc holds the re-formed ones; else acc holds the syndromes already.
-template <int R, int DW, bool AHEAD>
-__device__ __forceinline__ void loc_bitsliced_wave(const LocateArgs &a, uint32_t s, const uint32_t (&d)[R],
+template <int R, int DW, bool AHEAD, typename Args>
+__device__ __forceinline__ void loc_bitsliced_wave(const Args &a, uint32_t s, const uint32_t (&d)[R],
                                                    typename VecT<DW>::type (&acc)[R][8],
                                                    const typename VecT<DW>::type (&pv)[AHEAD ? R : 1][8]) {
   typedef typename VecT<DW>::type V;
@@ -1659,10 +1729,46 @@ __device__ __forceinline__ void loc_bitsliced_wave(const LocateArgs &a, uint32_t
   loc_publish(a, s, rows, hyp);
 }
 
+// The argument structs of the check's tile bodies: CheckArgs / LocateArgs, whose shards are the
+// logical chunks, and CheckRotArgs / LocateRotArgs, whose shards are the physical devices of a
+// rotated LUN (ec_kernels.h).
+template <typename Args>
+constexpr bool kLocArgs = std::is_same<Args, LocateArgs>::value || std::is_same<Args, LocateRotArgs>::value;
+template <typename Args>
+constexpr bool kRotArgs = std::is_base_of<CheckRotArgs, Args>::value;
+
+// Where a tile of stripe s takes the ref of data chunk j / parity row r from: a.in[j] / a.par[r],
+// or, rotated, sh[(j - rot_s) mod n] / sh[(K + r - rot_s) mod n] with rot_s worked out once per
+// tile.  Everything here is uniform over the workgroup: scalar arithmetic and scalar loads only.
+template <typename Args>
+struct ChkShards {
+  const Args &a;
+  uint32_t back = 0;
+  __device__ __forceinline__ ChkShards(const Args &a_, uint32_t s) : a(a_) {
+    if constexpr (kRotArgs<Args>) back = rot_back(a, s);
+  }
+  __device__ __forceinline__ ShardRef in(int j) const {
+    if constexpr (kRotArgs<Args>) return at(static_cast<uint32_t>(j));
+    else return a.in[j];
+  }
+  __device__ __forceinline__ ShardRef par(int r) const {
+    if constexpr (kRotArgs<Args>) return at(static_cast<uint32_t>(a.K + r));
+    else return a.par[r];
+  }
+
+ private:
+  __device__ __forceinline__ ShardRef at(uint32_t c) const {
+    uint32_t i = c + back;
+    if (i >= a.rot_n) i -= a.rot_n;
+    return a.sh[i];
+  }
+};
+
 // BF, X0, KC as bytewise_tiles.  A full tile with K fixed has its K*IT data loads and its R*IT
 // parity loads in flight before any arithmetic (the parity rows cost R*IT*VW VGPRs more than the
 // encode: 24 at RS(6+3)); with K at run time the parity loads go out ahead of the first four inputs.
-// Args: CheckArgs, or LocateArgs for the locate kernels (the same tile body up to the last call).
+// Args: CheckArgs, or LocateArgs for the locate kernels (the same tile body up to the last call);
+// their rotated forms differ in ChkShards alone.
 template <int R, int KC, int IT, bool BF, int VW, bool X0, typename Args>
 __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
   typedef typename VecT<VW>::type V;
@@ -1677,6 +1783,7 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
 
   for_tiles<(kTile >= 8192 ? 1 : 8192 / kTile)>(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
     const uint32_t s = t / tiles_per_stripe;
+    const ChkShards<Args> sh(a, s);
     const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
     const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
 
@@ -1688,11 +1795,16 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
 
     if (full) {
       bw_inputs<R, KC, IT, VW, BF, X0>(
-          acc, cells, K, [&](int j) LSEC_INLINE { return a.in[j].base + s * a.in[j].stride + off0; },
+          acc, cells, K,
+          [&](int j) LSEC_INLINE {
+            const ShardRef in = sh.in(j);
+            return in.base + s * in.stride + off0;
+          },
           [&]() LSEC_INLINE {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-              const uint64_t q = a.par[r].base + s * a.par[r].stride + off0;
+              const ShardRef par = sh.par(r);
+              const uint64_t q = par.base + s * par.stride + off0;
 #pragma unroll
               for (int it = 0; it < IT; ++it) pv[r][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
             }
@@ -1701,7 +1813,8 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
       // ragged last tile: zero-filled inputs give zero parity there, and the stored parity is
       // zero-filled the same way, so bytes past C never show as a difference
       for (int j = 0; j < K; ++j) {
-        const uint64_t p = a.in[j].base + s * a.in[j].stride;
+        const ShardRef in = sh.in(j);
+        const uint64_t p = in.base + s * in.stride;
         V v[IT];
 #pragma unroll
         for (int it = 0; it < IT; ++it) v[it] = load_ragged<VW>(p, off0 + it * kStep, C);
@@ -1709,7 +1822,8 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
       }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        const uint64_t q = a.par[r].base + s * a.par[r].stride;
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride;
 #pragma unroll
         for (int it = 0; it < IT; ++it) pv[r][it] = load_ragged<VW>(q, off0 + it * kStep, C);
       }
@@ -1723,7 +1837,7 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
 #pragma unroll
         for (int e = 0; e < VW; ++e) d[r] = or_diff(acc[it][r][e], pv[r][it][e], d[r]);
     }
-    if constexpr (std::is_same<Args, LocateArgs>::value) loc_bytewise_wave<R, IT, VW>(a, s, d, acc, pv);
+    if constexpr (kLocArgs<Args>) loc_bytewise_wave<R, IT, VW>(a, s, d, acc, pv);
     else chk_publish<R>(a, s, d);
   }, a.tile_phase);
 }
@@ -1750,6 +1864,16 @@ __global__ __launch_bounds__(kBlock) void k_loc_bytewise(LocateArgs a) {
   chk_bytewise_body<R, KC, IT, BF, VW>(a);
 }
 
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_chkrot_bytewise(CheckRotArgs a) {
+  chk_bytewise_body<R, KC, IT, BF, VW>(a);
+}
+
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_locrot_bytewise(LocateRotArgs a) {
+  chk_bytewise_body<R, KC, IT, BF, VW>(a);
+}
+
 // k_gf8_bitsliced's lanes and doubling loop.  The stored parity words are loaded ahead of the
 // inputs while they fit beside the accumulators (R * DW <= 8: 8 * R * DW VGPRs), else row by row
 // after them.  Lanes past the end of a ragged last tile leave the tile body (whole waves may).
@@ -1758,7 +1882,7 @@ template <int R, int DW, typename Args>
 __device__ __forceinline__ void chk_bitsliced_tiles(const Args &a) {
   typedef typename VecT<DW>::type V;
   constexpr bool kAhead = R * DW <= 8;
-  constexpr bool kLocate = std::is_same<Args, LocateArgs>::value;
+  constexpr bool kLocate = kLocArgs<Args>;
   const int K = a.K;
   const uint32_t P = static_cast<uint32_t>(a.packet);
   const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
@@ -1769,6 +1893,7 @@ __device__ __forceinline__ void chk_bitsliced_tiles(const Args &a) {
 
   for_tiles(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
     const uint32_t s = t / tiles_per_stripe;
+    const ChkShards<Args> sh(a, s);
     const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * (4 * DW);
     if (colb >= col_bytes) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
     const uint32_t sp = colb / P;
@@ -1782,14 +1907,16 @@ __device__ __forceinline__ void chk_bitsliced_tiles(const Args &a) {
     if constexpr (kAhead) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        const uint64_t q = a.par[r].base + s * a.par[r].stride + off;
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off;
 #pragma unroll
         for (int x = 0; x < 8; ++x) pv[r][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
       }
     }
 
     for (int j = 0; j < K; ++j) {
-      const uint64_t p = a.in[j].base + s * a.in[j].stride + off;
+      const ShardRef in = sh.in(j);
+      const uint64_t p = in.base + s * in.stride + off;
       V e[8];
 #pragma unroll
       for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<V>(p + x * P));
@@ -1806,7 +1933,8 @@ __device__ __forceinline__ void chk_bitsliced_tiles(const Args &a) {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if constexpr (!kAhead) {
-        const uint64_t q = a.par[r].base + s * a.par[r].stride + off;
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off;
 #pragma unroll
         for (int x = 0; x < 8; ++x) pv[0][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
       }
@@ -1844,6 +1972,16 @@ __global__ __launch_bounds__(kBlock) void k_loc_bitsliced(LocateArgs a) {
   chk_bitsliced_tiles<R, DW>(a);
 }
 
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_chkrot_bitsliced(CheckRotArgs a) {
+  chk_bitsliced_tiles<R, DW>(a);
+}
+
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_locrot_bitsliced(LocateRotArgs a) {
+  chk_bitsliced_tiles<R, DW>(a);
+}
+
 // The check's launch shape is the encode's automatic one for the same K x R (bw_auto, without
 // bytewise_shape's A/B variants), so tile sizes and vector widths match lsec_encode_dev's;
 // fixed-K forms for the K the encode has them for.
@@ -1852,10 +1990,12 @@ __global__ __launch_bounds__(kBlock) void k_loc_bitsliced(LocateArgs a) {
 // AGPRs), so those stripes run with K at run time, four inputs in flight at a time.
 constexpr bool chk_fixed_k(int K, int R, int IT, int VW) { return (K + 2 * R) * IT * VW <= 160; }
 
-// the check kernel of CheckArgs, the locate kernel of LocateArgs
+// the check kernel of CheckArgs, the locate kernel of LocateArgs, the rotated forms of theirs
 template <int R, int KC, int IT, bool BF, int VW, typename Args>
 hipError_t chk_or_loc_kernel(const Args &a, hipStream_t st, int grid) {
   if constexpr (std::is_same<Args, LocateArgs>::value) return launch_tiled(&k_loc_bytewise<R, KC, IT, BF, VW>, grid, st, a);
+  else if constexpr (std::is_same<Args, LocateRotArgs>::value) return launch_tiled(&k_locrot_bytewise<R, KC, IT, BF, VW>, grid, st, a);
+  else if constexpr (std::is_same<Args, CheckRotArgs>::value) return launch_tiled(&k_chkrot_bytewise<R, KC, IT, BF, VW>, grid, st, a);
   else return launch_tiled(&k_chk_bytewise<R, KC, IT, BF, VW>, grid, st, a);
 }
 
@@ -1915,6 +2055,53 @@ hipError_t dispatch_loc_bitsliced(const LocateArgs &a, hipStream_t st, int grid,
   }
   return dw == 1 ? launch_tiled(&k_loc_bitsliced<R, 1>, grid, st, a) : hipErrorInvalidValue;
 }
+
+// The rotated forms take the shapes of their unrotated twins.
+template <int R>
+hipError_t dispatch_chkrot_bytewise(const CheckRotArgs &a, hipStream_t st, int grid) {
+  return chk_bytewise_k<R>(a, st, grid);
+}
+
+template <int R>
+hipError_t dispatch_chkrot_bitsliced(const CheckRotArgs &a, hipStream_t st, int grid, int dw) {
+  switch (dw) {
+    case 4: return launch_tiled(&k_chkrot_bitsliced<R, 4>, grid, st, a);
+    case 2: return launch_tiled(&k_chkrot_bitsliced<R, 2>, grid, st, a);
+    default: return launch_tiled(&k_chkrot_bitsliced<R, 1>, grid, st, a);
+  }
+}
+
+template <int R>
+hipError_t dispatch_locrot_bytewise(const LocateRotArgs &a, hipStream_t st, int grid) {
+  static_assert(R >= 2, "locating needs two parity rows");
+  return chk_bytewise_k<R>(a, st, grid);
+}
+
+template <int R>
+hipError_t dispatch_locrot_bitsliced(const LocateRotArgs &a, hipStream_t st, int grid, int dw) {
+  static_assert(R >= 2, "locating needs two parity rows");
+  if constexpr (R <= kLocWideRows) {
+    if (dw == 4) return launch_tiled(&k_locrot_bitsliced<R, 4>, grid, st, a);
+    if (dw == 2) return launch_tiled(&k_locrot_bitsliced<R, 2>, grid, st, a);
+  }
+  return dw == 1 ? launch_tiled(&k_locrot_bitsliced<R, 1>, grid, st, a) : hipErrorInvalidValue;
+}
+
+// instantiated per R in ec_check_rot_inst.hip (1..8) and ec_locate_rot_inst.hip (2..8)
+#define LSEC_DECLARE_CHKROT_R(RR)                                                                   \
+  extern template hipError_t dispatch_chkrot_bytewise<RR>(const CheckRotArgs &, hipStream_t, int);  \
+  extern template hipError_t dispatch_chkrot_bitsliced<RR>(const CheckRotArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_CHKROT
+LSEC_DECLARE_CHKROT_R(1) LSEC_DECLARE_CHKROT_R(2) LSEC_DECLARE_CHKROT_R(3) LSEC_DECLARE_CHKROT_R(4)
+LSEC_DECLARE_CHKROT_R(5) LSEC_DECLARE_CHKROT_R(6) LSEC_DECLARE_CHKROT_R(7) LSEC_DECLARE_CHKROT_R(8)
+#endif
+#define LSEC_DECLARE_LOCROT_R(RR)                                                                    \
+  extern template hipError_t dispatch_locrot_bytewise<RR>(const LocateRotArgs &, hipStream_t, int);  \
+  extern template hipError_t dispatch_locrot_bitsliced<RR>(const LocateRotArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_LOCROT
+LSEC_DECLARE_LOCROT_R(2) LSEC_DECLARE_LOCROT_R(3) LSEC_DECLARE_LOCROT_R(4) LSEC_DECLARE_LOCROT_R(5)
+LSEC_DECLARE_LOCROT_R(6) LSEC_DECLARE_LOCROT_R(7) LSEC_DECLARE_LOCROT_R(8)
+#endif
 
 // instantiated per R (2..8) in ec_locate_inst.hip
 #define LSEC_DECLARE_LOC_R(RR)                                                                \

@@ -1197,6 +1197,201 @@ int locate_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, un
   return 0;
 }
 
+// ---------------------------------------------------------------- rotated check / locate / repair
+// lsec_check_dev_rotated / lsec_locate_dev_rotated: check_dev and locate_dev over the k+m physical
+// devices of a rotated LUN.  The kernels work each stripe's rotation out themselves (ec_kernels.h,
+// CheckRotArgs), so the outputs are those of the logical view; the finalize launch also names the
+// device behind each located chunk.  Validation order, messages and the split into launches are
+// check_dev's and locate_dev's; each later launch's rot0 advances by (s0 mod n) * rot_step, as
+// enqueue_patterns', and lsec_test_set_pattern_split bounds every launch of these calls.
+namespace {
+
+// stripes per launch: tile indices stay 32-bit; the test hook can lower it
+long long rotated_launch_stripes(long long C) {
+  long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
+  const int split = g_pattern_split.load(std::memory_order_relaxed);
+  if (split > 0) per = std::min<long long>(per, split);
+  return per;
+}
+
+// the fields the rotated argument structs share, for the launch that starts at stripe s0
+template <typename Args>
+void rotated_launch_fields(Args &a, const lsec_shard_t *devs, int n, long long s0, long long per, int nstripes, uint32_t rot0,
+                           uint32_t rot_step) {
+  a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
+  a.rot0 = static_cast<uint32_t>((rot0 + (s0 % n) * rot_step) % n);
+  for (int i = 0; i < n; ++i)
+    a.sh[i] = {reinterpret_cast<uint64_t>(devs[i].base) + static_cast<uint64_t>(s0) * devs[i].stride, devs[i].stride};
+}
+
+// The repair behind a rotated locate: the patterned decode over the k+m single-erasure table of
+// logical chunks, `located` as its stripe_pattern, the selection rotated per stripe in the kernel.
+int enqueue_repair_rotated(PlanExt *e, const PatternTable &tab, const PatternTable::Dev &dv, const lsec_shard_t *devs,
+                           int nstripes, long long C, const unsigned char *located, uint32_t rot0, uint32_t rot_step,
+                           hipStream_t st) {
+  const lio_erasure_plan_t *p = &e->pub;
+  const int n = p->data_strips + p->parity_strips;
+  if (nstripes <= 0 || C == 0 || tab.rmax == 0) return 0;
+  lsec::PatternRotArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  a.recs = dv.recs;
+  a.cells = dv.cells;
+  a.npat = static_cast<uint32_t>(tab.recs.size());
+  a.K = p->data_strips;
+  a.packet = p->packet_size;
+  a.nshards = n;
+  a.size = C;
+  a.rot_step = rot_step;
+  a.rot_n = static_cast<uint32_t>(n);
+  const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
+  const long long per = rotated_launch_stripes(C);
+  for (long long s0 = 0; s0 < nstripes; s0 += per) {
+    rotated_launch_fields(a, devs, n, s0, per, nstripes, rot0, rot_step);
+    a.stripe_pattern = located + s0;
+    const hipError_t err = sliced ? lsec::launch_pattern_rot_bitsliced(a, st) : lsec::launch_pattern_rot_bytewise(a, st);
+    if (err != hipSuccess) return fail("rotated repair kernel launch failed: %s", hipGetErrorString(err));
+  }
+  return 0;
+}
+
+}  // namespace
+
+int check_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                      unsigned *syndrome, unsigned *bad_count, hipStream_t st) {
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("lsec_check_dev_rotated needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  if (k < 1 || k > lsec::kMaxK) return fail("lsec_check_dev_rotated: k=%d outside 1..%d (one launch's inputs)", k, lsec::kMaxK);
+  if (m < 1 || m > 8) return fail("lsec_check_dev_rotated: m=%d outside 1..8 (one launch's parity rows)", m);
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (n_shift < 0) return fail("n_shift %d is negative", n_shift);
+  if (first_stripe < 0) return fail("first_stripe %lld is negative", first_stripe);
+  if (check_geometry(p, C)) return -1;
+  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
+  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
+  if (reinterpret_cast<uintptr_t>(bad_count) % 4 != 0) return fail("bad_count %p is not a multiple of 4 bytes", static_cast<void *>(bad_count));
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_cells(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("lsec_check_dev_rotated: the plan encodes %d parity rows, m=%d", R, m);
+  // the call sets every word itself, stripes of an empty chunk included
+  HIP_OK(hipMemsetAsync(syndrome, 0, sizeof(unsigned) * static_cast<size_t>(nstripes), st));
+  if (bad_count) HIP_OK(hipMemsetAsync(bad_count, 0, sizeof(unsigned), st));
+  if (C == 0) return 0;
+  lsec::CheckRotArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.cells = static_cast<const CoefCell *>(cells);
+  a.K = k;
+  a.R = R;
+  a.size = C;
+  a.packet = p->packet_size;
+  a.bad_count = bad_count;
+  a.rot_step = static_cast<uint32_t>(n_shift % n);
+  a.rot_n = static_cast<uint32_t>(n);
+  const uint32_t rot0 = pattern_rot0(n, n_shift, first_stripe);
+  const int dw = kind == KBITSLICED ? cauchy8_bitsliced_dw(k, R, C) : 0;  // check_dev's shape
+  const long long per = rotated_launch_stripes(C);
+  for (long long s0 = 0; s0 < nstripes; s0 += per) {
+    rotated_launch_fields(a, devs, n, s0, per, nstripes, rot0, a.rot_step);
+    a.syndrome = syndrome + s0;
+    const hipError_t err = kind == KBITSLICED ? lsec::launch_check_rot_bitsliced(a, st, dw) : lsec::launch_check_rot_bytewise(a, st);
+    if (err != hipSuccess) return fail("rotated check kernel launch failed: %s", hipGetErrorString(err));
+  }
+  return 0;
+}
+
+int locate_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                       unsigned *syndrome, unsigned long long *hyp, unsigned char *located, unsigned char *located_dev,
+                       unsigned *counts, unsigned *dev_faults, int flags, hipStream_t st) {
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("lsec_locate_dev_rotated needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  if (k < 1 || k > lsec::kMaxK)
+    return fail("lsec_locate_dev_rotated: k=%d outside 1..%d (one launch's inputs, one bit of hyp each)", k, lsec::kMaxK);
+  if (m < 2 || m > 8)
+    return fail("lsec_locate_dev_rotated: m=%d outside 2..8 (one parity row cannot locate; one launch's parity rows)", m);
+  if (flags & ~LSEC_LOCATE_REPAIR) return fail("lsec_locate_dev_rotated: flags %#x has bits other than LSEC_LOCATE_REPAIR", flags);
+  const bool repair = (flags & LSEC_LOCATE_REPAIR) != 0;
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (n_shift < 0) return fail("n_shift %d is negative", n_shift);
+  if (first_stripe < 0) return fail("first_stripe %lld is negative", first_stripe);
+  if (check_geometry(p, C)) return -1;
+  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
+  if (nstripes > 0 && !hyp) return fail("hyp is NULL");
+  if (nstripes > 0 && !located) return fail("located is NULL");
+  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
+  if (reinterpret_cast<uintptr_t>(hyp) % 8 != 0) return fail("hyp %p is not a multiple of 8 bytes", static_cast<void *>(hyp));
+  if (reinterpret_cast<uintptr_t>(counts) % 4 != 0) return fail("counts %p is not a multiple of 4 bytes", static_cast<void *>(counts));
+  if (reinterpret_cast<uintptr_t>(dev_faults) % 4 != 0) return fail("dev_faults %p is not a multiple of 4 bytes", static_cast<void *>(dev_faults));
+  const lsec::gf8::Mat *q = nullptr;
+  if (locate_ratio(e, &q)) return -1;  // a zero coefficient is refused here, before any device is touched
+  // locate_dev's table: the k+m single erasures of the logical chunks, in chunk order.  The limits above
+  // (k <= 64, m <= 8) are inside those of the patterned decode, so the repair adds none.
+  std::vector<int> singles;
+  for (int i = 0; i < n; ++i) {
+    singles.push_back(i);
+    singles.push_back(-1);
+  }
+  const PatternTable *tab = nullptr;
+  PatternTable::Dev dv;
+  if (repair && nstripes == 0) {
+    // preparing ahead: the matrix work always, the upload where there is a device to upload to
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+      PatternTable host_only;
+      return build_pattern_table(e, singles.data(), n, nullptr, 0, host_only);
+    }
+  }
+  if (repair && pattern_table_dev(e, singles.data(), n, nullptr, 0, &tab, &dv)) return -1;  // cached on the plan
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_cells(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("lsec_locate_dev_rotated: the plan encodes %d parity rows, m=%d", R, m);
+  const CoefCell *ratio = nullptr;
+  if (ratio_cells_dev(e, &ratio)) return -1;
+  // the call sets every element itself, stripes of an empty chunk included (located and located_dev: the finalize launch)
+  HIP_OK(hipMemsetAsync(syndrome, 0, sizeof(unsigned) * static_cast<size_t>(nstripes), st));
+  HIP_OK(hipMemsetAsync(hyp, 0xFF, sizeof(unsigned long long) * static_cast<size_t>(nstripes), st));
+  if (counts) HIP_OK(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), st));
+  if (dev_faults) HIP_OK(hipMemsetAsync(dev_faults, 0, sizeof(unsigned) * static_cast<size_t>(n), st));
+  const uint32_t rot_step = static_cast<uint32_t>(n_shift % n);
+  const uint32_t rot0 = pattern_rot0(n, n_shift, first_stripe);
+  if (C > 0) {
+    lsec::LocateRotArgs a;
+    std::memset(static_cast<void *>(&a), 0, sizeof(a));
+    a.cells = static_cast<const CoefCell *>(cells);
+    a.ratio = ratio;
+    a.K = k;
+    a.R = R;
+    a.size = C;
+    a.packet = p->packet_size;
+    a.rot_step = rot_step;
+    a.rot_n = static_cast<uint32_t>(n);
+    const int dw = kind == KBITSLICED ? cauchy8_bitsliced_dw(k, R, C) : 0;  // the check's shape
+    const long long per = rotated_launch_stripes(C);
+    for (long long s0 = 0; s0 < nstripes; s0 += per) {
+      rotated_launch_fields(a, devs, n, s0, per, nstripes, rot0, rot_step);
+      a.syndrome = syndrome + s0;
+      a.hyp = hyp + s0;
+      const hipError_t err = kind == KBITSLICED ? lsec::launch_locate_rot_bitsliced(a, st, dw) : lsec::launch_locate_rot_bytewise(a, st);
+      if (err != hipSuccess) return fail("rotated locate kernel launch failed: %s", hipGetErrorString(err));
+    }
+  }
+  const hipError_t err = lsec::launch_locate_finalize_rot(syndrome, hyp, located, located_dev, counts, dev_faults, nstripes, k, R,
+                                                         rot0, rot_step, static_cast<uint32_t>(n), st);
+  if (err != hipSuccess) return fail("rotated locate finalize launch failed: %s", hipGetErrorString(err));
+  if (repair) return enqueue_repair_rotated(e, *tab, dv, devs, nstripes, C, located, rot0, rot_step, st);
+  return 0;
+}
+
 }  // namespace eng
 
 using namespace eng;

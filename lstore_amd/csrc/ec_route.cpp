@@ -655,6 +655,29 @@ int lsec_decode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
   return decode_dev_rotated(e, devs, nstripes, block_size, lost, n_shift, first_stripe, static_cast<hipStream_t>(stream));
 }
 
+int lsec_check_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                           int n_shift, long long first_stripe, unsigned int *syndrome, unsigned int *bad_count,
+                           void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!devs) return fail("devs is NULL");
+  if (check_shards(plan, devs, nstripes)) return -1;
+  return check_dev_rotated(e, devs, nstripes, block_size, n_shift, first_stripe, syndrome, bad_count,
+                           static_cast<hipStream_t>(stream));
+}
+
+int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                            int n_shift, long long first_stripe, unsigned int *syndrome, unsigned long long *hyp,
+                            unsigned char *located, unsigned char *located_dev, unsigned int *counts,
+                            unsigned int *dev_faults, int flags, void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!devs) return fail("devs is NULL");
+  if (check_shards(plan, devs, nstripes)) return -1;
+  return locate_dev_rotated(e, devs, nstripes, block_size, n_shift, first_stripe, syndrome, hyp, located, located_dev,
+                            counts, dev_faults, flags, static_cast<hipStream_t>(stream));
+}
+
 int et_encode_stripes_magic(lio_erasure_plan_t *plan, char **ptrs, int nstripes, int block_size, char *magic) {
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");

@@ -81,7 +81,8 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_prepare_decode", "lsec_abi_version", "lsec_device_count", "lsec_last_error", "lsec_plan_kernel",
            "lsec_set_kernel_variant", "lsec_set_host_devices", "lsec_hbm_copy_dev", "lsec_hbm_mix_dev", "lsec_prepare_encode", "lsec_plan_jit", "lsec_device_numa",
            "lsec_set_tile_sharing", "lsec_tile_sharing", "lsec_host_unpin_drain", "lsec_hbm_decode_shape_dev",
-           "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev", "lsec_locate_dev")
+           "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev", "lsec_locate_dev",
+           "lsec_check_dev_rotated", "lsec_locate_dev_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -143,6 +144,10 @@ def lib():
     L.lsec_check_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lsec_locate_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p]
+    L.lsec_check_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
+    L.lsec_locate_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.lsec_test_locate_ratio.argtypes = [P, C.c_int, C.c_int]
     L.lsec_test_set_pattern_split.argtypes = [C.c_int]
     L.lsec_test_set_pattern_split.restype = None
@@ -599,6 +604,27 @@ class Plan:
                 raise ValueError(f"{name} must be a contiguous device tensor of {count} elements of {item} bytes")
         self.locate_dev_refs(refs, n, size, syndrome.data_ptr(), hyp.data_ptr(), located.data_ptr(),
                              0 if counts is None else counts.data_ptr(), repair, _stream_handle(stream))
+
+    def check_dev_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
+                               syndrome_ptr: int, bad_count_ptr: int = 0, stream: int = 0) -> None:
+        """lsec_check_dev_rotated: check_dev_refs over the PHYSICAL devices of a rotated LUN (refs[i]: device i,
+        as decode_dev_rotated_refs takes them).  The outputs are those of each stripe's logical view."""
+        _check(lib().lsec_check_dev_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                            n_shift, first_stripe, syndrome_ptr or None, bad_count_ptr or None, stream),
+               "lsec_check_dev_rotated")
+
+    def locate_dev_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
+                                syndrome_ptr: int, hyp_ptr: int, located_ptr: int, located_dev_ptr: int = 0,
+                                counts_ptr: int = 0, dev_faults_ptr: int = 0, repair: bool = False, stream: int = 0) -> None:
+        """lsec_locate_dev_rotated: locate_dev_refs over the PHYSICAL devices of a rotated LUN.  syndrome, hyp,
+        located and counts are those of each stripe's logical view; located_dev_ptr (nstripes bytes, 0: not
+        wanted) receives the device holding each located chunk, dev_faults_ptr (k+m uint32, 0: not wanted) the
+        located stripes per device.  repair rebuilds each located chunk in place on its device."""
+        _check(lib().lsec_locate_dev_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                             n_shift, first_stripe, syndrome_ptr or None, hyp_ptr or None,
+                                             located_ptr or None, located_dev_ptr or None, counts_ptr or None,
+                                             dev_faults_ptr or None, LOCATE_REPAIR if repair else 0, stream),
+               "lsec_locate_dev_rotated")
 
     def prepare_decode(self, erasures) -> None:
         _check(lib().lsec_prepare_decode(self._p, _erasure_array(erasures)), "lsec_prepare_decode")

@@ -13,6 +13,10 @@ lsec_check_dev against lsec_encode_dev and against encode-and-compare, on the sa
 
 python tools/kbench.py --locate [--rounds R] [--reps N]
 lsec_locate_dev against lsec_check_dev on the same shapes, clean, corrupt and repairing: see locate_bench.
+
+python tools/kbench.py --rotated-scrub [--rounds R] [--reps N]
+lsec_check_dev_rotated / lsec_locate_dev_rotated over the devices of a rotated LUN against the unrotated
+calls over the same bytes: see rotated_scrub_bench.
 """
 import argparse
 import os
@@ -341,6 +345,124 @@ def locate_bench(a):
         torch.cuda.empty_cache()
 
 
+def rotated_scrub_bench(a):
+    """The scrub of a rotated LUN against the unrotated calls, interleaved round by round (C = 1 MiB).  One
+    set of k+m buffers holds consistent logical stripes, a second one the same bytes as the devices of a LUN
+    with n_shift = 1 hold them (device i: logical chunk (i + first_stripe + s) mod n of stripe s):
+      (a) lsec_check_dev on the logical stripes         the yardstick of (b): code the rotated calls do not touch
+      (b) lsec_check_dev_rotated on the devices         (a) plus the rotation's scalar work per tile
+      (c) lsec_locate_dev on the logical stripes        the yardstick of (d)
+      (d) lsec_locate_dev_rotated on the devices
+      (e) lsec_locate_dev_rotated with repair, one      each launch is preceded by the torch op that corrupts those
+          byte of one device corrupt in every stripe    bytes again (inside the timed window); k+m chunks to locate
+      (f) lsec_locate_dev with repair, one byte of      (e)'s yardstick: one chunk to locate
+          one chunk corrupt in every stripe
+    (a)'s and (c)'s own min-max over the rounds are the margins (b) and (d) are judged by.  Results are checked
+    before timing."""
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    C, N = 1 << 20, a.pattern_stripes
+    n_shift, first = 1, 3_000_000_007
+    for name in a.pattern_codes.split(","):
+        meth, k, m = CONFIGS[name][:3]
+        n = k + m
+        plan = L.Plan.for_chunk(meth, k, m, C)
+        bufs = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(n)]
+        refs = [(b.data_ptr(), C) for b in bufs]
+        plan.encode_dev_refs(refs, N, C, sh)  # consistent parity in buffers k..n-1
+        rots = (first + torch.arange(N, device=dev)) * n_shift % n
+        devs = [torch.empty((N, C), dtype=torch.uint8, device=dev) for _ in range(n)]
+        for r in range(n):
+            rows = torch.nonzero(rots == r).flatten()
+            for i in range(n):
+                devs[i][rows] = bufs[(i + r) % n][rows]
+        dev_refs = [(b.data_ptr(), C) for b in devs]
+        syn = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        hyp = torch.full((N,), -1, dtype=torch.int64, device=dev)
+        loc = torch.full((N,), 0x7B, dtype=torch.uint8, device=dev)
+        loc_dev = torch.full((N,), 0x7B, dtype=torch.uint8, device=dev)
+        counts = torch.full((2,), -1, dtype=torch.int32, device=dev)
+        faults = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        one = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        jd, col = k // 2, 4097
+        good, good_dev = bufs[jd][:, col].clone(), devs[jd][:, col].clone()
+        outs = (syn.data_ptr(), hyp.data_ptr(), loc.data_ptr())
+        rot_outs = outs + (loc_dev.data_ptr(), counts.data_ptr(), faults.data_ptr())
+
+        def scrub_rotated():
+            devs[jd][:, col] = good_dev ^ 0x5A
+            plan.locate_dev_rotated_refs(dev_refs, N, C, n_shift, first, *rot_outs, True, sh)
+
+        def scrub():
+            bufs[jd][:, col] = good ^ 0x5A
+            plan.locate_dev_refs(refs, N, C, *outs, counts.data_ptr(), True, sh)
+
+        runs = {"a": lambda: plan.check_dev_refs(refs, N, C, syn.data_ptr(), one.data_ptr(), sh),
+                "b": lambda: plan.check_dev_rotated_refs(dev_refs, N, C, n_shift, first, syn.data_ptr(), one.data_ptr(), sh),
+                "c": lambda: plan.locate_dev_refs(refs, N, C, *outs, counts.data_ptr(), False, sh),
+                "d": lambda: plan.locate_dev_rotated_refs(dev_refs, N, C, n_shift, first, *rot_outs, False, sh),
+                "e": scrub_rotated,
+                "f": scrub}
+        # results first
+        full = (1 << k) - 1
+        for key in ("a", "b"):
+            runs[key]()
+            torch.cuda.synchronize()
+            assert int(syn.count_nonzero()) == 0 and int(one) == 0, f"({key}) found a difference in consistent stripes"
+        for key in ("c", "d"):
+            runs[key]()
+            torch.cuda.synchronize()
+            assert int(syn.count_nonzero()) == 0 and bool((hyp == full).all()) and bool((loc == E.LOCATE_CLEAN).all()) \
+                and counts.tolist() == [0, 0], f"({key}) found a difference in consistent stripes"
+        assert bool((loc_dev == E.LOCATE_CLEAN).all()) and faults.tolist() == [0] * n
+        runs["e"]()
+        torch.cuda.synchronize()
+        assert torch.equal(loc.to(torch.int64), (jd + rots) % n) and bool((loc_dev == jd).all()) and counts.tolist() == [N, 0] \
+            and faults.tolist() == [N if i == jd else 0 for i in range(n)] and torch.equal(devs[jd][:, col], good_dev), \
+            "(e) did not locate and repair device %d" % jd
+        runs["b"]()
+        torch.cuda.synchronize()
+        assert int(syn.count_nonzero()) == 0 and int(one) == 0, "(e) left an inconsistent stripe"
+        runs["f"]()
+        torch.cuda.synchronize()
+        assert bool((loc == jd).all()) and counts.tolist() == [N, 0] and torch.equal(bufs[jd][:, col], good), "(f) did not repair"
+        times = {key: [] for key in runs}
+        for _ in range(a.rounds):
+            for key, fn in runs.items():
+                fn()  # warm
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.reps):
+                    fn()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[key].append(e0.elapsed_time(e1) / a.reps)
+        what = {"a": "lsec_check_dev", "b": "lsec_check_dev_rotated", "c": "lsec_locate_dev", "d": "lsec_locate_dev_rotated",
+                "e": "corrupt + rotated locate + repair", "f": "corrupt + locate + repair"}
+        twin = {"b": "a", "d": "c"}
+        med = {key: sorted(ts)[len(ts) // 2] for key, ts in times.items()}
+        for key, ts in times.items():
+            db = n * C * N  # the k+m chunks a pass has to move
+            band = ""
+            if key in twin:
+                lo, hi = min(times[twin[key]]), max(times[twin[key]])
+                band = (f"  inside ({twin[key]})'s band" if lo <= med[key] <= hi else
+                        f"  {'below' if med[key] < lo else 'above'} ({twin[key]})'s band by "
+                        f"{abs(med[key] - (lo if med[key] < lo else hi)) / med[key]:.2%}")
+            print(f"{name} N={N} C={C} ({key}) {what[key]:34s} median {med[key]:7.3f} ms  min {min(ts):7.3f}  max {max(ts):7.3f}  "
+                  f"{db / med[key] / 1e6:7.1f} GB/s ({db / med[key] / 8e9:5.1%} of 8 TB/s){band}", flush=True)
+        for key in ("a", "c"):
+            lo, hi = min(times[key]), max(times[key])
+            print(f"{name} ({key}) band: {lo:.3f} .. {hi:.3f} ms ({(hi - lo) / lo:.2%}) over {a.rounds} rounds of {a.reps} launches",
+                  flush=True)
+        print(f"{name} (b)/(a) = {med['b'] / med['a']:.3f}, (d)/(c) = {med['d'] / med['c']:.3f}, (e)/(f) = {med['e'] / med['f']:.3f}",
+              flush=True)
+        del bufs, devs, syn, hyp, loc, loc_dev, counts, faults
+        plan.close()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data-gib", type=float, default=24.0)
@@ -366,7 +488,13 @@ def main():
     ap.add_argument("--locate", action="store_true",
                     help="time lsec_locate_dev against lsec_check_dev, clean, corrupt and repairing (locate_bench; "
                          "--pattern-stripes, --pattern-codes) and exit")
+    ap.add_argument("--rotated-scrub", action="store_true",
+                    help="time lsec_check_dev_rotated / lsec_locate_dev_rotated against the unrotated calls "
+                         "(rotated_scrub_bench; --pattern-stripes, --pattern-codes) and exit")
     a = ap.parse_args()
+    if a.rotated_scrub:
+        rotated_scrub_bench(a)
+        return
     if a.locate:
         locate_bench(a)
         return
