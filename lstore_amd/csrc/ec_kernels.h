@@ -261,6 +261,28 @@ struct PatternRotArgs : PatternArgs {};
 hipError_t launch_pattern_rot_bytewise(const PatternRotArgs &a, hipStream_t stream);
 hipError_t launch_pattern_rot_bitsliced(const PatternRotArgs &a, hipStream_t stream);
 
+// Which kernel ran (test hooks lsec_test_launch_record / lsec_test_predict_forms, ec_plan.cpp).  The
+// check, locate, patterned and rotated calls are families of separately compiled kernels; a form
+// names one of them by its template arguments: bytewise R, KC (0: K at run time), IT, VW, BF; or
+// bit-sliced R, DW (the patterned bit-sliced kernels have one dword per lane).  The per-R dispatch
+// functions record the form at the one place where the template arguments are known; the record
+// is the calling thread's, holds the launches since launch_record_reset() in order (the engine
+// resets it on entry to each of those calls) and costs a few host stores per launch.
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot };
+struct LaunchForm {
+  int family, sliced, R, KC, IT, VW, BF, DW;
+};
+constexpr int kLaunchRecordMax = 16;  // forms kept (the count goes on)
+void record_launch(const LaunchForm &f);
+void launch_record_reset();
+int launch_record(LaunchForm *out, int max);  // -> launches recorded; out[0 .. min(that, max, kLaunchRecordMax))
+// The form launch_*(family) takes for K x R (R: the table's rmax for the patterned families), from
+// the functions the dispatch itself calls; dw_pref: as launch_*_bitsliced takes it.  No GPU is
+// touched.  false: no such kernel (R or K out of range, a locate of one row, a packet no lane fits).
+bool predict_launch(int family, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
+// the K with fixed-K forms (LSEC_FIXED_K), ascending -> how many there are; out[0 .. min(that, max))
+int fixed_k_list(int *out, int max);
+
 // Work-sharing tiles.  The streaming kernels deal each XCD a contiguous eighth of the tiles
 // (xcd_remap), but the XCDs do not run at one rate: on the headline's memory shape the odd ones
 // take ~15 % longer per tile, every launch, so the even ones idle for the last 6-8 % of it

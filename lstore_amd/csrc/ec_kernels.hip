@@ -100,6 +100,10 @@ int lane_dwords(int want, int packet) {
   return dw;
 }
 
+// dwords per lane of a bit-sliced check and of a bit-sliced locate (one past kLocWideRows rows)
+int chk_lane_dwords(int dw_pref, int packet) { return lane_dwords(dw_pref, packet); }
+int loc_lane_dwords(int R, int dw_pref, int packet) { return lane_dwords(R <= kLocWideRows ? dw_pref : 1, packet); }
+
 // the device of stream st (the current device for the null stream), or -1
 int stream_device(hipStream_t st) {
   int dev = -1;
@@ -404,7 +408,7 @@ hipError_t launch_check_bitsliced(const CheckArgs &a, hipStream_t st, int dw_pre
   if (!check_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int dw = lane_dwords(dw_pref, a.packet);
+  const int dw = chk_lane_dwords(dw_pref, a.packet);
   const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
   if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_chk_bitsliced<decltype(r)::value>(a, st, grid, dw); });
@@ -448,7 +452,7 @@ hipError_t launch_locate_bitsliced(const LocateArgs &a, hipStream_t st, int dw_p
   if (!locate_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int dw = lane_dwords(a.R <= kLocWideRows ? dw_pref : 1, a.packet);
+  const int dw = loc_lane_dwords(a.R, dw_pref, a.packet);
   const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
   if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) {
@@ -520,7 +524,7 @@ hipError_t launch_check_rot_bitsliced(const CheckRotArgs &a, hipStream_t st, int
   if (!check_rot_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int dw = lane_dwords(dw_pref, a.packet);
+  const int dw = chk_lane_dwords(dw_pref, a.packet);
   const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
   if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_chkrot_bitsliced<decltype(r)::value>(a, st, grid, dw); });
@@ -541,7 +545,7 @@ hipError_t launch_locate_rot_bitsliced(const LocateRotArgs &a, hipStream_t st, i
   if (!locate_rot_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int dw = lane_dwords(a.R <= kLocWideRows ? dw_pref : 1, a.packet);
+  const int dw = loc_lane_dwords(a.R, dw_pref, a.packet);
   const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
   if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) {
@@ -583,6 +587,50 @@ hipError_t launch_pattern_rot_bitsliced(const PatternRotArgs &a, hipStream_t st)
   const int grid = tile_grid(kBlock * 4, a.size / 8, a.nstripes);
   if (!grid) return hipErrorInvalidValue;
   return dispatch_patrot_bitsliced(a, st, grid);
+}
+
+// ------------------------------------------------------------------ which kernel ran (test hooks)
+namespace {
+thread_local LaunchForm tl_forms[kLaunchRecordMax];
+thread_local int tl_nforms = 0;
+}  // namespace
+
+void record_launch(const LaunchForm &f) {
+  if (tl_nforms < kLaunchRecordMax) tl_forms[tl_nforms] = f;
+  ++tl_nforms;
+}
+
+void launch_record_reset() { tl_nforms = 0; }
+
+int launch_record(LaunchForm *out, int max) {
+  for (int i = 0; i < tl_nforms && i < max && i < kLaunchRecordMax; ++i) out[i] = tl_forms[i];
+  return tl_nforms;
+}
+
+bool predict_launch(int family, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out) {
+  const bool pat = family == kFormPat || family == kFormPatRot;
+  const bool loc = family == kFormLoc || family == kFormLocRot;
+  if (family < kFormChk || family > kFormPatRot || K < 1 || K > kMaxK || R < 1 || R > (pat ? kPatMaxOut : 8)) return false;
+  if ((loc && R < 2) || (family == kFormPatRot && R != 1)) return false;
+  if (sliced) {
+    if (packet <= 0 || packet % 4 != 0) return false;
+    const int dw = pat ? 1 : loc ? loc_lane_dwords(R, dw_pref, packet) : chk_lane_dwords(dw_pref, packet);
+    *out = LaunchForm{family, 1, R, 0, 0, 0, 0, dw};
+    return true;
+  }
+  const BwForm f = pat ? pat_bytewise_form(K, R) : chk_bytewise_form(K, R);
+  *out = LaunchForm{family, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
+  return true;
+}
+
+int fixed_k_list(int *out, int max) {
+  int n = 0;
+#define LSEC_LIST_K(KK)     \
+  if (n < max) out[n] = KK; \
+  ++n;
+  LSEC_FIXED_K(LSEC_LIST_K)
+#undef LSEC_LIST_K
+  return n;
 }
 
 // ------------------------------------------------------------------ stripe magic (adler32)

@@ -1187,6 +1187,13 @@ __global__ __launch_bounds__(kBlock) void k_gfw_transposed(ApplyArgs a) {
 // ------------------------------------------------------------------ per-R dispatch
 // the K with fixed-K forms of the bytewise kernels (the encode's, the check's and the locate's)
 #define LSEC_FIXED_K(X) X(4) X(6) X(8) X(10) X(12) X(16) X(20)
+constexpr bool has_fixed_k(int K) {
+#define LSEC_IS_K(KK) \
+  if (K == KK) return true;
+  LSEC_FIXED_K(LSEC_IS_K)
+#undef LSEC_IS_K
+  return false;
+}
 
 // Bytewise launch shapes (tile per lane): IT steps of VW dwords, BF the coefficient path.  By code:
 //   0 -> (2, 4) 32 B/lane, branch-free   1 -> (1, 4) 16 B/lane, branch-free
@@ -1534,21 +1541,42 @@ __global__ __launch_bounds__(kBlock) void k_patrot_bitsliced(PatternRotArgs a) {
 // K at run time: their fixed-K forms, with every input's 2 x 16 B in flight on top of the
 // accumulators, took 186 (K = 6) and 256 (K = 10) VGPRs and measured slower (RS(10+4), three
 // erasures: 17.5 ms against 10.2; profiles/patterns_fixedk_ab.txt).
+// K of the one-row kernel's form (0: K at run time), and a table's form by its row count
+constexpr int pat_one_row_kc(int K) { return K == 6 || K == 10 ? K : 0; }
+struct BwForm {
+  int kc, it, vw;
+  bool bf;
+};
+constexpr BwForm pat_bytewise_form(int K, int R) {
+  const BwShape sh = bw_auto(R == 1 ? 0 : K, R);
+  return BwForm{R == 1 ? pat_one_row_kc(K) : 0, sh.it, sh.vw, sh.bf};
+}
+
+template <int R, int KC, int IT, int VW, bool BF>
+hipError_t pat_kernel(const PatternArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormPat, 0, R, KC, IT, VW, BF ? 1 : 0, 0});
+  return launch_tiled(&k_pat_bytewise<R, KC, IT, VW, BF>, grid, st, a);
+}
+
 template <int R>
 hipError_t dispatch_pat_bytewise(const PatternArgs &a, hipStream_t st, int grid) {
+  const BwForm f = pat_bytewise_form(a.K, R);
   if constexpr (R == 1) {
     constexpr BwShape sh = bw_auto(0, 1);
-    if (a.K == 6) return launch_tiled(&k_pat_bytewise<1, 6, sh.it, sh.vw, sh.bf>, grid, st, a);
-    if (a.K == 10) return launch_tiled(&k_pat_bytewise<1, 10, sh.it, sh.vw, sh.bf>, grid, st, a);
-    return launch_tiled(&k_pat_bytewise<1, 0, sh.it, sh.vw, sh.bf>, grid, st, a);
+    switch (f.kc) {
+      case 6: return pat_kernel<1, 6, sh.it, sh.vw, sh.bf>(a, st, grid);
+      case 10: return pat_kernel<1, 10, sh.it, sh.vw, sh.bf>(a, st, grid);
+      default: return pat_kernel<1, 0, sh.it, sh.vw, sh.bf>(a, st, grid);
+    }
   } else {
-    if (bw_auto(a.K, R).it == 1) return launch_tiled(&k_pat_bytewise<R, 0, 1, 4, true>, grid, st, a);
-    return launch_tiled(&k_pat_bytewise<R, 0, 2, 4, true>, grid, st, a);
+    if (f.it == 1) return pat_kernel<R, 0, 1, 4, true>(a, st, grid);
+    return pat_kernel<R, 0, 2, 4, true>(a, st, grid);
   }
 }
 
 template <int R>
 hipError_t dispatch_pat_bitsliced(const PatternArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormPat, 1, R, 0, 0, 0, 0, 1});
   return launch_tiled(&k_pat_bitsliced<R>, grid, st, a);
 }
 
@@ -1557,14 +1585,23 @@ hipError_t dispatch_pat_bitsliced(const PatternArgs &a, hipStream_t st, int grid
 hipError_t dispatch_patrot_bytewise(const PatternRotArgs &a, hipStream_t st, int grid);
 hipError_t dispatch_patrot_bitsliced(const PatternRotArgs &a, hipStream_t st, int grid);
 #ifdef LSEC_INSTANTIATING_PATROT
+template <int KC, int IT, int VW, bool BF>
+hipError_t patrot_kernel(const PatternRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormPatRot, 0, 1, KC, IT, VW, BF ? 1 : 0, 0});
+  return launch_tiled(&k_patrot_bytewise<1, KC, IT, VW, BF>, grid, st, a);
+}
+
 hipError_t dispatch_patrot_bytewise(const PatternRotArgs &a, hipStream_t st, int grid) {
   constexpr BwShape sh = bw_auto(0, 1);
-  if (a.K == 6) return launch_tiled(&k_patrot_bytewise<1, 6, sh.it, sh.vw, sh.bf>, grid, st, a);
-  if (a.K == 10) return launch_tiled(&k_patrot_bytewise<1, 10, sh.it, sh.vw, sh.bf>, grid, st, a);
-  return launch_tiled(&k_patrot_bytewise<1, 0, sh.it, sh.vw, sh.bf>, grid, st, a);
+  switch (pat_bytewise_form(a.K, 1).kc) {
+    case 6: return patrot_kernel<6, sh.it, sh.vw, sh.bf>(a, st, grid);
+    case 10: return patrot_kernel<10, sh.it, sh.vw, sh.bf>(a, st, grid);
+    default: return patrot_kernel<0, sh.it, sh.vw, sh.bf>(a, st, grid);
+  }
 }
 
 hipError_t dispatch_patrot_bitsliced(const PatternRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormPatRot, 1, 1, 0, 0, 0, 0, 1});
   return launch_tiled(&k_patrot_bitsliced<1>, grid, st, a);
 }
 #endif
@@ -1990,23 +2027,43 @@ __global__ __launch_bounds__(kBlock) void k_locrot_bitsliced(LocateRotArgs a) {
 // AGPRs), so those stripes run with K at run time, four inputs in flight at a time.
 constexpr bool chk_fixed_k(int K, int R, int IT, int VW) { return (K + 2 * R) * IT * VW <= 160; }
 
+// The bytewise form of a K x R check or locate: the fixed-K form where K has one and it fits, else
+// K at run time in the automatic shape (R == 1: 8 B per lane, per-cell branches)
+constexpr BwForm chk_bytewise_form(int K, int R) {
+  const BwShape sh = bw_auto(K, R);
+  if (has_fixed_k(K) && chk_fixed_k(K, R, sh.it, sh.vw)) return BwForm{K, sh.it, sh.vw, sh.bf};
+  if (R == 1) return BwForm{0, 1, 2, false};
+  return BwForm{0, sh.it == 1 ? 1 : 2, 4, true};
+}
+
+template <typename Args>
+constexpr int chk_family() {
+  return std::is_same<Args, LocateArgs>::value      ? kFormLoc
+         : std::is_same<Args, LocateRotArgs>::value ? kFormLocRot
+         : std::is_same<Args, CheckRotArgs>::value  ? kFormChkRot
+                                                    : kFormChk;
+}
+
 // the check kernel of CheckArgs, the locate kernel of LocateArgs, the rotated forms of theirs
 template <int R, int KC, int IT, bool BF, int VW, typename Args>
 hipError_t chk_or_loc_kernel(const Args &a, hipStream_t st, int grid) {
+  record_launch({chk_family<Args>(), 0, R, KC, IT, VW, BF ? 1 : 0, 0});
   if constexpr (std::is_same<Args, LocateArgs>::value) return launch_tiled(&k_loc_bytewise<R, KC, IT, BF, VW>, grid, st, a);
   else if constexpr (std::is_same<Args, LocateRotArgs>::value) return launch_tiled(&k_locrot_bytewise<R, KC, IT, BF, VW>, grid, st, a);
   else if constexpr (std::is_same<Args, CheckRotArgs>::value) return launch_tiled(&k_chkrot_bytewise<R, KC, IT, BF, VW>, grid, st, a);
   else return launch_tiled(&k_chk_bytewise<R, KC, IT, BF, VW>, grid, st, a);
 }
 
+// decides the form (chk_bytewise_form), then switches on it
 template <int R, typename Args>
 hipError_t chk_bytewise_k(const Args &a, hipStream_t st, int grid) {
-  switch (a.K) {
+  const BwForm f = chk_bytewise_form(a.K, R);
+  switch (f.kc) {
 #define LSEC_CHK_K(KK)                                                                          \
   case KK: {                                                                                    \
-    constexpr BwShape sh = bw_auto(KK, R);                                                      \
-    if constexpr (chk_fixed_k(KK, R, sh.it, sh.vw))                                             \
-      return chk_or_loc_kernel<R, KK, sh.it, sh.bf, sh.vw>(a, st, grid);                      \
+    constexpr BwForm ff = chk_bytewise_form(KK, R);                                             \
+    if constexpr (ff.kc == KK)                                                                  \
+      return chk_or_loc_kernel<R, KK, ff.it, ff.bf, ff.vw>(a, st, grid);                      \
     break;                                                                                      \
   }
     LSEC_FIXED_K(LSEC_CHK_K)
@@ -2016,9 +2073,15 @@ hipError_t chk_bytewise_k(const Args &a, hipStream_t st, int grid) {
   if constexpr (R == 1) {
     return chk_or_loc_kernel<1, 0, 1, false, 2>(a, st, grid);
   } else {
-    if (bw_auto(a.K, R).it == 1) return chk_or_loc_kernel<R, 0, 1, true, 4>(a, st, grid);
+    if (f.it == 1) return chk_or_loc_kernel<R, 0, 1, true, 4>(a, st, grid);
     return chk_or_loc_kernel<R, 0, 2, true, 4>(a, st, grid);
   }
+}
+
+// a bit-sliced check or locate kernel's record
+template <typename Args>
+void record_bitsliced(int R, int dw) {
+  record_launch({chk_family<Args>(), 1, R, 0, 0, 0, 0, dw});
 }
 
 template <int R>
@@ -2029,9 +2092,9 @@ hipError_t dispatch_chk_bytewise(const CheckArgs &a, hipStream_t st, int grid) {
 template <int R>
 hipError_t dispatch_chk_bitsliced(const CheckArgs &a, hipStream_t st, int grid, int dw) {
   switch (dw) {
-    case 4: return launch_tiled(&k_chk_bitsliced<R, 4>, grid, st, a);
-    case 2: return launch_tiled(&k_chk_bitsliced<R, 2>, grid, st, a);
-    default: return launch_tiled(&k_chk_bitsliced<R, 1>, grid, st, a);
+    case 4: record_bitsliced<CheckArgs>(R, 4); return launch_tiled(&k_chk_bitsliced<R, 4>, grid, st, a);
+    case 2: record_bitsliced<CheckArgs>(R, 2); return launch_tiled(&k_chk_bitsliced<R, 2>, grid, st, a);
+    default: record_bitsliced<CheckArgs>(R, 1); return launch_tiled(&k_chk_bitsliced<R, 1>, grid, st, a);
   }
 }
 
@@ -2050,10 +2113,10 @@ hipError_t dispatch_loc_bitsliced(const LocateArgs &a, hipStream_t st, int grid,
   static_assert(R >= 2, "locating needs two parity rows");
   // (more than one dword per lane only up to kLocWideRows rows: launch_locate_bitsliced)
   if constexpr (R <= kLocWideRows) {
-    if (dw == 4) return launch_tiled(&k_loc_bitsliced<R, 4>, grid, st, a);
-    if (dw == 2) return launch_tiled(&k_loc_bitsliced<R, 2>, grid, st, a);
+    if (dw == 4) return record_bitsliced<LocateArgs>(R, 4), launch_tiled(&k_loc_bitsliced<R, 4>, grid, st, a);
+    if (dw == 2) return record_bitsliced<LocateArgs>(R, 2), launch_tiled(&k_loc_bitsliced<R, 2>, grid, st, a);
   }
-  return dw == 1 ? launch_tiled(&k_loc_bitsliced<R, 1>, grid, st, a) : hipErrorInvalidValue;
+  return dw == 1 ? (record_bitsliced<LocateArgs>(R, 1), launch_tiled(&k_loc_bitsliced<R, 1>, grid, st, a)) : hipErrorInvalidValue;
 }
 
 // The rotated forms take the shapes of their unrotated twins.
@@ -2065,9 +2128,9 @@ hipError_t dispatch_chkrot_bytewise(const CheckRotArgs &a, hipStream_t st, int g
 template <int R>
 hipError_t dispatch_chkrot_bitsliced(const CheckRotArgs &a, hipStream_t st, int grid, int dw) {
   switch (dw) {
-    case 4: return launch_tiled(&k_chkrot_bitsliced<R, 4>, grid, st, a);
-    case 2: return launch_tiled(&k_chkrot_bitsliced<R, 2>, grid, st, a);
-    default: return launch_tiled(&k_chkrot_bitsliced<R, 1>, grid, st, a);
+    case 4: record_bitsliced<CheckRotArgs>(R, 4); return launch_tiled(&k_chkrot_bitsliced<R, 4>, grid, st, a);
+    case 2: record_bitsliced<CheckRotArgs>(R, 2); return launch_tiled(&k_chkrot_bitsliced<R, 2>, grid, st, a);
+    default: record_bitsliced<CheckRotArgs>(R, 1); return launch_tiled(&k_chkrot_bitsliced<R, 1>, grid, st, a);
   }
 }
 
@@ -2081,10 +2144,10 @@ template <int R>
 hipError_t dispatch_locrot_bitsliced(const LocateRotArgs &a, hipStream_t st, int grid, int dw) {
   static_assert(R >= 2, "locating needs two parity rows");
   if constexpr (R <= kLocWideRows) {
-    if (dw == 4) return launch_tiled(&k_locrot_bitsliced<R, 4>, grid, st, a);
-    if (dw == 2) return launch_tiled(&k_locrot_bitsliced<R, 2>, grid, st, a);
+    if (dw == 4) return record_bitsliced<LocateRotArgs>(R, 4), launch_tiled(&k_locrot_bitsliced<R, 4>, grid, st, a);
+    if (dw == 2) return record_bitsliced<LocateRotArgs>(R, 2), launch_tiled(&k_locrot_bitsliced<R, 2>, grid, st, a);
   }
-  return dw == 1 ? launch_tiled(&k_locrot_bitsliced<R, 1>, grid, st, a) : hipErrorInvalidValue;
+  return dw == 1 ? (record_bitsliced<LocateRotArgs>(R, 1), launch_tiled(&k_locrot_bitsliced<R, 1>, grid, st, a)) : hipErrorInvalidValue;
 }
 
 // instantiated per R in ec_check_rot_inst.hip (1..8) and ec_locate_rot_inst.hip (2..8)

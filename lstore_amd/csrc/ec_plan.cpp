@@ -738,6 +738,7 @@ int decode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
 // Every limit's message names the limit; nothing is enqueued when one is passed.
 int check_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned *bad_count,
               hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
   lio_erasure_plan_t *p = &e->pub;
   const int kind = kernel_kind(p->method, p->w);
   if (kind != KBYTEWISE && kind != KBITSLICED)
@@ -1043,6 +1044,7 @@ int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::De
 
 int decode_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
                         const unsigned char *stripe_pattern, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
   lio_erasure_plan_t *p = &e->pub;
   if (!patterns) return fail("patterns is NULL");
   if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
@@ -1056,6 +1058,7 @@ int decode_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long l
 
 int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
                        long long first_stripe, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
   lio_erasure_plan_t *p = &e->pub;
   if (!lost) return fail("lost is NULL");
   if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
@@ -1127,6 +1130,7 @@ int ratio_cells_dev(PlanExt *e, const CoefCell **out) {
 
 int locate_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned long long *hyp,
                unsigned char *located, unsigned *counts, int flags, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
   lio_erasure_plan_t *p = &e->pub;
   const int kind = kernel_kind(p->method, p->w);
   if (kind != KBYTEWISE && kind != KBITSLICED)
@@ -1258,6 +1262,7 @@ int enqueue_repair_rotated(PlanExt *e, const PatternTable &tab, const PatternTab
 
 int check_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
                       unsigned *syndrome, unsigned *bad_count, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
   lio_erasure_plan_t *p = &e->pub;
   const int kind = kernel_kind(p->method, p->w);
   if (kind != KBYTEWISE && kind != KBITSLICED)
@@ -1307,6 +1312,7 @@ int check_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long l
 int locate_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
                        unsigned *syndrome, unsigned long long *hyp, unsigned char *located, unsigned char *located_dev,
                        unsigned *counts, unsigned *dev_faults, int flags, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
   lio_erasure_plan_t *p = &e->pub;
   const int kind = kernel_kind(p->method, p->w);
   if (kind != KBYTEWISE && kind != KBITSLICED)
@@ -1817,6 +1823,42 @@ void lsec_test_set_stamps(void *dev_buf, unsigned n) {
 // generic kernel (a w = 16 / 32 network with a ragged tail: bits 0 and 2).  The bytes are the same
 // on every path, so only this tells a test which one alignment and readiness picked.
 int lsec_test_apply_path(void) { return tl_apply_path; }
+
+// Test hook, not in include/: the kernel forms (ec_kernels.h, LaunchForm) that the calling thread's last
+// lsec_check_dev, lsec_locate_dev, lsec_decode_dev_patterns, lsec_decode_dev_rotated,
+// lsec_check_dev_rotated or lsec_locate_dev_rotated launched, in order: a locate with repair its
+// patterned decode too, a split call every launch; the finalize launch, which has one form, is not
+// among them.  forms: 8 ints each (family, bit-sliced, R, KC, IT, VW, BF, DW).  Returns the number
+// of launches; at most min(that, max_forms, 16) are written.
+int lsec_test_launch_record(int *forms, int max_forms) {
+  lsec::LaunchForm rec[lsec::kLaunchRecordMax];
+  const int n = lsec::launch_record(rec, lsec::kLaunchRecordMax);
+  for (int i = 0; forms && i < n && i < max_forms && i < lsec::kLaunchRecordMax; ++i) {
+    const int v[8] = {rec[i].family, rec[i].sliced, rec[i].R, rec[i].KC, rec[i].IT, rec[i].VW, rec[i].BF, rec[i].DW};
+    std::memcpy(forms + 8 * i, v, sizeof(v));
+  }
+  return n;
+}
+
+// Test hook, not in include/ (no GPU): the form a launch of `family` (1 check, 2 locate, 3 rotated
+// check, 4 rotated locate, 5 patterned decode, 6 rotated repair) takes for a plan of kernel 1
+// (bytewise) or 2 (bit-sliced) with K inputs and R rows (patterned: the table's largest erasure
+// count) at that packet and chunk size, as 8 ints.  It asks the functions the dispatch calls
+// (cauchy8_bitsliced_dw here, lsec::predict_launch for the rest).  0, or -1 with a message.
+int lsec_test_predict_form(int family, int plan_kernel, int K, int R, int packet, long long block_size, int *form) {
+  if (!form) return fail("lsec_test_predict_form: NULL output");
+  if (plan_kernel != KBYTEWISE && plan_kernel != KBITSLICED) return fail("lsec_test_predict_form: plan kernel %d", plan_kernel);
+  const bool sliced = plan_kernel == KBITSLICED;
+  lsec::LaunchForm f;
+  if (!lsec::predict_launch(family, sliced, K, R, packet, sliced ? cauchy8_bitsliced_dw(K, R, block_size) : 0, &f))
+    return fail("lsec_test_predict_form: no kernel of family %d for K=%d R=%d packet=%d", family, K, R, packet);
+  const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
+  std::memcpy(form, v, sizeof(v));
+  return 0;
+}
+
+// Test hook, not in include/ (no GPU): the K that have fixed-K forms (LSEC_FIXED_K), ascending
+int lsec_test_fixed_k(int *out, int max) { return lsec::fixed_k_list(out, max); }
 
 // Test hook, not in include/: 1 = Cauchy at w = 8 on its compiled packet network wherever one exists,
 // 0 = by shape (cauchy8_bitsliced_dw, the default).

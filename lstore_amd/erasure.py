@@ -14,6 +14,7 @@ the library's message when the status is non-zero.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -154,6 +155,9 @@ def lib():
     L.lsec_test_pattern_table.argtypes = [P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lsec_test_pattern_rot0.argtypes = [C.c_int, C.c_int, C.c_longlong]
+    L.lsec_test_launch_record.argtypes = [C.POINTER(C.c_int), C.c_int]
+    L.lsec_test_predict_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
+    L.lsec_test_fixed_k.argtypes = [C.POINTER(C.c_int), C.c_int]
     L.lsec_prepare_decode.argtypes = [P, C.POINTER(C.c_int)]
     L.lsec_prepare_encode.argtypes = [P]
     L.lsec_plan_jit.argtypes = [P, C.POINTER(C.c_int)]
@@ -702,6 +706,54 @@ def apply_path() -> int:
     """Test hook: what this thread's last encode_dev / decode_dev launched, as PATH_* bits (a
     w = 16 / 32 network that leaves a ragged tail to the generic kernel: PATH_NETWORK | PATH_GENERIC)."""
     return int(lib().lsec_test_apply_path())
+
+
+FORM_FAMILIES = ("chk", "loc", "chkrot", "locrot", "pat", "patrot")
+Form = collections.namedtuple("Form", "family sliced R KC IT VW BF DW")
+Form.__doc__ = """One separately compiled kernel of the check / locate / patterned / rotated calls: family (one of
+FORM_FAMILIES), sliced (plan kernel 2), R rows; bytewise: KC (0 = K at run time), IT steps of VW dwords
+per lane, BF branch-free; bit-sliced: DW dwords per lane (the others 0)."""
+
+
+def _form(v) -> Form:
+    return Form(FORM_FAMILIES[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
+
+
+def launch_record() -> list:
+    """Test hook: the Forms this thread's last check_dev / locate_dev / decode_dev_patterns / decode_dev_rotated
+    / check_dev_rotated / locate_dev_rotated call launched, in order (a locate with repair: its patterned
+    decode too; a split call: every launch)."""
+    buf = (C.c_int * (8 * 16))()
+    n = lib().lsec_test_launch_record(buf, 16)
+    if n > 16:
+        raise ErasureError(f"lsec_test_launch_record: {n} launches, 16 are kept")
+    return [_form(buf[8 * i:8 * i + 8]) for i in range(n)]
+
+
+def predict_form(family: str, plan_kernel: int, k: int, rows: int, packet: int = 0, block_size: int = 0) -> Form:
+    """Test hook (no GPU): the Form a launch of `family` takes for a plan of kernel 1 (bytewise) or 2
+    (bit-sliced) with k inputs and `rows` rows (pat: the table's largest erasure count), asked of the
+    functions the dispatch itself calls."""
+    out = (C.c_int * 8)()
+    _check(lib().lsec_test_predict_form(FORM_FAMILIES.index(family) + 1, plan_kernel, k, rows, packet, block_size, out),
+           "lsec_test_predict_form")
+    return _form(out)
+
+
+def predict_forms(call: str, plan_kernel: int, k: int, rows: int, packet: int = 0, block_size: int = 0,
+                  repair: bool = False) -> list:
+    """Test hook (no GPU): what launch_record() holds after one unsplit call of `call` (a family name): its
+    form, and behind a repairing locate the one-row patterned decode's (pat, or patrot for locrot)."""
+    forms = [predict_form(call, plan_kernel, k, rows, packet, block_size)]
+    if repair:
+        forms.append(predict_form({"loc": "pat", "locrot": "patrot"}[call], plan_kernel, k, 1, packet, block_size))
+    return forms
+
+
+def fixed_k() -> tuple:
+    """Test hook (no GPU): the K for which the bytewise kernels have fixed-K forms (LSEC_FIXED_K)."""
+    buf = (C.c_int * 64)()
+    return tuple(buf[:lib().lsec_test_fixed_k(buf, 64)])
 
 
 def set_pattern_split(stripes: int = 0) -> None:

@@ -54,9 +54,14 @@ CANARY_WORD, BAD_FILL = 0x5EED5EED, 0x7B7B7B7B
 _plans, _stripes = {}, {}
 
 
+def spec(code):
+    """(method, k, m, packet) of a code: a name of CODES, or the tuple itself (tests/scrub_forms.py's plans)"""
+    return CODES[code] if isinstance(code, str) else tuple(code)
+
+
 def ref_encode(code, packet, data):
     """the yardstick's parity [m, C] of data [k, C]"""
-    method, k, m, _ = CODES[code]
+    method, k, m, _ = spec(code)
     if not O.ref_available():
         return O.encode(method, np.ascontiguousarray(data), m, packet, 8)
     key = (code, packet)
@@ -69,7 +74,7 @@ def stripes(code, packet, size, nstripes):
     """uint8 [N, k+m, C]: random data and the yardstick's parity; computed once per shape, never modified"""
     key = (code, packet, size, nstripes)
     if key not in _stripes:
-        method, k, m, _ = CODES[code]
+        method, k, m, _ = spec(code)
         rng = np.random.default_rng(abs(hash(key)) % (1 << 32))
         full = np.empty((nstripes, k + m, size), np.uint8)
         full[:, :k] = rng.integers(0, 256, (nstripes, k, size), dtype=np.uint8)
@@ -82,13 +87,13 @@ def stripes(code, packet, size, nstripes):
 
 def expected_mask(code, packet, stripe):
     """stripe uint8 [k+m, C] as stored -> the syndrome word the call must produce"""
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     par = ref_encode(code, packet, stripe[:k])
     return sum(1 << r for r in range(m) if not np.array_equal(par[r], stripe[k + r]))
 
 
 def make_plan(code, packet, size):
-    method, k, m, _ = CODES[code]
+    method, k, m, _ = spec(code)
     p = L.Plan.new(method, size, k, m, 8, packet, 1 if method == L.RAID4 else 8)
     assert p.form_encoding_matrix() == 0
     return p
@@ -124,7 +129,7 @@ class Rig:
 
     def __init__(self, torch, code, packet, size, layout, nstripes=NSTRIPES):
         self.torch, self.code, self.packet, self.size, self.nstripes = torch, code, packet, size, nstripes
-        _, self.k, self.m, _ = CODES[code]
+        _, self.k, self.m, _ = spec(code)
         self.full = stripes(code, packet, size, nstripes)
         self.lay = LY.plan_layout(layout, self.k, self.m, nstripes, size, outputs=range(self.k, self.k + self.m))
         LY.check_layout(self.lay)

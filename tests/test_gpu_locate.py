@@ -49,19 +49,20 @@ def shapes(code):
 
 
 def ref_decode(code, packet, shards, erased):
-    """the yardstick's decode of one erased chunk, in place"""
-    method, k, m, _ = CODES[code]
+    """the yardstick's decode of one erased chunk (or of a list of them), in place"""
+    method, k, m, _ = TC.spec(code)
+    erased = [erased] if isinstance(erased, (int, np.integer)) else list(erased)
     if not O.ref_available():
-        assert O.decode(method, shards, k, [erased], packet, 8) == 0
+        assert O.decode(method, shards, k, erased, packet, 8) == 0
         return
     if (code, packet) not in TC._plans:  # (shared with test_gpu_check's ref_encode)
         TC._plans[(code, packet)] = O.RefPlan(method, k, m, 8, packet)
-    assert TC._plans[(code, packet)].decode(shards, [erased]) == 0
+    assert TC._plans[(code, packet)].decode(shards, erased) == 0
 
 
 def explanations(code, packet, stripe):
     """the chunks i of stripe [k+m, C] whose replacement by what the others rebuild makes it consistent"""
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = TC.spec(code)
     out = []
     for i in range(k + m):
         sh = stripe.copy()
@@ -73,8 +74,9 @@ def explanations(code, packet, stripe):
 
 
 def expected(code, packet, stripe, key):
-    """(syndrome, hyp, located) of a corrupted stripe as stored; key names the corruption for the cache"""
-    _, k, m, _ = CODES[code]
+    """(syndrome, hyp, located) of a corrupted stripe as stored; key names the corruption for the cache (the
+    rigs: the batch's stripe count, the stripe and what it holds, so the rotated rig shares the entries)"""
+    _, k, m, _ = TC.spec(code)
     key = (code, packet, stripe.shape[1]) + key
     if key not in _expect:
         syn = TC.expected_mask(code, packet, stripe)
@@ -137,7 +139,7 @@ class Rig:
 
     def __init__(self, torch, code, packet, size, layout, nstripes=NSTRIPES):
         self.torch, self.code, self.packet, self.size, self.nstripes = torch, code, packet, size, nstripes
-        _, self.k, self.m, _ = CODES[code]
+        _, self.k, self.m, _ = TC.spec(code)
         self.full = TC.stripes(code, packet, size, nstripes)
         self.lay = LY.plan_layout(layout, self.k, self.m, nstripes, size, outputs=range(self.k, self.k + self.m))
         LY.check_layout(self.lay)
@@ -147,6 +149,7 @@ class Rig:
         self.outs = Outs(torch, nstripes)
         self.plan = TC.make_plan(code, packet, size)
         self.flips, self.chunks = {}, {}  # stripe -> what it holds beside the reference bytes
+        self.written = {}                 # stripe -> (the whole stripe as stored, a name for the cache): write()
 
     def close(self):
         self.plan.close()
@@ -162,6 +165,14 @@ class Rig:
         self.arena[a:a + self.size].bitwise_xor_(0xFF)
         self.note(self.chunks.setdefault(s, []), i)
 
+    def write(self, s, stripe, name):
+        """store `stripe` uint8 [k+m, C] as stripe s (the chunks that differ from what the arena holds)"""
+        assert s not in self.flips and s not in self.chunks
+        for i in range(self.k + self.m):
+            a = self.lay.start(i, s)
+            self.arena[a:a + self.size] = self.torch.from_numpy(np.ascontiguousarray(stripe[i])).to(self.arena.device)
+        self.written[s] = (stripe.copy(), name)
+
     @staticmethod
     def note(cur, what):
         if what in cur:
@@ -176,6 +187,10 @@ class Rig:
         loc = np.full(n, CLEAN, np.uint8)
         for s in range(n):
             fl, ch = sorted(self.flips.get(s, [])), sorted(self.chunks.get(s, []))
+            if s in self.written:
+                st, name = self.written[s]
+                syn[s], hyp[s], loc[s] = expected(self.code, self.packet, st, (n, s, name))
+                continue
             if not fl and not ch:
                 continue
             st = self.full[s].copy()
@@ -183,7 +198,7 @@ class Rig:
                 st[i, b] ^= v
             for i in ch:
                 st[i] ^= 0xFF
-            syn[s], hyp[s], loc[s] = expected(self.code, self.packet, st, (s, tuple(fl), tuple(ch)))
+            syn[s], hyp[s], loc[s] = expected(self.code, self.packet, st, (n, s, tuple(fl), tuple(ch)))
         counts = [int(((loc != CLEAN) & (loc != MANY)).sum()), int((loc == MANY).sum())]
         return syn, hyp, loc, counts
 
@@ -282,6 +297,125 @@ def test_two_corrupt_chunks(cuda, code):
             assert loc.tolist() == [MANY, MANY, CLEAN, MANY, MANY] and counts == [0, 4]
         finally:
             rig.close()
+
+
+# ---------------------------------------------------------------- hypotheses that hold in different places
+ADVERSARIAL = ("rs63", "rs164", "r6_62", "cg63", "cg164")
+
+
+def placements(code, packet, size):
+    """{name: (b, b2)}: two chunk bytes in two columns that one dword, one lane unit, one lane, one wave, one
+    tile and two tiles of the locate kernel of this shape hold; the kernel's shape from the engine's prediction"""
+    _, k, m, _ = TC.spec(code)
+    f = E.predict_form("loc", 2 if packet else 1, k, m, packet, size)
+    if not f.sliced:
+        lane, step = 4 * f.VW, 256 * 4 * f.VW
+        tile, b = step * f.IT, 3 * 4 * f.VW  # lane 3 of the first tile
+        out = {"one dword": (b, b + 1), "two dwords of a lane unit": (b, b + 4), "two lanes of a wave": (b, b + lane),
+               "two waves of a tile": (b, b + 64 * lane), "two tiles": (b, b + tile),
+               "one dword of the ragged tail": (size - 8, size - 7), "two dwords of the ragged tail": (size - 8, size - 4)}
+        if f.IT == 2:
+            out["the two steps of a lane"] = (b, b + step)
+        assert size % tile == 8 and b + tile < size - 8  # the tail is a half lane behind whole tiles
+    else:
+        at = lambda col, x: (col // packet) * 8 * packet + x * packet + col % packet  # chunk byte of bit plane x of a column byte
+        lane, c0 = 4 * f.DW, 2 * 4 * f.DW  # lane 2 of the first column tile
+        tile = 256 * lane
+        # two bit planes of one column byte: the flip values overlap in some bits only, so some elements are wrong
+        # in one chunk, some in the other and some in both
+        out = {"two bit-plane packets of a lane": (at(c0, 0), at(c0, 5)), "two lanes of a wave": (at(c0, 2), at(c0 + lane, 2)),
+               "two waves of a tile": (at(c0, 7), at(c0 + 64 * lane, 7)), "two tiles": (at(c0, 1), at(c0 + tile, 1))}
+        if f.DW > 1:
+            out["two dwords of a lane"] = (at(c0, 3), at(c0 + 4, 3))
+        assert c0 + tile < size // 8
+    assert all(0 <= b < size and 0 <= b2 < size and b != b2 for b, b2 in out.values())
+    return out
+
+
+@pytest.mark.parametrize("code", ADVERSARIAL)
+def test_hypotheses_in_different_places_intersect_to_nothing(cuda, code):
+    """data chunk j1 wrong at byte b, data chunk j2 at byte b2: each column has its own single-chunk
+    explanation, the stripe has none.  hyp is an AND over lanes (the vote), waves and tiles (atomicAnd): the
+    two columns are put at every distance over which that reduction runs.  One stripe per placement."""
+    import torch
+
+    _, k, m, _ = CODES[code]
+    packet, size = shapes(code)[-1]
+    places = placements(code, packet, size)
+    j1, j2 = 1, k - 1
+    rig = Rig(torch, code, packet, size, "off8", nstripes=len(places) + 1)
+    try:
+        for s, (b, b2) in enumerate(places.values()):
+            rig.flip(s, j1, b)
+            rig.flip(s, j2, b2, FLIP2)
+        syn, hyp, loc, counts = rig.want()
+        # the reference says so: every row differs, no chunk explains the stripe
+        for s, name in enumerate(places):
+            assert (syn[s], hyp[s], loc[s]) == ((1 << m) - 1, 0, MANY), (code, name, syn[s], hyp[s], loc[s])
+        assert loc[-1] == CLEAN and counts == [0, len(places)]
+        rig.expect("two columns")
+    finally:
+        rig.close()
+
+
+# ---------------------------------------------------------------- two corrupt chunks that imitate a third
+def imitation(code, packet, clean, c, a, b, pos):
+    """(stored, consistent, rebuilt): a byte of data chunk c of the clean stripe flipped, and chunks a and b
+    rebuilt from the others by the reference.  With m = 2 that gives a consistent stripe.  With more rows the
+    reference's decode of two chunks leaves m - 2 parity rows out, and no stripe that differs from a consistent
+    one in fewer than m chunks has another single-chunk explanation (the code's distance is m + 1), so the last
+    parity chunks are rebuilt along with a and b, m chunks in all.  stored is the clean stripe with the rebuilt
+    chunks of the consistent one: it differs from the clean stripe in those alone, and from the consistent one
+    in chunk c alone."""
+    _, k, m, _ = TC.spec(code)
+    rebuilt = [a, b]
+    rebuilt += [i for i in range(k + m - 1, k - 1, -1) if i not in rebuilt][:m - 2]
+    y = clean.copy()
+    y[c, pos] ^= FLIP
+    y[rebuilt] = 0
+    ref_decode(code, packet, y, sorted(rebuilt))
+    assert np.array_equal(TC.ref_encode(code, packet, y[:k]), y[k:])
+    stored = clean.copy()
+    stored[rebuilt] = y[rebuilt]
+    assert all(not np.array_equal(stored[i], clean[i]) for i in rebuilt) and c not in rebuilt
+    return stored, y, sorted(rebuilt)
+
+
+@pytest.mark.parametrize("code", ADVERSARIAL)
+def test_two_corrupt_chunks_imitate_a_third(cuda, code):
+    """include/lstore_ec.h: with m = 2 two corrupt chunks can be what a third, innocent one would explain (with
+    m rows: m corrupt chunks, see imitation()).  Chunks a and b (two data chunks; a data and a parity chunk) hold
+    what makes the stripe consistent with a wrong chunk c, in a column of a full tile and in one of the ragged
+    tail: the call names c, and with repair rewrites it."""
+    import torch
+
+    _, k, m, _ = CODES[code]
+    packet, size = shapes(code)[-1]
+    c = k // 2
+    variants = [(a, b, pos) for a, b in ((0, k - 1), (1, k + m - 1)) for pos in (83, size - 3)]
+    rig = Rig(torch, code, packet, size, "off8", nstripes=len(variants) + 1)
+    try:
+        consistent = {}
+        for s, (a, b, pos) in enumerate(variants):
+            stored, consistent[s], _ = imitation(code, packet, rig.full[s], c, a, b, pos)
+            rig.write(s, stored, ("imitation", c, a, b, pos))
+        syn, hyp, loc, counts = rig.want()
+        # the reference says so: chunk c is the one explanation
+        assert loc.tolist() == [c] * len(variants) + [CLEAN] and counts == [len(variants), 0]
+        assert (hyp[:-1] == 1 << c).all() and (syn[:-1] == (1 << m) - 1).all()
+        rig.expect("imitation")
+        # repaired: chunk c holds the consistent stripe's bytes, nothing else changed
+        after = rig.arena.clone()
+        for s, y in consistent.items():
+            a0 = rig.lay.start(c, s)
+            after[a0:a0 + size] = torch.from_numpy(y[c].copy()).cuda()
+        got = rig.locate(repair=True)
+        for g, w, name in zip(got[:3], (syn, hyp, loc), ("syndrome", "hyp", "located")):
+            assert np.array_equal(g, w), f"{code}: {name} {g} != {w}"
+        assert got[3].tolist() == counts
+        LY.assert_arena(rig.lay, rig.arena.cpu().numpy(), after.cpu().numpy(), f"{code} imitation, repaired")
+    finally:
+        rig.close()
 
 
 # ---------------------------------------------------------------- repair

@@ -101,7 +101,7 @@ class Rig:
 
     def __init__(self, torch, code, packet, size, layout, n_shift, first, nstripes=None):
         self.torch, self.code, self.packet, self.size = torch, code, packet, size
-        _, self.k, self.m, _ = CODES[code]
+        _, self.k, self.m, _ = TC.spec(code)
         self.n = self.k + self.m
         self.nstripes = nstripes = nstripes or 2 * self.n + 1  # every rotation class at least twice, no multiple of n
         self.n_shift, self.first = n_shift, first
@@ -153,7 +153,7 @@ class Rig:
                 st[i, b] ^= v
             for i in ch:
                 st[i] ^= 0xFF
-            syn[s], hyp[s], loc[s] = TL.expected(self.code, self.packet, st, ("rotated", N, s, tuple(fl), tuple(ch)))
+            syn[s], hyp[s], loc[s] = TL.expected(self.code, self.packet, st, (N, s, tuple(fl), tuple(ch)))
         dev = loc.copy()
         for s in np.flatnonzero(loc < n):
             dev[s] = self.dev_of(int(s), int(loc[s]))
