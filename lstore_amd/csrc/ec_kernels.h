@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include <tuple>
+#include <type_traits>
 #include <utility>
 
 namespace lsec {
@@ -160,7 +161,7 @@ hipError_t launch_pattern_bitsliced(const PatternArgs &a, int rmax, hipStream_t 
 // rows of every stripe in registers, as the encode kernels do, and compares them with the stored
 // parity chunks instead of storing them.  Bit r of syndrome[s] is set when row r of stripe s
 // differs anywhere; bad_count (may be null) counts the stripes whose word became nonzero.  Both
-// are zeroed by the caller (check_dev's hipMemsetAsync, ahead of the kernel on the same stream):
+// are zeroed by the caller (scrub_dev's hipMemsetAsync, ahead of the kernel on the same stream):
 // the kernels only ever OR bits in, one returning atomic per wave that found a difference, and
 // the wave whose atomic returns 0 -- the first to make the word nonzero, so exactly one per bad
 // stripe -- counts the stripe.  A clean wave writes nothing.  An argument struct of its own:
@@ -180,11 +181,6 @@ struct CheckArgs {
   ShardRef par[kMaxR];    // the stored parity chunks (only read)
 };
 
-// R <= 8; the launch shape is the encode's for the same K x R (bytewise_shape's automatic policy)
-hipError_t launch_check_bytewise(const CheckArgs &a, hipStream_t stream);
-// dw_pref: dwords per lane (1, 2, 4; 0 = 1), as launch_bitsliced
-hipError_t launch_check_bitsliced(const CheckArgs &a, hipStream_t stream, int dw_pref = 0);
-
 // Locating the corrupt chunk (lsec_locate_dev): the check's pass, whose per-row differences
 // S_r = (row r re-formed from the stored data) ^ (stored parity r) are the stripe's syndromes.  One
 // wrong data chunk j gives S_r = Q[r-1][j] * S_0 at every byte column, Q[r-1][j] = g[r][j] / g[0][j]
@@ -200,9 +196,6 @@ struct LocateArgs : CheckArgs {
 
 constexpr unsigned kLocateClean = 0xFF, kLocateMany = 0xFE;  // LSEC_LOCATE_CLEAN / _MANY (lstore_ec.h)
 
-// 2 <= R <= 8; launch shapes are the check's
-hipError_t launch_locate_bytewise(const LocateArgs &a, hipStream_t stream);
-hipError_t launch_locate_bitsliced(const LocateArgs &a, hipStream_t stream, int dw_pref = 0);
 // One thread per stripe, behind the accumulate launches: masks hyp[s] to K bits, writes located[s]
 // (kLocateClean, K + r, j or kLocateMany: the rules of lsec_locate_dev) and, with counts, adds the
 // located stripes to counts[0] and the kLocateMany ones to counts[1] (zeroed by the caller).
@@ -238,10 +231,21 @@ struct LocateRotArgs : CheckRotArgs {
   unsigned long long *hyp;
 };
 
-hipError_t launch_check_rot_bytewise(const CheckRotArgs &a, hipStream_t stream);
-hipError_t launch_check_rot_bitsliced(const CheckRotArgs &a, hipStream_t stream, int dw_pref = 0);
-hipError_t launch_locate_rot_bytewise(const LocateRotArgs &a, hipStream_t stream);
-hipError_t launch_locate_rot_bitsliced(const LocateRotArgs &a, hipStream_t stream, int dw_pref = 0);
+// What tells the four argument structs apart, to the host's launch path and to the kernels' tile
+// bodies alike: a locate struct adds ratio and hyp, a rotated one takes its refs from sh.
+template <typename Args>
+constexpr bool kLocArgs = std::is_same<Args, LocateArgs>::value || std::is_same<Args, LocateRotArgs>::value;
+template <typename Args>
+constexpr bool kRotArgs = std::is_base_of<CheckRotArgs, Args>::value;
+
+// The accumulate launch of a check or locate, for each of CheckArgs, LocateArgs, CheckRotArgs and
+// LocateRotArgs.  R <= 8 (a locate: 2 <= R); the launch shape is the encode's for the same K x R
+// (bytewise_shape's automatic policy), and a locate's and a rotated form's are the check's.
+template <typename Args>
+hipError_t launch_scrub_bytewise(const Args &a, hipStream_t stream);
+// dw_pref: dwords per lane (1, 2, 4; 0 = 1), as launch_bitsliced
+template <typename Args>
+hipError_t launch_scrub_bitsliced(const Args &a, hipStream_t stream, int dw_pref = 0);
 // launch_locate_finalize's verdict, and with it the physical device of each located chunk:
 // located_dev[s] (may be null) = (located[s] - rot_s) mod rot_n, both sentinels passed through, and
 // one atomic add per located stripe into dev_faults[located_dev[s]] (may be null; rot_n words,

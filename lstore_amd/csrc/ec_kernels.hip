@@ -100,9 +100,10 @@ int lane_dwords(int want, int packet) {
   return dw;
 }
 
-// dwords per lane of a bit-sliced check and of a bit-sliced locate (one past kLocWideRows rows)
-int chk_lane_dwords(int dw_pref, int packet) { return lane_dwords(dw_pref, packet); }
-int loc_lane_dwords(int R, int dw_pref, int packet) { return lane_dwords(R <= kLocWideRows ? dw_pref : 1, packet); }
+// dwords per lane of a bit-sliced check or locate (a locate of more than kLocWideRows rows: one)
+int scrub_lane_dwords(bool locates, int R, int dw_pref, int packet) {
+  return lane_dwords(!locates || R <= kLocWideRows ? dw_pref : 1, packet);
+}
 
 // the device of stream st (the current device for the null stream), or -1
 int stream_device(hipStream_t st) {
@@ -389,37 +390,42 @@ hipError_t launch_pattern_bitsliced(const PatternArgs &a, int rmax, hipStream_t 
   return by_r(rmax, [&](auto r) { return dispatch_pat_bitsliced<decltype(r)::value>(a, st, grid); });
 }
 
+// ------------------------------------------------------------------ check / locate, rotated or not
 namespace {
-bool check_args_ok(const CheckArgs &a) {
-  return a.K >= 1 && a.K <= kMaxK && a.R >= 1 && a.R <= 8 && a.cells && a.syndrome && a.size % 8 == 0 &&
-         reinterpret_cast<uintptr_t>(a.syndrome) % 4 == 0 && reinterpret_cast<uintptr_t>(a.bad_count) % 4 == 0;
-}
-}  // namespace
-
-hipError_t launch_check_bytewise(const CheckArgs &a, hipStream_t st) {
-  if (!check_args_ok(a)) return hipErrorInvalidValue;
-  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int grid = tile_grid(bw_auto(a.K, a.R).tile_bytes(), a.size, a.nstripes);
-  if (!grid) return hipErrorInvalidValue;
-  return by_r(a.R, [&](auto r) { return dispatch_chk_bytewise<decltype(r)::value>(a, st, grid); });
+bool rot_fields_ok(uint32_t rot0, uint32_t rot_step, uint32_t rot_n, int nshards) {
+  return rot_n >= 1 && rot_n == static_cast<uint32_t>(nshards) && rot0 < rot_n && rot_step < rot_n;
 }
 
-hipError_t launch_check_bitsliced(const CheckArgs &a, hipStream_t st, int dw_pref) {
-  if (!check_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
-    return hipErrorInvalidValue;
-  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int dw = chk_lane_dwords(dw_pref, a.packet);
-  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
-  if (!grid) return hipErrorInvalidValue;
-  return by_r(a.R, [&](auto r) { return dispatch_chk_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+// the fields of CheckArgs / CheckRotArgs, then what a rotated struct and a locate struct add
+template <typename Args>
+bool scrub_args_ok(const Args &a) {
+  bool ok = a.K >= 1 && a.K <= kMaxK && a.R >= 1 && a.R <= 8 && a.cells && a.syndrome && a.size % 8 == 0 &&
+            reinterpret_cast<uintptr_t>(a.syndrome) % 4 == 0 && reinterpret_cast<uintptr_t>(a.bad_count) % 4 == 0;
+  if constexpr (kRotArgs<Args>) ok = ok && rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.K + a.R);
+  if constexpr (kLocArgs<Args>) ok = ok && a.R >= 2 && a.ratio && a.hyp && reinterpret_cast<uintptr_t>(a.hyp) % 8 == 0;
+  return ok;
 }
 
-namespace {
-bool locate_args_ok(const LocateArgs &a) {
-  return check_args_ok(a) && a.R >= 2 && a.ratio && a.hyp && reinterpret_cast<uintptr_t>(a.hyp) % 8 == 0;
+// R as a template argument of the dispatch (one row cannot locate: not instantiated)
+template <typename Args, typename F>
+hipError_t scrub_by_r(const Args &a, F f) {
+  return by_r(a.R, [&](auto r) {
+    if constexpr (!kLocArgs<Args> || decltype(r)::value >= 2) return f(r);
+    else return hipErrorInvalidValue;
+  });
 }
 
-// One thread per stripe, after the accumulate launches: the verdict of lsec_locate_dev.
+// The verdict of lsec_locate_dev for one stripe, from its row mask and its k-bit hypothesis mask.
+__device__ __forceinline__ unsigned locate_verdict(unsigned syn, unsigned long long h, int K, int R) {
+  unsigned loc;
+  if (syn == 0) loc = kLocateClean;
+  else if (__popc(syn) == 1) loc = static_cast<unsigned>(K + __ffs(static_cast<int>(syn)) - 1);  // one parity row alone
+  else if (syn == (1u << R) - 1 && __popcll(h) == 1) loc = static_cast<unsigned>(__ffsll(h) - 1);
+  else loc = kLocateMany;
+  return loc;
+}
+
+// One thread per stripe, after the accumulate launches.
 __global__ void k_locate_finalize(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
                                   unsigned *counts, int nstripes, int K, int R) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -427,65 +433,12 @@ __global__ void k_locate_finalize(const unsigned *syndrome, unsigned long long *
   const unsigned syn = syndrome[s];
   const unsigned long long h = hyp[s] & (K >= 64 ? ~0ull : (1ull << K) - 1);
   hyp[s] = h;
-  unsigned loc;
-  if (syn == 0) loc = kLocateClean;
-  else if (__popc(syn) == 1) loc = static_cast<unsigned>(K + __ffs(static_cast<int>(syn)) - 1);  // one parity row alone
-  else if (syn == (1u << R) - 1 && __popcll(h) == 1) loc = static_cast<unsigned>(__ffsll(h) - 1);
-  else loc = kLocateMany;
+  const unsigned loc = locate_verdict(syn, h, K, R);
   located[s] = static_cast<unsigned char>(loc);
   if (counts && syn != 0) atomicAdd(counts + (loc == kLocateMany ? 1 : 0), 1u);
 }
-}  // namespace
 
-hipError_t launch_locate_bytewise(const LocateArgs &a, hipStream_t st) {
-  if (!locate_args_ok(a)) return hipErrorInvalidValue;
-  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int grid = tile_grid(bw_auto(a.K, a.R).tile_bytes(), a.size, a.nstripes);
-  if (!grid) return hipErrorInvalidValue;
-  return by_r(a.R, [&](auto r) {
-    if constexpr (decltype(r)::value >= 2) return dispatch_loc_bytewise<decltype(r)::value>(a, st, grid);
-    else return hipErrorInvalidValue;  // (one row cannot locate: not instantiated)
-  });
-}
-
-hipError_t launch_locate_bitsliced(const LocateArgs &a, hipStream_t st, int dw_pref) {
-  if (!locate_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
-    return hipErrorInvalidValue;
-  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int dw = loc_lane_dwords(a.R, dw_pref, a.packet);
-  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
-  if (!grid) return hipErrorInvalidValue;
-  return by_r(a.R, [&](auto r) {
-    if constexpr (decltype(r)::value >= 2) return dispatch_loc_bitsliced<decltype(r)::value>(a, st, grid, dw);
-    else return hipErrorInvalidValue;
-  });
-}
-
-hipError_t launch_locate_finalize(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
-                                  unsigned *counts, int nstripes, int K, int R, hipStream_t st) {
-  if (!syndrome || !hyp || !located || K < 1 || K > kMaxK || R < 2 || R > 8) return hipErrorInvalidValue;
-  if (nstripes <= 0) return hipSuccess;
-  return launch_kernel(&k_locate_finalize, dim3((nstripes + 255) / 256), dim3(256), st, syndrome, hyp, located, counts,
-                       nstripes, K, R);
-}
-
-// ------------------------------------------------------------------ rotated check / locate / repair
-namespace {
-bool rot_fields_ok(uint32_t rot0, uint32_t rot_step, uint32_t rot_n, int nshards) {
-  return rot_n >= 1 && rot_n == static_cast<uint32_t>(nshards) && rot0 < rot_n && rot_step < rot_n;
-}
-
-bool check_rot_args_ok(const CheckRotArgs &a) {
-  return a.K >= 1 && a.K <= kMaxK && a.R >= 1 && a.R <= 8 && a.cells && a.syndrome && a.size % 8 == 0 &&
-         reinterpret_cast<uintptr_t>(a.syndrome) % 4 == 0 && reinterpret_cast<uintptr_t>(a.bad_count) % 4 == 0 &&
-         rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.K + a.R);
-}
-
-bool locate_rot_args_ok(const LocateRotArgs &a) {
-  return check_rot_args_ok(a) && a.R >= 2 && a.ratio && a.hyp && reinterpret_cast<uintptr_t>(a.hyp) % 8 == 0;
-}
-
-// k_locate_finalize's verdict, and the device it points at: stripe s has rotation
+// k_locate_finalize, and the device its verdict points at: stripe s has rotation
 // (rot0 + s * rot_step) mod rot_n, and logical chunk c of it lives on device (c - rotation) mod rot_n
 __global__ void k_locate_finalize_rot(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
                                       unsigned char *located_dev, unsigned *counts, unsigned *dev_faults, int nstripes,
@@ -495,11 +448,7 @@ __global__ void k_locate_finalize_rot(const unsigned *syndrome, unsigned long lo
   const unsigned syn = syndrome[s];
   const unsigned long long h = hyp[s] & (K >= 64 ? ~0ull : (1ull << K) - 1);
   hyp[s] = h;
-  unsigned loc;
-  if (syn == 0) loc = kLocateClean;
-  else if (__popc(syn) == 1) loc = static_cast<unsigned>(K + __ffs(static_cast<int>(syn)) - 1);  // one parity row alone
-  else if (syn == (1u << R) - 1 && __popcll(h) == 1) loc = static_cast<unsigned>(__ffsll(h) - 1);
-  else loc = kLocateMany;
+  const unsigned loc = locate_verdict(syn, h, K, R);
   located[s] = static_cast<unsigned char>(loc);
   if (counts && syn != 0) atomicAdd(counts + (loc == kLocateMany ? 1 : 0), 1u);
   unsigned dev = loc;  // the sentinels pass through
@@ -512,46 +461,38 @@ __global__ void k_locate_finalize_rot(const unsigned *syndrome, unsigned long lo
 }
 }  // namespace
 
-hipError_t launch_check_rot_bytewise(const CheckRotArgs &a, hipStream_t st) {
-  if (!check_rot_args_ok(a)) return hipErrorInvalidValue;
+template <typename Args>
+hipError_t launch_scrub_bytewise(const Args &a, hipStream_t st) {
+  if (!scrub_args_ok(a)) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
   const int grid = tile_grid(bw_auto(a.K, a.R).tile_bytes(), a.size, a.nstripes);
   if (!grid) return hipErrorInvalidValue;
-  return by_r(a.R, [&](auto r) { return dispatch_chkrot_bytewise<decltype(r)::value>(a, st, grid); });
+  return scrub_by_r(a, [&](auto r) { return dispatch_scrub_bytewise<decltype(r)::value>(a, st, grid); });
 }
 
-hipError_t launch_check_rot_bitsliced(const CheckRotArgs &a, hipStream_t st, int dw_pref) {
-  if (!check_rot_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+template <typename Args>
+hipError_t launch_scrub_bitsliced(const Args &a, hipStream_t st, int dw_pref) {
+  if (!scrub_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int dw = chk_lane_dwords(dw_pref, a.packet);
+  const int dw = scrub_lane_dwords(kLocArgs<Args>, a.R, dw_pref, a.packet);
   const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
   if (!grid) return hipErrorInvalidValue;
-  return by_r(a.R, [&](auto r) { return dispatch_chkrot_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+  return scrub_by_r(a, [&](auto r) { return dispatch_scrub_bitsliced<decltype(r)::value>(a, st, grid, dw); });
 }
 
-hipError_t launch_locate_rot_bytewise(const LocateRotArgs &a, hipStream_t st) {
-  if (!locate_rot_args_ok(a)) return hipErrorInvalidValue;
-  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int grid = tile_grid(bw_auto(a.K, a.R).tile_bytes(), a.size, a.nstripes);
-  if (!grid) return hipErrorInvalidValue;
-  return by_r(a.R, [&](auto r) {
-    if constexpr (decltype(r)::value >= 2) return dispatch_locrot_bytewise<decltype(r)::value>(a, st, grid);
-    else return hipErrorInvalidValue;  // (one row cannot locate: not instantiated)
-  });
-}
+#define LSEC_SCRUB_LAUNCHES(ARGS)                                                  \
+  template hipError_t launch_scrub_bytewise<ARGS>(const ARGS &, hipStream_t);      \
+  template hipError_t launch_scrub_bitsliced<ARGS>(const ARGS &, hipStream_t, int);
+LSEC_SCRUB_LAUNCHES(CheckArgs) LSEC_SCRUB_LAUNCHES(LocateArgs) LSEC_SCRUB_LAUNCHES(CheckRotArgs) LSEC_SCRUB_LAUNCHES(LocateRotArgs)
+#undef LSEC_SCRUB_LAUNCHES
 
-hipError_t launch_locate_rot_bitsliced(const LocateRotArgs &a, hipStream_t st, int dw_pref) {
-  if (!locate_rot_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
-    return hipErrorInvalidValue;
-  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  const int dw = loc_lane_dwords(a.R, dw_pref, a.packet);
-  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
-  if (!grid) return hipErrorInvalidValue;
-  return by_r(a.R, [&](auto r) {
-    if constexpr (decltype(r)::value >= 2) return dispatch_locrot_bitsliced<decltype(r)::value>(a, st, grid, dw);
-    else return hipErrorInvalidValue;
-  });
+hipError_t launch_locate_finalize(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
+                                  unsigned *counts, int nstripes, int K, int R, hipStream_t st) {
+  if (!syndrome || !hyp || !located || K < 1 || K > kMaxK || R < 2 || R > 8) return hipErrorInvalidValue;
+  if (nstripes <= 0) return hipSuccess;
+  return launch_kernel(&k_locate_finalize, dim3((nstripes + 255) / 256), dim3(256), st, syndrome, hyp, located, counts,
+                       nstripes, K, R);
 }
 
 hipError_t launch_locate_finalize_rot(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
@@ -614,7 +555,7 @@ bool predict_launch(int family, bool sliced, int K, int R, int packet, int dw_pr
   if ((loc && R < 2) || (family == kFormPatRot && R != 1)) return false;
   if (sliced) {
     if (packet <= 0 || packet % 4 != 0) return false;
-    const int dw = pat ? 1 : loc ? loc_lane_dwords(R, dw_pref, packet) : chk_lane_dwords(dw_pref, packet);
+    const int dw = pat ? 1 : scrub_lane_dwords(loc, R, dw_pref, packet);
     *out = LaunchForm{family, 1, R, 0, 0, 0, 0, dw};
     return true;
   }

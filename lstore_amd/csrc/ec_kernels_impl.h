@@ -1768,11 +1768,7 @@ __device__ __forceinline__ void loc_bitsliced_wave(const Args &a, uint32_t s, co
 
 // The argument structs of the check's tile bodies: CheckArgs / LocateArgs, whose shards are the
 // logical chunks, and CheckRotArgs / LocateRotArgs, whose shards are the physical devices of a
-// rotated LUN (ec_kernels.h).
-template <typename Args>
-constexpr bool kLocArgs = std::is_same<Args, LocateArgs>::value || std::is_same<Args, LocateRotArgs>::value;
-template <typename Args>
-constexpr bool kRotArgs = std::is_base_of<CheckRotArgs, Args>::value;
+// rotated LUN; kLocArgs and kRotArgs tell them apart (ec_kernels.h).
 
 // Where a tile of stripe s takes the ref of data chunk j / parity row r from: a.in[j] / a.par[r],
 // or, rotated, sh[(j - rot_s) mod n] / sh[(K + r - rot_s) mod n] with rot_s worked out once per
@@ -2036,34 +2032,54 @@ constexpr BwForm chk_bytewise_form(int K, int R) {
   return BwForm{0, sh.it == 1 ? 1 : 2, 4, true};
 }
 
+// The family and the __global__ functions of an argument struct: the check kernels of CheckArgs, the
+// locate kernels of LocateArgs, the rotated forms of theirs.
 template <typename Args>
-constexpr int chk_family() {
-  return std::is_same<Args, LocateArgs>::value      ? kFormLoc
-         : std::is_same<Args, LocateRotArgs>::value ? kFormLocRot
-         : std::is_same<Args, CheckRotArgs>::value  ? kFormChkRot
-                                                    : kFormChk;
-}
+struct ScrubKernels;
+#define LSEC_SCRUB_KERNELS(ARGS, FAMILY, STEM)                      \
+  template <>                                                       \
+  struct ScrubKernels<ARGS> {                                       \
+    static constexpr int family = FAMILY;                           \
+    template <int R, int KC, int IT, bool BF, int VW>               \
+    static auto bytewise() {                                        \
+      return &k_##STEM##_bytewise<R, KC, IT, BF, VW>;               \
+    }                                                               \
+    template <int R, int DW>                                        \
+    static auto bitsliced() {                                       \
+      return &k_##STEM##_bitsliced<R, DW>;                          \
+    }                                                               \
+  };
+LSEC_SCRUB_KERNELS(CheckArgs, kFormChk, chk)
+LSEC_SCRUB_KERNELS(LocateArgs, kFormLoc, loc)
+LSEC_SCRUB_KERNELS(CheckRotArgs, kFormChkRot, chkrot)
+LSEC_SCRUB_KERNELS(LocateRotArgs, kFormLocRot, locrot)
+#undef LSEC_SCRUB_KERNELS
 
-// the check kernel of CheckArgs, the locate kernel of LocateArgs, the rotated forms of theirs
+// one kernel's launch, and its record (the template arguments are known here and nowhere later)
 template <int R, int KC, int IT, bool BF, int VW, typename Args>
-hipError_t chk_or_loc_kernel(const Args &a, hipStream_t st, int grid) {
-  record_launch({chk_family<Args>(), 0, R, KC, IT, VW, BF ? 1 : 0, 0});
-  if constexpr (std::is_same<Args, LocateArgs>::value) return launch_tiled(&k_loc_bytewise<R, KC, IT, BF, VW>, grid, st, a);
-  else if constexpr (std::is_same<Args, LocateRotArgs>::value) return launch_tiled(&k_locrot_bytewise<R, KC, IT, BF, VW>, grid, st, a);
-  else if constexpr (std::is_same<Args, CheckRotArgs>::value) return launch_tiled(&k_chkrot_bytewise<R, KC, IT, BF, VW>, grid, st, a);
-  else return launch_tiled(&k_chk_bytewise<R, KC, IT, BF, VW>, grid, st, a);
+hipError_t scrub_bytewise_kernel(const Args &a, hipStream_t st, int grid) {
+  record_launch({ScrubKernels<Args>::family, 0, R, KC, IT, VW, BF ? 1 : 0, 0});
+  return launch_tiled(ScrubKernels<Args>::template bytewise<R, KC, IT, BF, VW>(), grid, st, a);
 }
 
-// decides the form (chk_bytewise_form), then switches on it
+template <int R, int DW, typename Args>
+hipError_t scrub_bitsliced_kernel(const Args &a, hipStream_t st, int grid) {
+  record_launch({ScrubKernels<Args>::family, 1, R, 0, 0, 0, 0, DW});
+  return launch_tiled(ScrubKernels<Args>::template bitsliced<R, DW>(), grid, st, a);
+}
+
+// The bytewise check or locate of R rows (a locate: R >= 2, one row cannot locate): decides the form
+// (chk_bytewise_form), then switches on it.  A locate and the rotated forms take the check's shape.
 template <int R, typename Args>
-hipError_t chk_bytewise_k(const Args &a, hipStream_t st, int grid) {
+hipError_t dispatch_scrub_bytewise(const Args &a, hipStream_t st, int grid) {
+  static_assert(!kLocArgs<Args> || R >= 2, "locating needs two parity rows");
   const BwForm f = chk_bytewise_form(a.K, R);
   switch (f.kc) {
 #define LSEC_CHK_K(KK)                                                                          \
   case KK: {                                                                                    \
     constexpr BwForm ff = chk_bytewise_form(KK, R);                                             \
     if constexpr (ff.kc == KK)                                                                  \
-      return chk_or_loc_kernel<R, KK, ff.it, ff.bf, ff.vw>(a, st, grid);                      \
+      return scrub_bytewise_kernel<R, KK, ff.it, ff.bf, ff.vw>(a, st, grid);                   \
     break;                                                                                      \
   }
     LSEC_FIXED_K(LSEC_CHK_K)
@@ -2071,117 +2087,37 @@ hipError_t chk_bytewise_k(const Args &a, hipStream_t st, int grid) {
     default: break;
   }
   if constexpr (R == 1) {
-    return chk_or_loc_kernel<1, 0, 1, false, 2>(a, st, grid);
+    return scrub_bytewise_kernel<1, 0, 1, false, 2>(a, st, grid);
   } else {
-    if (f.it == 1) return chk_or_loc_kernel<R, 0, 1, true, 4>(a, st, grid);
-    return chk_or_loc_kernel<R, 0, 2, true, 4>(a, st, grid);
+    if (f.it == 1) return scrub_bytewise_kernel<R, 0, 1, true, 4>(a, st, grid);
+    return scrub_bytewise_kernel<R, 0, 2, true, 4>(a, st, grid);
   }
 }
 
-// a bit-sliced check or locate kernel's record
-template <typename Args>
-void record_bitsliced(int R, int dw) {
-  record_launch({chk_family<Args>(), 1, R, 0, 0, 0, 0, dw});
-}
-
-template <int R>
-hipError_t dispatch_chk_bytewise(const CheckArgs &a, hipStream_t st, int grid) {
-  return chk_bytewise_k<R>(a, st, grid);
-}
-
-template <int R>
-hipError_t dispatch_chk_bitsliced(const CheckArgs &a, hipStream_t st, int grid, int dw) {
-  switch (dw) {
-    case 4: record_bitsliced<CheckArgs>(R, 4); return launch_tiled(&k_chk_bitsliced<R, 4>, grid, st, a);
-    case 2: record_bitsliced<CheckArgs>(R, 2); return launch_tiled(&k_chk_bitsliced<R, 2>, grid, st, a);
-    default: record_bitsliced<CheckArgs>(R, 1); return launch_tiled(&k_chk_bitsliced<R, 1>, grid, st, a);
-  }
-}
-
-// The locate kernels take the check's shape for the same K x R (R >= 2: one row cannot locate).
-// Bit-sliced, the encode's policy gives more than one dword per lane only up to 4 rows
-// (cauchy8_bitsliced_dw), so the wider forms, which would not fit the register file, do not exist.
+// Bit-sliced, dw dwords per lane.  A locate has more than one only up to kLocWideRows rows: the
+// encode's policy asks for none wider (cauchy8_bitsliced_dw), and they would not fit the register
+// file, so those forms do not exist.
 constexpr int kLocWideRows = 4;
-template <int R>
-hipError_t dispatch_loc_bytewise(const LocateArgs &a, hipStream_t st, int grid) {
-  static_assert(R >= 2, "locating needs two parity rows");
-  return chk_bytewise_k<R>(a, st, grid);
-}
-
-template <int R>
-hipError_t dispatch_loc_bitsliced(const LocateArgs &a, hipStream_t st, int grid, int dw) {
-  static_assert(R >= 2, "locating needs two parity rows");
-  // (more than one dword per lane only up to kLocWideRows rows: launch_locate_bitsliced)
-  if constexpr (R <= kLocWideRows) {
-    if (dw == 4) return record_bitsliced<LocateArgs>(R, 4), launch_tiled(&k_loc_bitsliced<R, 4>, grid, st, a);
-    if (dw == 2) return record_bitsliced<LocateArgs>(R, 2), launch_tiled(&k_loc_bitsliced<R, 2>, grid, st, a);
+template <int R, typename Args>
+hipError_t dispatch_scrub_bitsliced(const Args &a, hipStream_t st, int grid, int dw) {
+  static_assert(!kLocArgs<Args> || R >= 2, "locating needs two parity rows");
+  if constexpr (!kLocArgs<Args> || R <= kLocWideRows) {
+    if (dw == 4) return scrub_bitsliced_kernel<R, 4>(a, st, grid);
+    if (dw == 2) return scrub_bitsliced_kernel<R, 2>(a, st, grid);
   }
-  return dw == 1 ? (record_bitsliced<LocateArgs>(R, 1), launch_tiled(&k_loc_bitsliced<R, 1>, grid, st, a)) : hipErrorInvalidValue;
+  return dw == 1 ? scrub_bitsliced_kernel<R, 1>(a, st, grid) : hipErrorInvalidValue;
 }
 
-// The rotated forms take the shapes of their unrotated twins.
-template <int R>
-hipError_t dispatch_chkrot_bytewise(const CheckRotArgs &a, hipStream_t st, int grid) {
-  return chk_bytewise_k<R>(a, st, grid);
-}
-
-template <int R>
-hipError_t dispatch_chkrot_bitsliced(const CheckRotArgs &a, hipStream_t st, int grid, int dw) {
-  switch (dw) {
-    case 4: record_bitsliced<CheckRotArgs>(R, 4); return launch_tiled(&k_chkrot_bitsliced<R, 4>, grid, st, a);
-    case 2: record_bitsliced<CheckRotArgs>(R, 2); return launch_tiled(&k_chkrot_bitsliced<R, 2>, grid, st, a);
-    default: record_bitsliced<CheckRotArgs>(R, 1); return launch_tiled(&k_chkrot_bitsliced<R, 1>, grid, st, a);
-  }
-}
-
-template <int R>
-hipError_t dispatch_locrot_bytewise(const LocateRotArgs &a, hipStream_t st, int grid) {
-  static_assert(R >= 2, "locating needs two parity rows");
-  return chk_bytewise_k<R>(a, st, grid);
-}
-
-template <int R>
-hipError_t dispatch_locrot_bitsliced(const LocateRotArgs &a, hipStream_t st, int grid, int dw) {
-  static_assert(R >= 2, "locating needs two parity rows");
-  if constexpr (R <= kLocWideRows) {
-    if (dw == 4) return record_bitsliced<LocateRotArgs>(R, 4), launch_tiled(&k_locrot_bitsliced<R, 4>, grid, st, a);
-    if (dw == 2) return record_bitsliced<LocateRotArgs>(R, 2), launch_tiled(&k_locrot_bitsliced<R, 2>, grid, st, a);
-  }
-  return dw == 1 ? (record_bitsliced<LocateRotArgs>(R, 1), launch_tiled(&k_locrot_bitsliced<R, 1>, grid, st, a)) : hipErrorInvalidValue;
-}
-
-// instantiated per R in ec_check_rot_inst.hip (1..8) and ec_locate_rot_inst.hip (2..8)
-#define LSEC_DECLARE_CHKROT_R(RR)                                                                   \
-  extern template hipError_t dispatch_chkrot_bytewise<RR>(const CheckRotArgs &, hipStream_t, int);  \
-  extern template hipError_t dispatch_chkrot_bitsliced<RR>(const CheckRotArgs &, hipStream_t, int, int);
-#ifndef LSEC_INSTANTIATING_CHKROT
-LSEC_DECLARE_CHKROT_R(1) LSEC_DECLARE_CHKROT_R(2) LSEC_DECLARE_CHKROT_R(3) LSEC_DECLARE_CHKROT_R(4)
-LSEC_DECLARE_CHKROT_R(5) LSEC_DECLARE_CHKROT_R(6) LSEC_DECLARE_CHKROT_R(7) LSEC_DECLARE_CHKROT_R(8)
-#endif
-#define LSEC_DECLARE_LOCROT_R(RR)                                                                    \
-  extern template hipError_t dispatch_locrot_bytewise<RR>(const LocateRotArgs &, hipStream_t, int);  \
-  extern template hipError_t dispatch_locrot_bitsliced<RR>(const LocateRotArgs &, hipStream_t, int, int);
-#ifndef LSEC_INSTANTIATING_LOCROT
-LSEC_DECLARE_LOCROT_R(2) LSEC_DECLARE_LOCROT_R(3) LSEC_DECLARE_LOCROT_R(4) LSEC_DECLARE_LOCROT_R(5)
-LSEC_DECLARE_LOCROT_R(6) LSEC_DECLARE_LOCROT_R(7) LSEC_DECLARE_LOCROT_R(8)
-#endif
-
-// instantiated per R (2..8) in ec_locate_inst.hip
-#define LSEC_DECLARE_LOC_R(RR)                                                                \
-  extern template hipError_t dispatch_loc_bytewise<RR>(const LocateArgs &, hipStream_t, int); \
-  extern template hipError_t dispatch_loc_bitsliced<RR>(const LocateArgs &, hipStream_t, int, int);
-#ifndef LSEC_INSTANTIATING_LOC
-LSEC_DECLARE_LOC_R(2) LSEC_DECLARE_LOC_R(3) LSEC_DECLARE_LOC_R(4) LSEC_DECLARE_LOC_R(5)
-LSEC_DECLARE_LOC_R(6) LSEC_DECLARE_LOC_R(7) LSEC_DECLARE_LOC_R(8)
-#endif
-
-// instantiated per R in ec_check_inst.hip
-#define LSEC_DECLARE_CHK_R(RR)                                                              \
-  extern template hipError_t dispatch_chk_bytewise<RR>(const CheckArgs &, hipStream_t, int); \
-  extern template hipError_t dispatch_chk_bitsliced<RR>(const CheckArgs &, hipStream_t, int, int);
-#ifndef LSEC_INSTANTIATING_CHK
-LSEC_DECLARE_CHK_R(1) LSEC_DECLARE_CHK_R(2) LSEC_DECLARE_CHK_R(3) LSEC_DECLARE_CHK_R(4)
-LSEC_DECLARE_CHK_R(5) LSEC_DECLARE_CHK_R(6) LSEC_DECLARE_CHK_R(7) LSEC_DECLARE_CHK_R(8)
+// instantiated per argument struct and R in ec_scrub_inst.hip (the checks 1..8, the locates 2..8)
+#define LSEC_DECLARE_SCRUB_R(ARGS, RR)                                                              \
+  extern template hipError_t dispatch_scrub_bytewise<RR, ARGS>(const ARGS &, hipStream_t, int);     \
+  extern template hipError_t dispatch_scrub_bitsliced<RR, ARGS>(const ARGS &, hipStream_t, int, int);
+#define LSEC_DECLARE_SCRUB(ARGS)                                                                    \
+  LSEC_DECLARE_SCRUB_R(ARGS, 2) LSEC_DECLARE_SCRUB_R(ARGS, 3) LSEC_DECLARE_SCRUB_R(ARGS, 4)        \
+  LSEC_DECLARE_SCRUB_R(ARGS, 5) LSEC_DECLARE_SCRUB_R(ARGS, 6) LSEC_DECLARE_SCRUB_R(ARGS, 7) LSEC_DECLARE_SCRUB_R(ARGS, 8)
+#ifndef LSEC_INSTANTIATING_SCRUB
+LSEC_DECLARE_SCRUB_R(CheckArgs, 1) LSEC_DECLARE_SCRUB_R(CheckRotArgs, 1)
+LSEC_DECLARE_SCRUB(CheckArgs) LSEC_DECLARE_SCRUB(LocateArgs) LSEC_DECLARE_SCRUB(CheckRotArgs) LSEC_DECLARE_SCRUB(LocateRotArgs)
 #endif
 
 #define LSEC_DECLARE_R(RR)                                                                         \

@@ -597,6 +597,18 @@ int cauchy8_bitsliced_dw(int K, int R, long long size) {
   return 1;
 }
 
+// Stripes per launch of chunks of C bytes: batches split so that tile indices stay 32-bit.  With
+// `split`, lsec_test_set_pattern_split can lower it: the patterned calls, the repair behind a
+// locate and every launch of the rotated check and locate.
+std::atomic<int> g_pattern_split{0};  // stripes per launch, 0 = the 32-bit tile limit only
+
+long long launch_stripes(long long C, bool split) {
+  long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
+  const int hook = split ? g_pattern_split.load(std::memory_order_relaxed) : 0;
+  if (hook > 0) per = std::min<long long>(per, hook);
+  return per;
+}
+
 // Enqueue out[r] = rows[r] . in  for every stripe, splitting R into launches of <= 8 rows
 // (<= 2 for the bitmatrix kernel) and K into groups of <= lsec::kMaxK inputs.  `image` is the
 // CoefCell[R][K] matrix image, the uint32 row masks [((r*w+l)*K + j)*NW + q] (KBITMATRIX) or the
@@ -614,8 +626,7 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
     if (hipFunction_t fn = lsec::jit::ready(image, R, K)) {  // the matrix's compiled XOR network
       // w = 16 / 32 networks take whole tiles only: the tail columns go to the generic kernel
       const long long whole = kind == KWORDWISE ? size / lsec::jit::gfw_tile(w, R) * lsec::jit::gfw_tile(w, R) : size;
-      // batches split so tile indices stay 32-bit, as below
-      const long long per = std::max(1LL, (1LL << 30) / std::max(1LL, size / 4096 + 1));
+      const long long per = launch_stripes(size, false);
       ShardRef bi[lsec::jit::kMaxCols], bo[lsec::jit::kMaxRows];
       for (int s0 = 0; whole > 0 && s0 < nstripes; s0 += static_cast<int>(std::min<long long>(per, nstripes))) {
         const int n = static_cast<int>(std::min<long long>(per, nstripes - s0));
@@ -668,8 +679,7 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
       a.packet = packet;
       for (int j = 0; j < kg; ++j) a.in[j] = in[k0 + j];
       for (int r = 0; r < a.R; ++r) a.out[r] = out[r0 + r];
-      // split very large batches so tile indices stay 32-bit
-      const long long per = std::max(1LL, (1LL << 30) / std::max(1LL, size / 4096 + 1));
+      const long long per = launch_stripes(size, false);
       for (int s0 = 0; s0 < nstripes; s0 += static_cast<int>(std::min<long long>(per, nstripes))) {
         lsec::ApplyArgs b = a;
         b.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
@@ -731,65 +741,10 @@ int decode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
   return enqueue_apply(decode_kind(e, ent), cells, k, R, in, out, nstripes, C, p->packet_size, st, p->w);
 }
 
-// ---------------------------------------------------------------- parity check
-// lsec_check_dev: syndrome[s] bit r = parity row r of stripe s, as encode_dev would write it,
-// differs from the stored one.  One launch per 32-bit range of tiles (as enqueue_apply) over the
-// encode image, in the encode's launch shape; the words are zeroed on the stream ahead of it.
-// Every limit's message names the limit; nothing is enqueued when one is passed.
-int check_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned *bad_count,
-              hipStream_t st) {
-  lsec::launch_record_reset();  // (lsec_test_launch_record)
-  lio_erasure_plan_t *p = &e->pub;
-  const int kind = kernel_kind(p->method, p->w);
-  if (kind != KBYTEWISE && kind != KBITSLICED)
-    return fail("lsec_check_dev needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
-                JE_method[p->method], p->w, kind);
-  const int k = p->data_strips, m = p->parity_strips;
-  if (k < 1 || k > lsec::kMaxK) return fail("lsec_check_dev: k=%d outside 1..%d (one launch's inputs)", k, lsec::kMaxK);
-  if (m < 1 || m > 8) return fail("lsec_check_dev: m=%d outside 1..8 (one launch's parity rows)", m);
-  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
-  if (check_geometry(p, C)) return -1;
-  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
-  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
-  if (reinterpret_cast<uintptr_t>(bad_count) % 4 != 0) return fail("bad_count %p is not a multiple of 4 bytes", static_cast<void *>(bad_count));
-  if (nstripes == 0) return 0;
-  const void *cells = nullptr;
-  if (encode_cells(e, &cells)) return -1;
-  const int R = encode_rows(e);
-  if (R != m) return fail("lsec_check_dev: the plan encodes %d parity rows, m=%d", R, m);
-  // the call sets every word itself, stripes of an empty chunk included
-  HIP_OK(hipMemsetAsync(syndrome, 0, sizeof(unsigned) * static_cast<size_t>(nstripes), st));
-  if (bad_count) HIP_OK(hipMemsetAsync(bad_count, 0, sizeof(unsigned), st));
-  if (C == 0) return 0;
-  lsec::CheckArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.cells = static_cast<const CoefCell *>(cells);
-  a.K = k;
-  a.R = R;
-  a.size = C;
-  a.packet = p->packet_size;
-  a.bad_count = bad_count;
-  // the encode's dwords per lane for this shape (0: its packet network, which the check has no form of)
-  const int dw = kind == KBITSLICED ? cauchy8_bitsliced_dw(k, R, C) : 0;
-  const long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
-    a.syndrome = syndrome + s0;
-    for (int j = 0; j < k; ++j)
-      a.in[j] = {reinterpret_cast<uint64_t>(sh[j].base) + static_cast<uint64_t>(s0) * sh[j].stride, sh[j].stride};
-    for (int r = 0; r < R; ++r)
-      a.par[r] = {reinterpret_cast<uint64_t>(sh[k + r].base) + static_cast<uint64_t>(s0) * sh[k + r].stride, sh[k + r].stride};
-    const hipError_t err = kind == KBITSLICED ? lsec::launch_check_bitsliced(a, st, dw) : lsec::launch_check_bytewise(a, st);
-    if (err != hipSuccess) return fail("check kernel launch failed: %s", hipGetErrorString(err));
-  }
-  return 0;
-}
-
 // ---------------------------------------------------------------- per-stripe erasure patterns
 // lsec_decode_dev_patterns / lsec_decode_dev_rotated: one table of pattern records and matrix
 // images (ec_kernels.h, PatRecord) per call shape, built from the per-pattern host plans of
 // decode_cache -- the matrices lsec_decode_dev applies -- and cached per device on the plan.
-std::atomic<int> g_pattern_split{0};  // lsec_test_set_pattern_split: stripes per launch, 0 = the 32-bit tile limit only
 
 // (first_stripe * n_shift) mod n in 64 bits: first_stripe >= 0, n_shift >= 0, n >= 1
 uint32_t pattern_rot0(int n, int n_shift, long long first_stripe) {
@@ -1006,14 +961,27 @@ int pattern_table_dev(PlanExt *e, const int *patterns, int npatterns, const int 
   return 0;
 }
 
-// the launches of a patterned call, split so that tile indices stay 32-bit (as enqueue_apply)
+// a shard's ref for the launch that starts at stripe s0, and that launch's first rotation
+ShardRef shard_from(const lsec_shard_t &sh, long long s0) {
+  return {reinterpret_cast<uint64_t>(sh.base) + static_cast<uint64_t>(s0) * sh.stride, sh.stride};
+}
+uint32_t rot0_from(uint32_t rot0, uint32_t rot_step, int n, long long s0) {
+  return static_cast<uint32_t>((rot0 + (s0 % n) * rot_step) % n);
+}
+
+// The launches of a patterned call, split so that tile indices stay 32-bit (as enqueue_apply).  A
+// stripe's pattern id comes from stripe_pattern or, without one, from its rotation.  rotated_repair:
+// the repair behind a rotated locate, whose table is the k+m single erasures of the logical chunks
+// and whose kernel turns each selection into a physical device by the stripe's rotation.
 int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::Dev &dv, const lsec_shard_t *sh, int nstripes,
-                     long long C, const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, hipStream_t st) {
+                     long long C, const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, bool rotated_repair,
+                     hipStream_t st) {
   const lio_erasure_plan_t *p = &e->pub;
   const int n = p->data_strips + p->parity_strips;
   if (nstripes <= 0 || C == 0 || tab.rmax == 0) return 0;  // rmax 0: every pattern is empty
-  lsec::PatternArgs a;
-  std::memset(&a, 0, sizeof(a));
+  const bool rotates = rotated_repair || !stripe_pattern;
+  lsec::PatternRotArgs a;  // (PatternArgs, which the type's rotated launches take too)
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
   a.recs = dv.recs;
   a.cells = dv.cells;
   a.npat = static_cast<uint32_t>(tab.recs.size());
@@ -1022,20 +990,22 @@ int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::De
   a.nshards = n;
   a.size = C;
   a.rot_step = rot_step;
-  a.rot_n = stripe_pattern ? 0 : static_cast<uint32_t>(n);
+  a.rot_n = rotates ? static_cast<uint32_t>(n) : 0;
+  // a Cauchy plan's patterns all take the bit-sliced kernel, 0 / 1 rows too (the same bytes in either layout)
   const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
-  long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
-  const int split = g_pattern_split.load(std::memory_order_relaxed);
-  if (split > 0) per = std::min<long long>(per, split);
+  const long long per = launch_stripes(C, true);
   for (long long s0 = 0; s0 < nstripes; s0 += per) {
     a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
-    for (int i = 0; i < n; ++i)
-      a.sh[i] = {reinterpret_cast<uint64_t>(sh[i].base) + static_cast<uint64_t>(s0) * sh[i].stride, sh[i].stride};
+    for (int i = 0; i < n; ++i) a.sh[i] = shard_from(sh[i], s0);
     a.stripe_pattern = stripe_pattern ? stripe_pattern + s0 : nullptr;
-    a.rot0 = stripe_pattern ? 0 : static_cast<uint32_t>((rot0 + (s0 % n) * rot_step) % n);
-    // a Cauchy plan's patterns all take the bit-sliced kernel, 0 / 1 rows too (the same bytes in either layout)
-    const hipError_t err = sliced ? lsec::launch_pattern_bitsliced(a, tab.rmax, st) : lsec::launch_pattern_bytewise(a, tab.rmax, st);
-    if (err != hipSuccess) return fail("pattern kernel launch failed: %s", hipGetErrorString(err));
+    a.rot0 = rotates ? rot0_from(rot0, rot_step, n, s0) : 0;
+    if (rotated_repair) {
+      const hipError_t err = sliced ? lsec::launch_pattern_rot_bitsliced(a, st) : lsec::launch_pattern_rot_bytewise(a, st);
+      if (err != hipSuccess) return fail("rotated repair kernel launch failed: %s", hipGetErrorString(err));
+    } else {
+      const hipError_t err = sliced ? lsec::launch_pattern_bitsliced(a, tab.rmax, st) : lsec::launch_pattern_bytewise(a, tab.rmax, st);
+      if (err != hipSuccess) return fail("pattern kernel launch failed: %s", hipGetErrorString(err));
+    }
   }
   return 0;
 }
@@ -1053,7 +1023,7 @@ int decode_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long l
   const PatternTable *tab = nullptr;
   PatternTable::Dev dv;
   if (pattern_table_dev(e, patterns, npatterns, nullptr, 0, &tab, &dv)) return -1;
-  return enqueue_patterns(e, *tab, dv, sh, nstripes, C, stripe_pattern, 0, 0, st);
+  return enqueue_patterns(e, *tab, dv, sh, nstripes, C, stripe_pattern, 0, 0, false, st);
 }
 
 int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
@@ -1070,17 +1040,28 @@ int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
   if (pattern_table_dev(e, nullptr, 0, lost, n_shift, &tab, &dv)) return -1;
   const int n = p->data_strips + p->parity_strips;
   return enqueue_patterns(e, *tab, dv, devs, nstripes, C, nullptr, pattern_rot0(n, n_shift, first_stripe),
-                          static_cast<uint32_t>(n_shift % n), st);
+                          static_cast<uint32_t>(n_shift % n), false, st);
 }
 
-// ---------------------------------------------------------------- locate
+// ---------------------------------------------------------------- check / locate, rotated or not
+// lsec_check_dev: syndrome[s] bit r = parity row r of stripe s, as encode_dev would write it,
+// differs from the stored one.  One launch per 32-bit range of tiles (as enqueue_apply) over the
+// encode image, in the encode's launch shape; the words are zeroed on the stream ahead of it.
+//
 // lsec_locate_dev: the check's pass, whose differences S_r are the stripe's syndromes.  A wrong
 // data chunk j shows as S_r = Q[r-1][j] * S_0 at every byte column, Q[r-1][j] = g[r][j] / g[0][j]
 // (the ratio image, cached on the plan per device as the encode image is); a wrong parity chunk r
-// as S_r alone.  The accumulate launches (one per 32-bit range of tiles, as check_dev) OR row masks
-// into syndrome and AND hypothesis masks into hyp, both set on the stream ahead of them; one
-// finalize launch behind them writes located and counts.  With LSEC_LOCATE_REPAIR the patterned
-// decode follows on the stream over the k+m single-erasure table, located as its stripe_pattern.
+// as S_r alone.  The accumulate launches OR row masks into syndrome and AND hypothesis masks into
+// hyp, both set on the stream ahead of them; one finalize launch behind them writes located and
+// counts.  With LSEC_LOCATE_REPAIR the patterned decode follows on the stream over the k+m
+// single-erasure table, located as its stripe_pattern.
+//
+// lsec_check_dev_rotated / lsec_locate_dev_rotated: the same over the k+m physical devices of a
+// rotated LUN.  The kernels work each stripe's rotation out themselves (ec_kernels.h, CheckRotArgs),
+// so the outputs are those of the logical view; the finalize launch also names the device behind
+// each located chunk.  Each later launch's rot0 advances by (s0 mod n) * rot_step.
+//
+// The four calls are one path (scrub_dev) that a ScrubCall steers.
 
 // The host ratio image.  The hypothesis test divides by g[0][j] and tells "row r untouched" from
 // "row r touched" by g[r][j] != 0, so a zero coefficient anywhere is refused.
@@ -1126,276 +1107,176 @@ int ratio_cells_dev(PlanExt *e, const CoefCell **out) {
   return 0;
 }
 
-}  // namespace
+// What tells the four calls apart.  A check leaves the locate fields null, an unrotated call the
+// rotation at 0 and located_dev / dev_faults null.
+struct ScrubCall {
+  const char *name;  // for messages
+  bool rotated;
+  int n_shift;
+  long long first_stripe;
+  bool locates;
+  unsigned long long *hyp;
+  unsigned char *located, *located_dev;
+  unsigned *counts, *dev_faults;
+  int flags;
+};
 
-int locate_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned long long *hyp,
-               unsigned char *located, unsigned *counts, int flags, hipStream_t st) {
-  lsec::launch_record_reset();  // (lsec_test_launch_record)
-  lio_erasure_plan_t *p = &e->pub;
-  const int kind = kernel_kind(p->method, p->w);
-  if (kind != KBYTEWISE && kind != KBITSLICED)
-    return fail("lsec_locate_dev needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
-                JE_method[p->method], p->w, kind);
-  const int k = p->data_strips, m = p->parity_strips, n = k + m;
-  if (k < 1 || k > lsec::kMaxK) return fail("lsec_locate_dev: k=%d outside 1..%d (one launch's inputs, one bit of hyp each)", k, lsec::kMaxK);
-  if (m < 2 || m > 8) return fail("lsec_locate_dev: m=%d outside 2..8 (one parity row cannot locate; one launch's parity rows)", m);
-  if (flags & ~LSEC_LOCATE_REPAIR) return fail("lsec_locate_dev: flags %#x has bits other than LSEC_LOCATE_REPAIR", flags);
-  const bool repair = (flags & LSEC_LOCATE_REPAIR) != 0;
-  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
-  if (check_geometry(p, C)) return -1;
-  if (repair && pattern_limits(p)) return -1;
-  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
-  if (nstripes > 0 && !hyp) return fail("hyp is NULL");
-  if (nstripes > 0 && !located) return fail("located is NULL");
-  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
-  if (reinterpret_cast<uintptr_t>(hyp) % 8 != 0) return fail("hyp %p is not a multiple of 8 bytes", static_cast<void *>(hyp));
-  if (reinterpret_cast<uintptr_t>(counts) % 4 != 0) return fail("counts %p is not a multiple of 4 bytes", static_cast<void *>(counts));
-  const lsec::gf8::Mat *q = nullptr;
-  if (locate_ratio(e, &q)) return -1;  // a zero coefficient is refused here, before any device is touched
-  // the k+m single erasures in chunk order: located[s] is the stripe's pattern id, both sentinels are past the table
-  std::vector<int> singles;
-  for (int i = 0; i < n; ++i) {
-    singles.push_back(i);
-    singles.push_back(-1);
-  }
-  const PatternTable *tab = nullptr;
-  PatternTable::Dev dv;
-  if (repair && pattern_table_dev(e, singles.data(), n, nullptr, 0, &tab, &dv)) return -1;  // cached on the plan
-  if (nstripes == 0) return 0;
-  const void *cells = nullptr;
-  if (encode_cells(e, &cells)) return -1;
-  const int R = encode_rows(e);
-  if (R != m) return fail("lsec_locate_dev: the plan encodes %d parity rows, m=%d", R, m);
-  const CoefCell *ratio = nullptr;
-  if (ratio_cells_dev(e, &ratio)) return -1;
-  // the call sets every element itself, stripes of an empty chunk included
-  HIP_OK(hipMemsetAsync(syndrome, 0, sizeof(unsigned) * static_cast<size_t>(nstripes), st));
-  HIP_OK(hipMemsetAsync(hyp, 0xFF, sizeof(unsigned long long) * static_cast<size_t>(nstripes), st));
-  if (counts) HIP_OK(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), st));
-  if (C > 0) {
-    lsec::LocateArgs a;
-    std::memset(static_cast<void *>(&a), 0, sizeof(a));
-    a.cells = static_cast<const CoefCell *>(cells);
-    a.ratio = ratio;
-    a.K = k;
-    a.R = R;
-    a.size = C;
-    a.packet = p->packet_size;
-    const int dw = kind == KBITSLICED ? cauchy8_bitsliced_dw(k, R, C) : 0;  // the check's shape
-    const long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
-    for (long long s0 = 0; s0 < nstripes; s0 += per) {
-      a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
-      a.syndrome = syndrome + s0;
-      a.hyp = hyp + s0;
-      for (int j = 0; j < k; ++j)
-        a.in[j] = {reinterpret_cast<uint64_t>(sh[j].base) + static_cast<uint64_t>(s0) * sh[j].stride, sh[j].stride};
-      for (int r = 0; r < R; ++r)
-        a.par[r] = {reinterpret_cast<uint64_t>(sh[k + r].base) + static_cast<uint64_t>(s0) * sh[k + r].stride, sh[k + r].stride};
-      const hipError_t err = kind == KBITSLICED ? lsec::launch_locate_bitsliced(a, st, dw) : lsec::launch_locate_bytewise(a, st);
-      if (err != hipSuccess) return fail("locate kernel launch failed: %s", hipGetErrorString(err));
-    }
-  }
-  const hipError_t err = lsec::launch_locate_finalize(syndrome, hyp, located, counts, nstripes, k, R, st);
-  if (err != hipSuccess) return fail("locate finalize launch failed: %s", hipGetErrorString(err));
-  if (repair) return enqueue_patterns(e, *tab, dv, sh, nstripes, C, located, 0, 0, st);
-  return 0;
-}
-
-// ---------------------------------------------------------------- rotated check / locate / repair
-// lsec_check_dev_rotated / lsec_locate_dev_rotated: check_dev and locate_dev over the k+m physical
-// devices of a rotated LUN.  The kernels work each stripe's rotation out themselves (ec_kernels.h,
-// CheckRotArgs), so the outputs are those of the logical view; the finalize launch also names the
-// device behind each located chunk.  Validation order, messages and the split into launches are
-// check_dev's and locate_dev's; each later launch's rot0 advances by (s0 mod n) * rot_step, as
-// enqueue_patterns', and lsec_test_set_pattern_split bounds every launch of these calls.
-namespace {
-
-// stripes per launch: tile indices stay 32-bit; the test hook can lower it
-long long rotated_launch_stripes(long long C) {
-  long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
-  const int split = g_pattern_split.load(std::memory_order_relaxed);
-  if (split > 0) per = std::min<long long>(per, split);
-  return per;
-}
-
-// the fields the rotated argument structs share, for the launch that starts at stripe s0
+// the fields of an argument struct that change from launch to launch, for the one that starts at stripe s0
 template <typename Args>
-void rotated_launch_fields(Args &a, const lsec_shard_t *devs, int n, long long s0, long long per, int nstripes, uint32_t rot0,
-                           uint32_t rot_step) {
+void scrub_launch_fields(Args &a, const ScrubCall &c, const lsec_shard_t *sh, unsigned *syndrome, long long s0, long long per,
+                         int nstripes, uint32_t rot0) {
+  const int n = a.K + a.R;
   a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
-  a.rot0 = static_cast<uint32_t>((rot0 + (s0 % n) * rot_step) % n);
-  for (int i = 0; i < n; ++i)
-    a.sh[i] = {reinterpret_cast<uint64_t>(devs[i].base) + static_cast<uint64_t>(s0) * devs[i].stride, devs[i].stride};
-}
-
-// The repair behind a rotated locate: the patterned decode over the k+m single-erasure table of
-// logical chunks, `located` as its stripe_pattern, the selection rotated per stripe in the kernel.
-int enqueue_repair_rotated(PlanExt *e, const PatternTable &tab, const PatternTable::Dev &dv, const lsec_shard_t *devs,
-                           int nstripes, long long C, const unsigned char *located, uint32_t rot0, uint32_t rot_step,
-                           hipStream_t st) {
-  const lio_erasure_plan_t *p = &e->pub;
-  const int n = p->data_strips + p->parity_strips;
-  if (nstripes <= 0 || C == 0 || tab.rmax == 0) return 0;
-  lsec::PatternRotArgs a;
-  std::memset(static_cast<void *>(&a), 0, sizeof(a));
-  a.recs = dv.recs;
-  a.cells = dv.cells;
-  a.npat = static_cast<uint32_t>(tab.recs.size());
-  a.K = p->data_strips;
-  a.packet = p->packet_size;
-  a.nshards = n;
-  a.size = C;
-  a.rot_step = rot_step;
-  a.rot_n = static_cast<uint32_t>(n);
-  const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
-  const long long per = rotated_launch_stripes(C);
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    rotated_launch_fields(a, devs, n, s0, per, nstripes, rot0, rot_step);
-    a.stripe_pattern = located + s0;
-    const hipError_t err = sliced ? lsec::launch_pattern_rot_bitsliced(a, st) : lsec::launch_pattern_rot_bytewise(a, st);
-    if (err != hipSuccess) return fail("rotated repair kernel launch failed: %s", hipGetErrorString(err));
+  a.syndrome = syndrome + s0;
+  if constexpr (lsec::kLocArgs<Args>) a.hyp = c.hyp + s0;
+  if constexpr (lsec::kRotArgs<Args>) {
+    a.rot0 = rot0_from(rot0, a.rot_step, n, s0);
+    for (int i = 0; i < n; ++i) a.sh[i] = shard_from(sh[i], s0);
+  } else {
+    for (int j = 0; j < a.K; ++j) a.in[j] = shard_from(sh[j], s0);
+    for (int r = 0; r < a.R; ++r) a.par[r] = shard_from(sh[a.K + r], s0);
   }
-  return 0;
 }
 
-}  // namespace
-
-int check_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
-                      unsigned *syndrome, unsigned *bad_count, hipStream_t st) {
-  lsec::launch_record_reset();  // (lsec_test_launch_record)
-  lio_erasure_plan_t *p = &e->pub;
-  const int kind = kernel_kind(p->method, p->w);
-  if (kind != KBYTEWISE && kind != KBITSLICED)
-    return fail("lsec_check_dev_rotated needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
-                JE_method[p->method], p->w, kind);
-  const int k = p->data_strips, m = p->parity_strips, n = k + m;
-  if (k < 1 || k > lsec::kMaxK) return fail("lsec_check_dev_rotated: k=%d outside 1..%d (one launch's inputs)", k, lsec::kMaxK);
-  if (m < 1 || m > 8) return fail("lsec_check_dev_rotated: m=%d outside 1..8 (one launch's parity rows)", m);
-  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
-  if (n_shift < 0) return fail("n_shift %d is negative", n_shift);
-  if (first_stripe < 0) return fail("first_stripe %lld is negative", first_stripe);
-  if (check_geometry(p, C)) return -1;
-  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
-  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
-  if (reinterpret_cast<uintptr_t>(bad_count) % 4 != 0) return fail("bad_count %p is not a multiple of 4 bytes", static_cast<void *>(bad_count));
-  if (nstripes == 0) return 0;
-  const void *cells = nullptr;
-  if (encode_cells(e, &cells)) return -1;
-  const int R = encode_rows(e);
-  if (R != m) return fail("lsec_check_dev_rotated: the plan encodes %d parity rows, m=%d", R, m);
-  // the call sets every word itself, stripes of an empty chunk included
-  HIP_OK(hipMemsetAsync(syndrome, 0, sizeof(unsigned) * static_cast<size_t>(nstripes), st));
-  if (bad_count) HIP_OK(hipMemsetAsync(bad_count, 0, sizeof(unsigned), st));
-  if (C == 0) return 0;
-  lsec::CheckRotArgs a;
-  std::memset(&a, 0, sizeof(a));
+// The accumulate launches: one per 32-bit range of tiles, in the encode's launch shape for K x R.
+template <typename Args>
+int enqueue_scrub(const ScrubCall &c, const lio_erasure_plan_t *p, const void *cells, const CoefCell *ratio, const lsec_shard_t *sh,
+                  int nstripes, long long C, unsigned *syndrome, unsigned *bad_count, uint32_t rot0, uint32_t rot_step,
+                  hipStream_t st) {
+  Args a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
   a.cells = static_cast<const CoefCell *>(cells);
-  a.K = k;
-  a.R = R;
+  a.K = p->data_strips;
+  a.R = p->parity_strips;
   a.size = C;
   a.packet = p->packet_size;
   a.bad_count = bad_count;
-  a.rot_step = static_cast<uint32_t>(n_shift % n);
-  a.rot_n = static_cast<uint32_t>(n);
-  const uint32_t rot0 = pattern_rot0(n, n_shift, first_stripe);
-  const int dw = kind == KBITSLICED ? cauchy8_bitsliced_dw(k, R, C) : 0;  // check_dev's shape
-  const long long per = rotated_launch_stripes(C);
+  if constexpr (lsec::kLocArgs<Args>) a.ratio = ratio;
+  if constexpr (lsec::kRotArgs<Args>) {
+    a.rot_step = rot_step;
+    a.rot_n = static_cast<uint32_t>(a.K + a.R);
+  }
+  // the encode's dwords per lane for this shape (0: its packet network, which the check has no form of)
+  const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
+  const int dw = sliced ? cauchy8_bitsliced_dw(a.K, a.R, C) : 0;
+  const long long per = launch_stripes(C, c.rotated);
   for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    rotated_launch_fields(a, devs, n, s0, per, nstripes, rot0, a.rot_step);
-    a.syndrome = syndrome + s0;
-    const hipError_t err = kind == KBITSLICED ? lsec::launch_check_rot_bitsliced(a, st, dw) : lsec::launch_check_rot_bytewise(a, st);
-    if (err != hipSuccess) return fail("rotated check kernel launch failed: %s", hipGetErrorString(err));
+    scrub_launch_fields(a, c, sh, syndrome, s0, per, nstripes, rot0);
+    const hipError_t err = sliced ? lsec::launch_scrub_bitsliced(a, st, dw) : lsec::launch_scrub_bytewise(a, st);
+    if (err != hipSuccess)
+      return fail("%s%s kernel launch failed: %s", c.rotated ? "rotated " : "", c.locates ? "locate" : "check", hipGetErrorString(err));
   }
   return 0;
+}
+
+// Every limit's message names the limit; nothing is enqueued when one is passed.
+int scrub_dev(PlanExt *e, const ScrubCall &c, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome,
+              unsigned *bad_count, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("%s needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d", c.name,
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  if (k < 1 || k > lsec::kMaxK)
+    return fail("%s: k=%d outside 1..%d (one launch's inputs%s)", c.name, k, lsec::kMaxK, c.locates ? ", one bit of hyp each" : "");
+  if (c.locates && (m < 2 || m > 8))
+    return fail("%s: m=%d outside 2..8 (one parity row cannot locate; one launch's parity rows)", c.name, m);
+  if (m < 1 || m > 8) return fail("%s: m=%d outside 1..8 (one launch's parity rows)", c.name, m);
+  if (c.flags & ~LSEC_LOCATE_REPAIR) return fail("%s: flags %#x has bits other than LSEC_LOCATE_REPAIR", c.name, c.flags);
+  const bool repair = (c.flags & LSEC_LOCATE_REPAIR) != 0;
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (c.n_shift < 0) return fail("n_shift %d is negative", c.n_shift);
+  if (c.first_stripe < 0) return fail("first_stripe %lld is negative", c.first_stripe);
+  if (check_geometry(p, C)) return -1;
+  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
+  if (c.locates && nstripes > 0 && !c.hyp) return fail("hyp is NULL");
+  if (c.locates && nstripes > 0 && !c.located) return fail("located is NULL");
+  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
+  if (reinterpret_cast<uintptr_t>(bad_count) % 4 != 0) return fail("bad_count %p is not a multiple of 4 bytes", static_cast<void *>(bad_count));
+  if (reinterpret_cast<uintptr_t>(c.hyp) % 8 != 0) return fail("hyp %p is not a multiple of 8 bytes", static_cast<void *>(c.hyp));
+  if (reinterpret_cast<uintptr_t>(c.counts) % 4 != 0) return fail("counts %p is not a multiple of 4 bytes", static_cast<void *>(c.counts));
+  if (reinterpret_cast<uintptr_t>(c.dev_faults) % 4 != 0) return fail("dev_faults %p is not a multiple of 4 bytes", static_cast<void *>(c.dev_faults));
+  const PatternTable *tab = nullptr;
+  PatternTable::Dev dv;
+  if (c.locates) {
+    const lsec::gf8::Mat *q = nullptr;
+    if (locate_ratio(e, &q)) return -1;  // a zero coefficient is refused here, before any device is touched
+  }
+  if (repair) {
+    // The k+m single erasures of the logical chunks, in chunk order: located[s] is the stripe's pattern id,
+    // both sentinels are past the table.  The limits above (k <= 64, m <= 8) are inside those of the
+    // patterned decode, so the repair adds none.
+    std::vector<int> singles;
+    for (int i = 0; i < n; ++i) {
+      singles.push_back(i);
+      singles.push_back(-1);
+    }
+    if (nstripes == 0) {
+      // preparing ahead: the matrix work always, the upload where there is a device to upload to
+      int ndev = 0;
+      if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+        PatternTable host_only;
+        return build_pattern_table(e, singles.data(), n, nullptr, 0, host_only);
+      }
+    }
+    if (pattern_table_dev(e, singles.data(), n, nullptr, 0, &tab, &dv)) return -1;  // cached on the plan
+  }
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_cells(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("%s: the plan encodes %d parity rows, m=%d", c.name, R, m);
+  const CoefCell *ratio = nullptr;
+  if (c.locates && ratio_cells_dev(e, &ratio)) return -1;
+  // the call sets every element itself, stripes of an empty chunk included (located and located_dev: the finalize launch)
+  HIP_OK(hipMemsetAsync(syndrome, 0, sizeof(unsigned) * static_cast<size_t>(nstripes), st));
+  if (bad_count) HIP_OK(hipMemsetAsync(bad_count, 0, sizeof(unsigned), st));
+  if (c.locates) HIP_OK(hipMemsetAsync(c.hyp, 0xFF, sizeof(unsigned long long) * static_cast<size_t>(nstripes), st));
+  if (c.counts) HIP_OK(hipMemsetAsync(c.counts, 0, 2 * sizeof(unsigned), st));
+  if (c.dev_faults) HIP_OK(hipMemsetAsync(c.dev_faults, 0, sizeof(unsigned) * static_cast<size_t>(n), st));
+  const uint32_t rot_step = c.rotated ? static_cast<uint32_t>(c.n_shift % n) : 0;
+  const uint32_t rot0 = c.rotated ? pattern_rot0(n, c.n_shift, c.first_stripe) : 0;
+  if (C > 0) {
+    const auto enqueue = c.rotated ? (c.locates ? enqueue_scrub<lsec::LocateRotArgs> : enqueue_scrub<lsec::CheckRotArgs>)
+                                   : (c.locates ? enqueue_scrub<lsec::LocateArgs> : enqueue_scrub<lsec::CheckArgs>);
+    if (enqueue(c, p, cells, ratio, sh, nstripes, C, syndrome, bad_count, rot0, rot_step, st)) return -1;
+  }
+  if (!c.locates) return 0;
+  const hipError_t err = c.rotated ? lsec::launch_locate_finalize_rot(syndrome, c.hyp, c.located, c.located_dev, c.counts, c.dev_faults,
+                                                                      nstripes, k, R, rot0, rot_step, static_cast<uint32_t>(n), st)
+                                   : lsec::launch_locate_finalize(syndrome, c.hyp, c.located, c.counts, nstripes, k, R, st);
+  if (err != hipSuccess) return fail("%slocate finalize launch failed: %s", c.rotated ? "rotated " : "", hipGetErrorString(err));
+  if (repair) return enqueue_patterns(e, *tab, dv, sh, nstripes, C, c.located, rot0, rot_step, c.rotated, st);
+  return 0;
+}
+
+}  // namespace
+
+int check_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned *bad_count,
+              hipStream_t st) {
+  const ScrubCall c = {"lsec_check_dev"};
+  return scrub_dev(e, c, sh, nstripes, C, syndrome, bad_count, st);
+}
+
+int check_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                      unsigned *syndrome, unsigned *bad_count, hipStream_t st) {
+  const ScrubCall c = {"lsec_check_dev_rotated", true, n_shift, first_stripe};
+  return scrub_dev(e, c, devs, nstripes, C, syndrome, bad_count, st);
+}
+
+int locate_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned long long *hyp,
+               unsigned char *located, unsigned *counts, int flags, hipStream_t st) {
+  const ScrubCall c = {"lsec_locate_dev", false, 0, 0, true, hyp, located, nullptr, counts, nullptr, flags};
+  return scrub_dev(e, c, sh, nstripes, C, syndrome, nullptr, st);
 }
 
 int locate_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
                        unsigned *syndrome, unsigned long long *hyp, unsigned char *located, unsigned char *located_dev,
                        unsigned *counts, unsigned *dev_faults, int flags, hipStream_t st) {
-  lsec::launch_record_reset();  // (lsec_test_launch_record)
-  lio_erasure_plan_t *p = &e->pub;
-  const int kind = kernel_kind(p->method, p->w);
-  if (kind != KBYTEWISE && kind != KBITSLICED)
-    return fail("lsec_locate_dev_rotated needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
-                JE_method[p->method], p->w, kind);
-  const int k = p->data_strips, m = p->parity_strips, n = k + m;
-  if (k < 1 || k > lsec::kMaxK)
-    return fail("lsec_locate_dev_rotated: k=%d outside 1..%d (one launch's inputs, one bit of hyp each)", k, lsec::kMaxK);
-  if (m < 2 || m > 8)
-    return fail("lsec_locate_dev_rotated: m=%d outside 2..8 (one parity row cannot locate; one launch's parity rows)", m);
-  if (flags & ~LSEC_LOCATE_REPAIR) return fail("lsec_locate_dev_rotated: flags %#x has bits other than LSEC_LOCATE_REPAIR", flags);
-  const bool repair = (flags & LSEC_LOCATE_REPAIR) != 0;
-  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
-  if (n_shift < 0) return fail("n_shift %d is negative", n_shift);
-  if (first_stripe < 0) return fail("first_stripe %lld is negative", first_stripe);
-  if (check_geometry(p, C)) return -1;
-  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
-  if (nstripes > 0 && !hyp) return fail("hyp is NULL");
-  if (nstripes > 0 && !located) return fail("located is NULL");
-  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
-  if (reinterpret_cast<uintptr_t>(hyp) % 8 != 0) return fail("hyp %p is not a multiple of 8 bytes", static_cast<void *>(hyp));
-  if (reinterpret_cast<uintptr_t>(counts) % 4 != 0) return fail("counts %p is not a multiple of 4 bytes", static_cast<void *>(counts));
-  if (reinterpret_cast<uintptr_t>(dev_faults) % 4 != 0) return fail("dev_faults %p is not a multiple of 4 bytes", static_cast<void *>(dev_faults));
-  const lsec::gf8::Mat *q = nullptr;
-  if (locate_ratio(e, &q)) return -1;  // a zero coefficient is refused here, before any device is touched
-  // locate_dev's table: the k+m single erasures of the logical chunks, in chunk order.  The limits above
-  // (k <= 64, m <= 8) are inside those of the patterned decode, so the repair adds none.
-  std::vector<int> singles;
-  for (int i = 0; i < n; ++i) {
-    singles.push_back(i);
-    singles.push_back(-1);
-  }
-  const PatternTable *tab = nullptr;
-  PatternTable::Dev dv;
-  if (repair && nstripes == 0) {
-    // preparing ahead: the matrix work always, the upload where there is a device to upload to
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-      PatternTable host_only;
-      return build_pattern_table(e, singles.data(), n, nullptr, 0, host_only);
-    }
-  }
-  if (repair && pattern_table_dev(e, singles.data(), n, nullptr, 0, &tab, &dv)) return -1;  // cached on the plan
-  if (nstripes == 0) return 0;
-  const void *cells = nullptr;
-  if (encode_cells(e, &cells)) return -1;
-  const int R = encode_rows(e);
-  if (R != m) return fail("lsec_locate_dev_rotated: the plan encodes %d parity rows, m=%d", R, m);
-  const CoefCell *ratio = nullptr;
-  if (ratio_cells_dev(e, &ratio)) return -1;
-  // the call sets every element itself, stripes of an empty chunk included (located and located_dev: the finalize launch)
-  HIP_OK(hipMemsetAsync(syndrome, 0, sizeof(unsigned) * static_cast<size_t>(nstripes), st));
-  HIP_OK(hipMemsetAsync(hyp, 0xFF, sizeof(unsigned long long) * static_cast<size_t>(nstripes), st));
-  if (counts) HIP_OK(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), st));
-  if (dev_faults) HIP_OK(hipMemsetAsync(dev_faults, 0, sizeof(unsigned) * static_cast<size_t>(n), st));
-  const uint32_t rot_step = static_cast<uint32_t>(n_shift % n);
-  const uint32_t rot0 = pattern_rot0(n, n_shift, first_stripe);
-  if (C > 0) {
-    lsec::LocateRotArgs a;
-    std::memset(static_cast<void *>(&a), 0, sizeof(a));
-    a.cells = static_cast<const CoefCell *>(cells);
-    a.ratio = ratio;
-    a.K = k;
-    a.R = R;
-    a.size = C;
-    a.packet = p->packet_size;
-    a.rot_step = rot_step;
-    a.rot_n = static_cast<uint32_t>(n);
-    const int dw = kind == KBITSLICED ? cauchy8_bitsliced_dw(k, R, C) : 0;  // the check's shape
-    const long long per = rotated_launch_stripes(C);
-    for (long long s0 = 0; s0 < nstripes; s0 += per) {
-      rotated_launch_fields(a, devs, n, s0, per, nstripes, rot0, rot_step);
-      a.syndrome = syndrome + s0;
-      a.hyp = hyp + s0;
-      const hipError_t err = kind == KBITSLICED ? lsec::launch_locate_rot_bitsliced(a, st, dw) : lsec::launch_locate_rot_bytewise(a, st);
-      if (err != hipSuccess) return fail("rotated locate kernel launch failed: %s", hipGetErrorString(err));
-    }
-  }
-  const hipError_t err = lsec::launch_locate_finalize_rot(syndrome, hyp, located, located_dev, counts, dev_faults, nstripes, k, R,
-                                                         rot0, rot_step, static_cast<uint32_t>(n), st);
-  if (err != hipSuccess) return fail("rotated locate finalize launch failed: %s", hipGetErrorString(err));
-  if (repair) return enqueue_repair_rotated(e, *tab, dv, devs, nstripes, C, located, rot0, rot_step, st);
-  return 0;
+  const ScrubCall c = {"lsec_locate_dev_rotated", true, n_shift, first_stripe, true, hyp, located, located_dev, counts, dev_faults, flags};
+  return scrub_dev(e, c, devs, nstripes, C, syndrome, nullptr, st);
 }
 
 }  // namespace eng

@@ -53,6 +53,8 @@ def test_zero_stripes_validate_only(rs63):
     rs63.locate_dev_refs([(FAKE + i * 4096, 8192) for i in range(9)], 0, 4096, 0, 0, 0)  # the mirror, NULL outputs
     # NULL bases stay valid with no stripes (the prepare-ahead convention of the *_dev calls)
     assert locate(rs63, shards_of(9, base=0, stride=0), 0, 4096) == 0, E.last_error()
+    # with the repair flag the single-erasure table is prepared: the matrix work where there is no device
+    assert locate(rs63, shards_of(9), 0, 4096, flags=E.LOCATE_REPAIR) == 0, E.last_error()
 
 
 def test_refuses_other_plan_kernels(built):

@@ -7,7 +7,8 @@
  * boxes here), driven from C the way LStore drives it:
  *   CPU part (any host): method names, plan generation for every method incl. refused shapes,
  *     the self-tests behind the CPU test suite (waits, copies, bit-decode planner, DMA lattices,
- *     pinned budget, in-place stall guard), scatter-list straddle sizes.
+ *     pinned budget, in-place stall guard), scatter-list straddle sizes, the validation ladder and
+ *     the validate-only calls of the check and locate calls' one path.
  *   GPU part (when a device is visible): T threads per configuration calling the plan's
  *     encode_block / decode_block per stripe with the parity buffer malloc'd and freed around
  *     every call (segjerase_write_func, segment/jerasure.c:1689-1697, :1882), batched
@@ -149,6 +150,42 @@ static void cpu_part(void) {
       const long long st = lsec_segment_straddle_bytes(p, iov, 4, 3, (int)C);
       CHECK(st == 6 * C, "straddle bytes %lld", st); /* stripe 1 only */
       free(a);
+      et_destroy_plan(p);
+    }
+  }
+  { /* the one path behind the check and locate calls, rotated or not: its validation ladder and the
+       validate-only calls (no stripes: nothing is enqueued, the fake addresses are never read) */
+    lio_erasure_plan_t *p = et_generate_plan(6ll * 4096, REED_SOL_VAN, 6, 3, -1, -1, -1);
+    CHECK(p != NULL, "plan for the scrub ladder");
+    if (p) {
+      const uintptr_t fake = 0x7F0000001000ull;
+      lsec_shard_t sh[9];
+      for (int i = 0; i < 9; ++i) {
+        sh[i].base = (void *)(fake + (uintptr_t)i * 4096);
+        sh[i].stride = 8192;
+      }
+      unsigned *u4 = (unsigned *)fake, *odd4 = (unsigned *)(fake + 2);
+      unsigned long long *u8 = (unsigned long long *)fake, *odd8 = (unsigned long long *)(fake + 4);
+      unsigned char *u1 = (unsigned char *)(fake + 1);
+      CHECK(lsec_check_dev(p, sh, 0, 4096, u4, u4, NULL) == 0, "check, no stripes");
+      CHECK(lsec_check_dev_rotated(p, sh, 0, 4096, 11, 5, u4, u4, NULL) == 0, "rotated check, no stripes");
+      CHECK(lsec_locate_dev(p, sh, 0, 4096, u4, u8, u1, u4, LSEC_LOCATE_REPAIR, NULL) == 0, "locate prepares its repair");
+      CHECK(lsec_locate_dev_rotated(p, sh, 0, 4096, 3, 7, u4, u8, u1, u1, u4, u4, LSEC_LOCATE_REPAIR, NULL) == 0,
+            "rotated locate prepares its repair");
+      CHECK(lsec_check_dev(p, sh, -1, 4096, NULL, NULL, NULL) == -1 && strstr(lsec_last_error(), "nstripes -1"), "check nstripes");
+      CHECK(lsec_check_dev(p, sh, 1, 4096, NULL, NULL, NULL) == -1 && strstr(lsec_last_error(), "syndrome is NULL"), "check NULL");
+      CHECK(lsec_check_dev_rotated(p, sh, 0, 12, -1, 0, NULL, NULL, NULL) == -1 && strstr(lsec_last_error(), "n_shift -1"),
+            "rotated check n_shift");
+      CHECK(lsec_check_dev_rotated(p, sh, 0, 4096, 1, 0, u4, odd4, NULL) == -1 && strstr(lsec_last_error(), "bad_count 0x"),
+            "rotated check bad_count");
+      CHECK(lsec_locate_dev(p, sh, 0, 4096, NULL, NULL, NULL, NULL, 6, NULL) == -1 && strstr(lsec_last_error(), "flags 0x6"),
+            "locate flags");
+      CHECK(lsec_locate_dev(p, sh, 1, 4096, u4, odd8, NULL, NULL, 0, NULL) == -1 && strstr(lsec_last_error(), "located is NULL"),
+            "locate NULL");
+      CHECK(lsec_locate_dev_rotated(p, sh, 0, 4096, 1, -1, NULL, NULL, NULL, NULL, NULL, NULL, 0, NULL) == -1 &&
+                strstr(lsec_last_error(), "first_stripe -1"), "rotated locate first_stripe");
+      CHECK(lsec_locate_dev_rotated(p, sh, 0, 4096, 1, 0, u4, u8, u1, u1, u4, odd4, 0, NULL) == -1 &&
+                strstr(lsec_last_error(), "dev_faults 0x"), "rotated locate dev_faults");
       et_destroy_plan(p);
     }
   }
