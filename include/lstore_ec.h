@@ -298,6 +298,53 @@ int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
                             unsigned int *counts, unsigned int *dev_faults,
                             int flags, void *stream);
 
+/* Parity update for a partial-stripe write, one pass: c of a stripe's k data chunks change, and the
+ * parity follows without the other k - c chunks being read, or even being on the device.  Purely
+ * additive too: the version stays 3, a caller detects the call by its symbol.
+ *
+ * - `shards` are the k+m logical chunks as for lsec_encode_dev, but only shards[cols[i]] (the old
+ *   contents of the changed chunks) and shards[k .. k+m) (the parity) are used.  Every other data
+ *   entry is ignored entirely: its base may be NULL or misaligned, it is not validated, and it
+ *   never reaches the kernel, whose arguments carry only the c old, the c fresh and the m parity
+ *   chunks.
+ * - `cols` is a -1 terminated list of c distinct data chunk ids, 1 <= c <= k, each in 0..k-1, in
+ *   any order; fresh[i] is the new content of chunk cols[i], under the layout rule of `shards`.
+ * - Effect, per stripe and byte column: parity_r ^= sum_i g[r][cols[i]] * (old_i ^ fresh_i) for
+ *   every r < m, g the plan's coding matrix (for Cauchy the bit-sliced product over packets, as the
+ *   encode forms it).  Nothing else is computed.  So:
+ *     1. a stripe that was consistent comes out with exactly the parity bytes lsec_encode_dev
+ *        writes for the data with those chunks replaced;
+ *     2. any stripe keeps its syndrome: lsec_check_dev over the stripe with the chunks replaced
+ *        gives after the call the word it gave over the old stripe before it.  An inconsistent
+ *        stripe is neither healed nor made worse.
+ * - Without LSEC_UPDATE_STORE only the m parity chunks are written; shards[cols[i]] and fresh are
+ *   only read.  With the flag shards[cols[i]] <- fresh[i] in the same pass, from the registers
+ *   that hold the fresh bytes: one store more per unit and no further load.  fresh is never
+ *   written.
+ * - fresh must not overlap shards; the changed chunks and the parity must not overlap one another.
+ * - Layout, alignment and block_size rules are those of lsec_encode_dev (lsec_shard_t, above; for
+ *   Cauchy block_size is a multiple of 8 * packet_size), applied to the c old, the c fresh and the
+ *   m parity chunks.
+ * - Plans: lsec_plan_kernel 1 (bytewise GF(2^8): RS, r6, raid4) and 2 (bit-sliced GF(2^8): Cauchy
+ *   at w = 8), k <= 64, 1 <= m <= 8.
+ * - nstripes == 0 validates everything, returns 0 and touches no GPU; all bases may then be NULL,
+ *   cols may not.
+ * - Nothing is allocated and nothing is uploaded per call: the kernel indexes the plan's cached
+ *   encode image by column.
+ * - One column list per call: stripes that change in different chunks take separate calls.  There
+ *   are no per-stripe lists and there is no form over the physical devices of a rotated LUN.
+ * - Every refusal -- plan kernels 3-5; k or m out of range; a NULL shards, cols or fresh; an empty
+ *   list; an id < 0, an id >= k (a parity id) or a duplicate; more than k ids; unknown flag bits; a
+ *   misaligned base, or a misaligned stride with nstripes > 1; a bad block_size; a negative
+ *   nstripes -- returns -1 with a message for lsec_last_error that names the limit, and nothing is
+ *   enqueued.  There is no fallback to re-encoding.
+ * Enqueued on `stream`; returns without synchronising.  0 / -1. */
+#define LSEC_UPDATE_STORE 1   /* flags: also write the fresh bytes over the old data chunks */
+
+int lsec_update_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
+                    long long block_size, const int *cols, const lsec_shard_t *fresh,
+                    int flags, void *stream);
+
 /* Per-stripe "magic": the 4-byte little-endian zlib adler32 over the concatenation of a
  * stripe's k+m chunks that LStore's erasure segment stores in front of every chunk
  * (je_cksum_calc, src/lio/segment/jerasure.c:169-182; checked by je_cksum_compare, :188-194).

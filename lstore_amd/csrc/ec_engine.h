@@ -154,6 +154,9 @@ int check_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, uns
 int locate_ratio(PlanExt *e, const lsec::gf8::Mat **out);  // the host ratio image; no device is touched
 int locate_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned long long *hyp,
                unsigned char *located, unsigned *counts, int flags, hipStream_t st);
+// parity update for a partial-stripe write: parity ^= g[.][cols[i]] * (old_i ^ fresh_i); only sh[cols[i]] and the parity are looked at
+int update_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *cols, const lsec_shard_t *fresh, int flags,
+               hipStream_t st);
 // both over the k+m physical devices of a rotated LUN (devs[i]: device i, as decode_dev_rotated's)
 int check_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
                       unsigned *syndrome, unsigned *bad_count, hipStream_t st);

@@ -265,14 +265,47 @@ struct PatternRotArgs : PatternArgs {};
 hipError_t launch_pattern_rot_bytewise(const PatternRotArgs &a, hipStream_t stream);
 hipError_t launch_pattern_rot_bitsliced(const PatternRotArgs &a, hipStream_t stream);
 
+// Parity update for partial-stripe writes (lsec_update_dev): c of a stripe's K data chunks change
+// from old_i to fresh_i, and the code is linear, so every parity row r takes
+//   par_r ^= sum_i cells[r][col[i]] * (old_i ^ fresh_i)
+// (for Cauchy the bit-sliced product over packets, as the encode forms it).  One streaming pass
+// reads 2c + R chunks of a stripe and writes R, or R + c with `store`, which also puts the fresh
+// bytes over the old ones from the registers that hold them.  Only the changed chunks and the
+// parity travel here: a data chunk that does not change has no ref in the struct, so no kernel can
+// read it.  cells is the plan's cached encode image, indexed by column: nothing is uploaded per
+// call.  An argument struct of its own: ApplyArgs, PatternArgs and the four scrub structs keep
+// their layout.
+struct UpdateArgs {
+  const CoefCell *cells;  // the encode image, R x K, row-major (device memory)
+  int K, R;
+  int c;                  // changed chunks, 1..K
+  int nstripes;
+  int packet;             // bit-sliced: packet size P (bytes)
+  int store;              // != 0: old[i] <- fresh[i] in the same pass
+  int64_t size;           // bytes per shard (chunk C)
+  unsigned *tiles;        // as ApplyArgs
+  uint32_t tiles_pre;
+  uint32_t tile_phase;
+  alignas(4) uint8_t col[kMaxK];  // data chunk id of changed chunk i (distinct, < K)
+  ShardRef old[kMaxK];    // the changed chunks as stored (read; written with store)
+  ShardRef fresh[kMaxK];  // their new contents (only read)
+  ShardRef par[8];        // the parity chunks (read and written)
+};
+
+// R <= 8, 1 <= c <= K <= kMaxK, every col[i] < K.  The launch shapes are the update's own
+// (upd_bytewise_form: they depend on R alone, the columns being walked at run time).
+hipError_t launch_update_bytewise(const UpdateArgs &a, hipStream_t stream);
+// dw_pref: dwords per lane (1, 2, 4; 0 = 1), as launch_bitsliced
+hipError_t launch_update_bitsliced(const UpdateArgs &a, hipStream_t stream, int dw_pref = 0);
+
 // Which kernel ran (test hooks lsec_test_launch_record / lsec_test_predict_forms, ec_plan.cpp).  The
-// check, locate, patterned and rotated calls are families of separately compiled kernels; a form
+// check, locate, patterned, rotated and update calls are families of separately compiled kernels; a form
 // names one of them by its template arguments: bytewise R, KC (0: K at run time), IT, VW, BF; or
 // bit-sliced R, DW (the patterned bit-sliced kernels have one dword per lane).  The per-R dispatch
 // functions record the form at the one place where the template arguments are known; the record
 // is the calling thread's, holds the launches since launch_record_reset() in order (the engine
 // resets it on entry to each of those calls) and costs a few host stores per launch.
-enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot };
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd };
 struct LaunchForm {
   int family, sliced, R, KC, IT, VW, BF, DW;
 };

@@ -2120,6 +2120,224 @@ LSEC_DECLARE_SCRUB_R(CheckArgs, 1) LSEC_DECLARE_SCRUB_R(CheckRotArgs, 1)
 LSEC_DECLARE_SCRUB(CheckArgs) LSEC_DECLARE_SCRUB(LocateArgs) LSEC_DECLARE_SCRUB(CheckRotArgs) LSEC_DECLARE_SCRUB(LocateRotArgs)
 #endif
 
+// ------------------------------------------------------------------ parity update
+// lsec_update_dev (ec_kernels.h, UpdateArgs): parity_r ^= sum_i g[r][col[i]] * (old_i ^ fresh_i) over
+// the c changed data chunks of a stripe.  The tile loop, the lanes and the arithmetic are the
+// encode's; the accumulators start as the stored parity rows instead of zero, so those loads go out
+// ahead of the columns' and nothing but the accumulators holds them.  old_i ^ fresh_i is formed once
+// per column and multiplied once per row; its cell is cells[r * K + col[i]], col[i] from the kernel
+// arguments and so uniform over the wave (a scalar load, as the patterned decode's cells).  With
+// UpdateArgs::store the fresh units, already in registers, go over the old ones.  One lane reads
+// and writes each byte of a tile: no atomics, no LDS, no cross-lane traffic.
+
+// col[i] of the call (i uniform over the workgroup): the byte out of its aligned word of the arguments
+__device__ __forceinline__ uint32_t upd_col(const UpdateArgs &a, int i) {
+  uint32_t w;
+  __builtin_memcpy(&w, a.col + (i & ~3), 4);
+  return (w >> (8 * (i & 3))) & 0xFFu;
+}
+
+// BF as k_gf8_bytewise: the branch-free coefficient path, or per-cell branches (R = 1).  Row 0's
+// all-ones flag is not used: the tables of coefficient 1 give the same bytes.
+template <int R, int IT, int VW, bool BF>
+__device__ __forceinline__ void upd_bytewise_tiles(const UpdateArgs &a) {
+  typedef typename VecT<VW>::type V;
+  constexpr int kStep = BwTile<IT, VW>::kStep;
+  constexpr int kTile = BwTile<IT, VW>::kBytes;
+  constexpr int kLane = 4 * VW;
+  const int K = a.K;
+  const int64_t C = a.size;
+  const uint32_t tiles_per_stripe = static_cast<uint32_t>((C + kTile - 1) / kTile);
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+  const bool store = a.store != 0;  // uniform over the launch
+
+  for_tiles<(kTile >= 8192 ? 1 : 8192 / kTile)>(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
+    const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
+
+    V acc[IT][R];
+    if (full) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint64_t q = a.par[r].base + s * a.par[r].stride + off0;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) acc[it][r] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
+      }
+      for (int i = 0; i < a.c; ++i) {
+        const ShardRef old = a.old[i], fresh = a.fresh[i];
+        const uint64_t po = old.base + s * old.stride + off0, pf = fresh.base + s * fresh.stride + off0;
+        V d[IT], f[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+          d[it] = __builtin_nontemporal_load(gptr<V>(po + it * kStep));
+          f[it] = __builtin_nontemporal_load(gptr<V>(pf + it * kStep));
+        }
+        if (store) {
+#pragma unroll
+          for (int it = 0; it < IT; ++it) put_nt<false, V>(po + it * kStep, f[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) d[it] ^= f[it];
+        bw_acc1<R, IT, VW, BF, false>(acc, d, cells, K, static_cast<int>(upd_col(a, i)));
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint64_t q = a.par[r].base + s * a.par[r].stride + off0;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) put_nt<false, V>(q + it * kStep, acc[it][r]);
+      }
+    } else {
+      // ragged last tile: units past C read as zero and are not stored, a half unit moves 8 bytes
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint64_t q = a.par[r].base + s * a.par[r].stride;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) acc[it][r] = load_ragged<VW>(q, off0 + it * kStep, C);
+      }
+      for (int i = 0; i < a.c; ++i) {
+        const ShardRef old = a.old[i], fresh = a.fresh[i];
+        const uint64_t po = old.base + s * old.stride, pf = fresh.base + s * fresh.stride;
+        V d[IT], f[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+          d[it] = load_ragged<VW>(po, off0 + it * kStep, C);
+          f[it] = load_ragged<VW>(pf, off0 + it * kStep, C);
+        }
+        if (store) {
+#pragma unroll
+          for (int it = 0; it < IT; ++it) store_ragged<false, VW>(po, off0 + it * kStep, C, f[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) d[it] ^= f[it];
+        bw_acc1<R, IT, VW, BF, false>(acc, d, cells, K, static_cast<int>(upd_col(a, i)));
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint64_t q = a.par[r].base + s * a.par[r].stride;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
+      }
+    }
+  }, a.tile_phase);
+}
+
+template <int R, int IT, int VW, bool BF>
+__global__ __launch_bounds__(kBlock) void k_upd_bytewise(UpdateArgs a) {
+  upd_bytewise_tiles<R, IT, VW, BF>(a);
+}
+
+// k_gf8_bitsliced's lanes and doubling loop over old_i ^ fresh_i, the accumulators starting as the
+// 8 * R stored parity words.  Lanes past the end of a ragged last tile leave the tile body.
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_upd_bitsliced(UpdateArgs a) {
+  typedef typename VecT<DW>::type V;
+  const int K = a.K;
+  const uint32_t P = static_cast<uint32_t>(a.packet);
+  const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
+  constexpr uint32_t kTile = kBlock * 4 * DW;
+  const uint32_t tiles_per_stripe = (col_bytes + kTile - 1) / kTile;
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+  const bool store = a.store != 0;  // uniform over the launch
+
+  for_tiles(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * (4 * DW);
+    if (colb >= col_bytes) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
+    const uint32_t sp = colb / P;
+    const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+
+    V acc[R][8];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const uint64_t q = a.par[r].base + s * a.par[r].stride + off;
+#pragma unroll
+      for (int x = 0; x < 8; ++x) acc[r][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
+    }
+    for (int i = 0; i < a.c; ++i) {
+      const ShardRef old = a.old[i], fresh = a.fresh[i];
+      const uint64_t po = old.base + s * old.stride + off, pf = fresh.base + s * fresh.stride + off;
+      V e[8], f[8];
+#pragma unroll
+      for (int x = 0; x < 8; ++x) {
+        e[x] = __builtin_nontemporal_load(gptr<V>(po + x * P));
+        f[x] = __builtin_nontemporal_load(gptr<V>(pf + x * P));
+      }
+      if (store) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) put_nt<false, V>(po + x * P, f[x]);
+      }
+#pragma unroll
+      for (int x = 0; x < 8; ++x) e[x] ^= f[x];
+      const uint32_t j = upd_col(a, i);
+      uint32_t c[R];
+      uint32_t cm = 0;  // bits used by any row: no doublings past the highest one
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        c[r] = cells[r * K + j].coef;
+        cm |= c[r];
+      }
+      gf8_sliced_mul_acc<0>(acc, e, c, cm);
+    }
+    // The stores go to the addresses the parity loads came from.  Kept from there to here they are
+    // 16 * R VGPRs, more than the accumulators at one dword per lane (R = 8: 236 VGPRs, 2 waves per
+    // SIMD); formed again from an offset the compiler cannot see through, they cost two adds each.
+    int64_t off_st = off;
+    asm volatile("" : "+v"(off_st));
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const uint64_t q = a.par[r].base + s * a.par[r].stride + off_st;
+#pragma unroll
+      for (int x = 0; x < 8; ++x) put_nt<false, V>(q + x * P, acc[r][x]);
+    }
+  }, a.tile_phase);
+}
+
+// The forms (DESIGN.md 3.6 has their registers).  Bytewise: one per R, the changed columns at run
+// time -- one row in the one-row shape of the other kernels (8 B per lane, per-cell branches), two or
+// more branch-free in 16-byte units, two per lane up to kUpdTwoStepRows rows and one beyond, where a
+// second unit's accumulators would cost a wave of occupancy.  Bit-sliced: 1, 2 or 4 dwords per lane up
+// to kUpdWideRows rows, as the locate (the encode's policy asks for none wider), else one.
+constexpr int kUpdTwoStepRows = 4;
+constexpr int kUpdWideRows = kLocWideRows;
+constexpr BwForm upd_bytewise_form(int R) {
+  if (R == 1) return BwForm{0, 1, 2, false};
+  return BwForm{0, R <= kUpdTwoStepRows ? 2 : 1, 4, true};
+}
+
+template <int R>
+hipError_t dispatch_upd_bytewise(const UpdateArgs &a, hipStream_t st, int grid) {
+  constexpr BwForm f = upd_bytewise_form(R);
+  record_launch({kFormUpd, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0});
+  return launch_tiled(&k_upd_bytewise<R, f.it, f.vw, f.bf>, grid, st, a);
+}
+
+template <int R, int DW>
+hipError_t upd_bitsliced_kernel(const UpdateArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormUpd, 1, R, 0, 0, 0, 0, DW});
+  return launch_tiled(&k_upd_bitsliced<R, DW>, grid, st, a);
+}
+
+template <int R>
+hipError_t dispatch_upd_bitsliced(const UpdateArgs &a, hipStream_t st, int grid, int dw) {
+  if constexpr (R <= kUpdWideRows) {
+    if (dw == 4) return upd_bitsliced_kernel<R, 4>(a, st, grid);
+    if (dw == 2) return upd_bitsliced_kernel<R, 2>(a, st, grid);
+  }
+  return dw == 1 ? upd_bitsliced_kernel<R, 1>(a, st, grid) : hipErrorInvalidValue;
+}
+
+// instantiated per R in ec_update_inst.hip
+#define LSEC_DECLARE_UPD_R(RR)                                                                \
+  extern template hipError_t dispatch_upd_bytewise<RR>(const UpdateArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_upd_bitsliced<RR>(const UpdateArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_UPD
+LSEC_DECLARE_UPD_R(1) LSEC_DECLARE_UPD_R(2) LSEC_DECLARE_UPD_R(3) LSEC_DECLARE_UPD_R(4)
+LSEC_DECLARE_UPD_R(5) LSEC_DECLARE_UPD_R(6) LSEC_DECLARE_UPD_R(7) LSEC_DECLARE_UPD_R(8)
+#endif
+
 #define LSEC_DECLARE_R(RR)                                                                         \
   extern template hipError_t dispatch_bytewise<RR>(const ApplyArgs &, hipStream_t, int, int);      \
   extern template hipError_t dispatch_bitsliced<RR>(const ApplyArgs &, hipStream_t, int, int);         \

@@ -599,7 +599,7 @@ int cauchy8_bitsliced_dw(int K, int R, long long size) {
 
 // Stripes per launch of chunks of C bytes: batches split so that tile indices stay 32-bit.  With
 // `split`, lsec_test_set_pattern_split can lower it: the patterned calls, the repair behind a
-// locate and every launch of the rotated check and locate.
+// locate, every launch of the rotated check and locate, and the parity update.
 std::atomic<int> g_pattern_split{0};  // stripes per launch, 0 = the 32-bit tile limit only
 
 long long launch_stripes(long long C, bool split) {
@@ -1279,6 +1279,85 @@ int locate_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
   return scrub_dev(e, c, devs, nstripes, C, syndrome, nullptr, st);
 }
 
+// ---------------------------------------------------------------- parity update
+// lsec_update_dev: parity_r ^= sum_i g[r][cols[i]] * (old_i ^ fresh_i), and with LSEC_UPDATE_STORE
+// old_i <- fresh_i, over the cached encode image: one launch per 32-bit range of tiles (as
+// enqueue_scrub), nothing allocated or uploaded per call.  Only the c changed chunks, their fresh
+// contents and the m parity chunks are looked at: every other entry of sh is never read, here or in
+// the kernel.  One validation ladder, in the order of the header's refusal list; it touches no device.
+int update_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *cols, const lsec_shard_t *fresh,
+               int flags, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("lsec_update_dev needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips;
+  if (k < 1 || k > lsec::kMaxK) return fail("lsec_update_dev: k=%d outside 1..%d (one launch's columns)", k, lsec::kMaxK);
+  if (m < 1 || m > 8) return fail("lsec_update_dev: m=%d outside 1..8 (one launch's parity rows)", m);
+  if (!sh) return fail("shards is NULL");
+  if (!cols) return fail("cols is NULL");
+  if (!fresh) return fail("fresh is NULL");
+  if (cols[0] == -1) return fail("lsec_update_dev: cols is empty (1..k=%d changed data chunks)", k);
+  lsec::UpdateArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  unsigned long long seen = 0;
+  int c = 0;
+  for (; cols[c] != -1; ++c) {
+    if (c == k) return fail("lsec_update_dev: cols lists more than k=%d chunks", k);
+    const int id = cols[c];
+    if (id < 0) return fail("lsec_update_dev: cols[%d] = %d is negative (data chunk ids are 0..%d)", c, id, k - 1);
+    if (id >= k)
+      return fail("lsec_update_dev: cols[%d] = %d is not a data chunk (ids are 0..%d; %d..%d are parity)", c, id, k - 1, k, k + m - 1);
+    if (seen >> id & 1) return fail("lsec_update_dev: cols lists chunk %d twice (ids must be distinct)", id);
+    seen |= 1ull << id;
+    a.col[c] = static_cast<uint8_t>(id);
+  }
+  if (flags & ~LSEC_UPDATE_STORE) return fail("lsec_update_dev: flags %#x has bits other than LSEC_UPDATE_STORE", flags);
+  const auto aligned = [&](const char *what, int i, const lsec_shard_t &s) {
+    if (reinterpret_cast<uintptr_t>(s.base) % 8 != 0)
+      return fail("%s %d: base %p is not a multiple of 8 bytes (lsec_shard_t)", what, i, s.base);
+    if (nstripes > 1 && s.stride % 8 != 0)
+      return fail("%s %d: stride %lld is not a multiple of 8 bytes (lsec_shard_t)", what, i, s.stride);
+    return 0;
+  };
+  for (int i = 0; i < c; ++i)
+    if (aligned("shard", cols[i], sh[cols[i]]) || aligned("fresh", i, fresh[i])) return -1;
+  for (int r = 0; r < m; ++r)
+    if (aligned("shard", k + r, sh[k + r])) return -1;
+  if (check_geometry(p, C)) return -1;
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_cells(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("lsec_update_dev: the plan encodes %d parity rows, m=%d", R, m);
+  if (C == 0) return 0;
+  a.cells = static_cast<const CoefCell *>(cells);
+  a.K = k;
+  a.R = m;
+  a.c = c;
+  a.size = C;
+  a.packet = p->packet_size;
+  a.store = (flags & LSEC_UPDATE_STORE) ? 1 : 0;
+  // the encode's dwords per lane for this shape (0: its packet network, which the update has no form of)
+  const bool sliced = kind == KBITSLICED;
+  const int dw = sliced ? cauchy8_bitsliced_dw(k, m, C) : 0;
+  const long long per = launch_stripes(C, true);
+  for (long long s0 = 0; s0 < nstripes; s0 += per) {
+    a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
+    for (int i = 0; i < c; ++i) {
+      a.old[i] = shard_from(sh[cols[i]], s0);
+      a.fresh[i] = shard_from(fresh[i], s0);
+    }
+    for (int r = 0; r < m; ++r) a.par[r] = shard_from(sh[k + r], s0);
+    const hipError_t err = sliced ? lsec::launch_update_bitsliced(a, st, dw) : lsec::launch_update_bytewise(a, st);
+    if (err != hipSuccess) return fail("update kernel launch failed: %s", hipGetErrorString(err));
+  }
+  return 0;
+}
+
 }  // namespace eng
 
 using namespace eng;
@@ -1707,7 +1786,7 @@ int lsec_test_apply_path(void) { return tl_apply_path; }
 
 // Test hook, not in include/: the kernel forms (ec_kernels.h, LaunchForm) that the calling thread's last
 // lsec_check_dev, lsec_locate_dev, lsec_decode_dev_patterns, lsec_decode_dev_rotated,
-// lsec_check_dev_rotated or lsec_locate_dev_rotated launched, in order: a locate with repair its
+// lsec_check_dev_rotated, lsec_locate_dev_rotated or lsec_update_dev launched, in order: a locate with repair its
 // patterned decode too, a split call every launch; the finalize launch, which has one form, is not
 // among them.  forms: 8 ints each (family, bit-sliced, R, KC, IT, VW, BF, DW).  Returns the number
 // of launches; at most min(that, max_forms, 16) are written.
@@ -1722,7 +1801,7 @@ int lsec_test_launch_record(int *forms, int max_forms) {
 }
 
 // Test hook, not in include/ (no GPU): the form a launch of `family` (1 check, 2 locate, 3 rotated
-// check, 4 rotated locate, 5 patterned decode, 6 rotated repair) takes for a plan of kernel 1
+// check, 4 rotated locate, 5 patterned decode, 6 rotated repair, 7 parity update) takes for a plan of kernel 1
 // (bytewise) or 2 (bit-sliced) with K inputs and R rows (patterned: the table's largest erasure
 // count) at that packet and chunk size, as 8 ints.  It asks the functions the dispatch calls
 // (cauchy8_bitsliced_dw here, lsec::predict_launch for the rest).  0, or -1 with a message.
@@ -1750,7 +1829,7 @@ void lsec_test_set_cauchy8_policy(int mode) { g_c8_policy.store(mode == 1 ? 1 : 
 // A/B runs in one allocation.
 void lsec_test_set_tile_phase(int mode) { lsec::set_tile_phase(mode); }
 
-// Test hook, not in include/: a patterned call launches at most `stripes` stripes at a time
+// Test hook, not in include/: a patterned call (and lsec_update_dev) launches at most `stripes` stripes at a time
 // (0, the default: only the 32-bit tile limit splits), so a small batch exercises the split.
 void lsec_test_set_pattern_split(int stripes) { g_pattern_split.store(std::max(0, stripes), std::memory_order_relaxed); }
 

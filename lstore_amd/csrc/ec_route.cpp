@@ -636,6 +636,14 @@ int lsec_locate_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int ns
   return locate_dev(e, shards, nstripes, block_size, syndrome, hyp, located, counts, flags, static_cast<hipStream_t>(stream));
 }
 
+// (no check_shards: the rule covers the changed chunks, their fresh contents and the parity alone, in update_dev's ladder)
+int lsec_update_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size, const int *cols,
+                    const lsec_shard_t *fresh, int flags, void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  return update_dev(e, shards, nstripes, block_size, cols, fresh, flags, static_cast<hipStream_t>(stream));
+}
+
 int lsec_decode_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
                              const int *patterns, int npatterns, const unsigned char *stripe_pattern, void *stream) {
   PlanExt *e = ext_of(plan);

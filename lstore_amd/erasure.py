@@ -83,12 +83,14 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_set_kernel_variant", "lsec_set_host_devices", "lsec_hbm_copy_dev", "lsec_hbm_mix_dev", "lsec_prepare_encode", "lsec_plan_jit", "lsec_device_numa",
            "lsec_set_tile_sharing", "lsec_tile_sharing", "lsec_host_unpin_drain", "lsec_hbm_decode_shape_dev",
            "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev", "lsec_locate_dev",
-           "lsec_check_dev_rotated", "lsec_locate_dev_rotated")
+           "lsec_check_dev_rotated", "lsec_locate_dev_rotated", "lsec_update_dev")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
 # lsec_locate_dev: the two sentinels of located[] and the flag
 LOCATE_CLEAN, LOCATE_MANY, LOCATE_REPAIR = 0xFF, 0xFE, 1
+# lsec_update_dev: the flag
+UPDATE_STORE = 1
 STRIPE_OK, STRIPE_EMPTY, STRIPE_BAD_MAGIC, STRIPE_REPAIRED, STRIPE_LOST_MAGIC, STRIPE_LOST_MISMATCH = range(6)
 
 
@@ -149,6 +151,8 @@ def lib():
                                          C.c_void_p, C.c_void_p]
     L.lsec_locate_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.lsec_update_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.POINTER(ShardRef),
+                                  C.c_int, C.c_void_p]
     L.lsec_test_locate_ratio.argtypes = [P, C.c_int, C.c_int]
     L.lsec_test_set_pattern_split.argtypes = [C.c_int]
     L.lsec_test_set_pattern_split.restype = None
@@ -630,6 +634,29 @@ class Plan:
                                              dev_faults_ptr or None, LOCATE_REPAIR if repair else 0, stream),
                "lsec_locate_dev_rotated")
 
+    def update_dev_refs(self, refs, nstripes: int, block_size: int, cols, fresh_refs, store: bool = False,
+                        stream: int = 0) -> None:
+        """lsec_update_dev: parity update for a partial-stripe write.  cols: the changed data chunk ids;
+        fresh_refs[i]: the new content of chunk cols[i]; refs: the k+m logical chunks, of which only
+        refs[cols[i]] (the old contents) and the parity are used -- every other data entry may be (0, 0).
+        store: also write the fresh bytes over the old chunks.  refs / cols / fresh_refs None: NULL."""
+        _check(lib().lsec_update_dev(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                     None if cols is None else _erasure_array(cols),
+                                     None if fresh_refs is None else self.shard_refs(fresh_refs),
+                                     UPDATE_STORE if store else 0, stream), "lsec_update_dev")
+
+    def update_dev(self, data, parity, cols, fresh, store=False, stream=None) -> None:
+        """torch: bring parity [N,m,C] up to date for data [N,k,C] whose chunks `cols` change to fresh
+        [N,len(cols),C] (in the order of cols); data still holds the old bytes of those chunks, and with
+        store=True receives the fresh ones.  The other chunks of data are not read."""
+        refs, n, size = self.tensor_refs(data, parity)
+        cols = list(cols)
+        if fresh.dtype.itemsize != 1 or not fresh.is_cuda or fresh.dim() != 3 or fresh.shape[0] != n \
+                or fresh.shape[1] != len(cols) or fresh.shape[2] != size or fresh.stride(2) != 1:
+            raise ValueError("fresh must be a uint8 device tensor [N, len(cols), C] with contiguous rows")
+        fresh_refs = [(fresh.data_ptr() + i * fresh.stride(1), fresh.stride(0)) for i in range(len(cols))]
+        self.update_dev_refs(refs, n, size, cols, fresh_refs, store, _stream_handle(stream))
+
     def prepare_decode(self, erasures) -> None:
         _check(lib().lsec_prepare_decode(self._p, _erasure_array(erasures)), "lsec_prepare_decode")
 
@@ -708,9 +735,9 @@ def apply_path() -> int:
     return int(lib().lsec_test_apply_path())
 
 
-FORM_FAMILIES = ("chk", "loc", "chkrot", "locrot", "pat", "patrot")
+FORM_FAMILIES = ("chk", "loc", "chkrot", "locrot", "pat", "patrot", "upd")
 Form = collections.namedtuple("Form", "family sliced R KC IT VW BF DW")
-Form.__doc__ = """One separately compiled kernel of the check / locate / patterned / rotated calls: family (one of
+Form.__doc__ = """One separately compiled kernel of the check / locate / patterned / rotated / update calls: family (one of
 FORM_FAMILIES), sliced (plan kernel 2), R rows; bytewise: KC (0 = K at run time), IT steps of VW dwords
 per lane, BF branch-free; bit-sliced: DW dwords per lane (the others 0)."""
 
@@ -721,7 +748,7 @@ def _form(v) -> Form:
 
 def launch_record() -> list:
     """Test hook: the Forms this thread's last check_dev / locate_dev / decode_dev_patterns / decode_dev_rotated
-    / check_dev_rotated / locate_dev_rotated call launched, in order (a locate with repair: its patterned
+    / check_dev_rotated / locate_dev_rotated / update_dev call launched, in order (a locate with repair: its patterned
     decode too; a split call: every launch)."""
     buf = (C.c_int * (8 * 16))()
     n = lib().lsec_test_launch_record(buf, 16)
@@ -757,7 +784,7 @@ def fixed_k() -> tuple:
 
 
 def set_pattern_split(stripes: int = 0) -> None:
-    """Test hook: a patterned decode launches at most `stripes` stripes at a time (0: no extra split)."""
+    """Test hook: a patterned decode (and update_dev) launches at most `stripes` stripes at a time (0: no extra split)."""
     lib().lsec_test_set_pattern_split(int(stripes))
 
 

@@ -14,6 +14,9 @@ lsec_check_dev against lsec_encode_dev and against encode-and-compare, on the sa
 python tools/kbench.py --locate [--rounds R] [--reps N]
 lsec_locate_dev against lsec_check_dev on the same shapes, clean, corrupt and repairing: see locate_bench.
 
+python tools/kbench.py --update [--rounds R] [--reps N] [--pattern-codes rs63,rs164,cg63]
+lsec_update_dev against a device copy of the fresh chunk followed by lsec_encode_dev: see update_bench.
+
 python tools/kbench.py --rotated-scrub [--rounds R] [--reps N]
 lsec_check_dev_rotated / lsec_locate_dev_rotated over the devices of a rotated LUN against the unrotated
 calls over the same bytes: see rotated_scrub_bench.
@@ -463,6 +466,89 @@ def rotated_scrub_bench(a):
         torch.cuda.empty_cache()
 
 
+def update_bench(a):
+    """The partial-stripe write four ways, interleaved round by round on the same k+m buffers (one per
+    chunk, C = 1 MiB) and two buffers of fresh bytes:
+      (a) a device copy of the fresh chunk over data chunk 0,  what a device caller does without the call: c + k
+          then lsec_encode_dev                                 chunk reads and c + m chunk writes
+      (b) lsec_update_dev, LSEC_UPDATE_STORE, cols = {0}       2c + m reads, m + c writes
+      (c) lsec_update_dev without the flag, cols = {0}         2c + m reads, m writes
+      (d) lsec_update_dev, LSEC_UPDATE_STORE, cols = {0, k-1}  c = 2
+    (a)'s own min-max over the rounds is the margin (b) is judged by.  Every case is checked before timing: the
+    parity after (b), (c) and (d) is lsec_encode_dev's for the data with the chunks replaced."""
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    C, N = 1 << 20, a.pattern_stripes
+    for name in a.pattern_codes.split(","):
+        meth, k, m = CONFIGS[name][:3]
+        n = k + m
+        plan = L.Plan.for_chunk(meth, k, m, C)
+        bufs = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(n)]
+        fresh = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(2)]
+        refs = [(b.data_ptr(), C) for b in bufs]
+        fresh_refs = [(f.data_ptr(), C) for f in fresh]
+        # the untouched data chunks are not handed to the update at all
+        only = lambda cols: [refs[i] if i in cols or i >= k else (0, 0) for i in range(n)]
+        one, two = only((0,)), only((0, k - 1))
+
+        def copy_encode():
+            bufs[0].copy_(fresh[0])
+            plan.encode_dev_refs(refs, N, C, sh)
+
+        runs = {"a": copy_encode,
+                "b": lambda: plan.update_dev_refs(one, N, C, [0], fresh_refs[:1], True, sh),
+                "c": lambda: plan.update_dev_refs(one, N, C, [0], fresh_refs[:1], False, sh),
+                "d": lambda: plan.update_dev_refs(two, N, C, [0, k - 1], fresh_refs, True, sh)}
+        # results first: each update against a re-encode of the data with the chunks replaced
+        want = [torch.empty((N, C), dtype=torch.uint8, device=dev) for _ in range(m)]
+        for key, cols in (("b", (0,)), ("c", (0,)), ("d", (0, k - 1))):
+            old = {j: bufs[j].clone() for j in cols}
+            plan.encode_dev_refs(refs, N, C, sh)  # consistent stripes
+            runs[key]()
+            torch.cuda.synchronize()
+            for i, j in enumerate(cols):
+                assert torch.equal(bufs[j], fresh[i] if key != "c" else old[j]), f"({key}) data chunk {j}"
+                bufs[j].copy_(fresh[i])
+            plan.encode_dev_refs(refs[:k] + [(w.data_ptr(), C) for w in want], N, C, sh)
+            torch.cuda.synchronize()
+            for r in range(m):
+                assert torch.equal(bufs[k + r], want[r]), f"({key}) parity row {r} differs from the re-encode"
+            for j in cols:
+                bufs[j].copy_(old[j])
+            del old
+        del want
+        torch.cuda.empty_cache()
+        times = {key: [] for key in runs}
+        for _ in range(a.rounds):
+            for key, fn in runs.items():
+                fn()  # warm
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.reps):
+                    fn()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[key].append(e0.elapsed_time(e1) / a.reps)
+        lo, hi = min(times["a"]), max(times["a"])
+        what = {"a": "copy + lsec_encode_dev", "b": "lsec_update_dev, store, c = 1", "c": "lsec_update_dev, c = 1",
+                "d": "lsec_update_dev, store, c = 2"}
+        chunks = {"a": 1 + k + 1 + m, "b": 2 + m + m + 1, "c": 2 + m + m, "d": 4 + m + m + 2}  # chunk transfers per stripe
+        med = {key: sorted(ts)[len(ts) // 2] for key, ts in times.items()}
+        for key, ts in times.items():
+            db = chunks[key] * C * N
+            band = "" if key != "b" else ("  inside (a)'s band" if lo <= med[key] <= hi else
+                                          f"  {'below' if med[key] < lo else 'above'} (a)'s band by "
+                                          f"{abs(med[key] - (lo if med[key] < lo else hi)) / med[key]:.2%}")
+            print(f"{name} N={N} C={C} ({key}) {what[key]:30s} median {med[key]:7.3f} ms  min {min(ts):7.3f}  max {max(ts):7.3f}  "
+                  f"{chunks[key]:2d} chunks {db / med[key] / 1e6:7.1f} GB/s ({db / med[key] / 8e9:5.1%} of 8 TB/s){band}", flush=True)
+        print(f"{name} (a) band: {lo:.3f} .. {hi:.3f} ms ({(hi - lo) / lo:.2%}) over {a.rounds} rounds of {a.reps} launches; "
+              f"(b)/(a) = {med['b'] / med['a']:.3f}, (c)/(b) = {med['c'] / med['b']:.3f}, (d)/(b) = {med['d'] / med['b']:.3f}", flush=True)
+        del bufs, fresh
+        plan.close()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data-gib", type=float, default=24.0)
@@ -491,7 +577,13 @@ def main():
     ap.add_argument("--rotated-scrub", action="store_true",
                     help="time lsec_check_dev_rotated / lsec_locate_dev_rotated against the unrotated calls "
                          "(rotated_scrub_bench; --pattern-stripes, --pattern-codes) and exit")
+    ap.add_argument("--update", action="store_true",
+                    help="time lsec_update_dev against a device copy + lsec_encode_dev (update_bench; "
+                         "--pattern-stripes, --pattern-codes) and exit")
     a = ap.parse_args()
+    if a.update:
+        update_bench(a)
+        return
     if a.rotated_scrub:
         rotated_scrub_bench(a)
         return
