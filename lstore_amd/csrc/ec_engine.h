@@ -1,9 +1,11 @@
 // ec_engine.h -- internal interface between the engine's host-side files (not part of the C ABI;
 // include/lstore_ec.h is).  The engine is split by route:
 //
-//   ec_plan.cpp           plan service: et_* plan entry points, matrices, device images, decode
-//                         entries, check_geometry, enqueue_apply (every kernel launch of a coding
-//                         job goes through it), the device-resident core
+//   ec_plan.cpp           plan service: et_* plan entry points, matrices, the per-device images
+//                         (DevImage: one cache type for the encode, ratio, decode-entry and
+//                         pattern-table images), the coding jobs (encode_job / decode_job: what a
+//                         call applies), check_geometry, enqueue_apply (every kernel launch of a
+//                         coding job goes through it), the device-resident core
 //   ec_route.cpp          the routing function (route_host) and its threshold table (RouteTable),
 //                         the batched / per-stripe entry points, the device set, the direct retry
 //   ec_stripe_server.cpp  route 1: the persistent stripe server (host side of ec_server.hip)
@@ -25,6 +27,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -65,13 +68,35 @@ enum KernelKind { KNONE = 0, KBYTEWISE = 1, KBITSLICED = 2, KBITMATRIX = 3, KWOR
 constexpr int kMaxDevs = LSEC_MAX_DEVS_WIDE;
 int max_devs(int method, int w);
 
+// One host image, uploaded at most once per device: device -> pointer.  Every per-device image of
+// a plan is one of these (PlanImpl::for_each_image), so et_destroy_plan frees them in one walk.  The
+// plan's mutex guards it.
+int upload(const void *host, size_t nbytes, const char *what, void **out);  // hipMalloc + hipMemcpy; `what` names the copy in the message
+class DevImage {
+ public:
+  const void *find(int dev) const {  // null before the device's first get()
+    const auto it = by_dev_.find(dev);
+    return it == by_dev_.end() ? nullptr : it->second;
+  }
+  // The image on `dev`, the current device: a miss uploads host[0, nbytes) and, if there is an
+  // on_first_upload, calls it once with the fresh pointer (it binds the image's network).
+  int get(int dev, const void *host, size_t nbytes, const char *what, const std::function<void(const void *)> &on_first_upload,
+          const void **out);
+  void drop(int dev);  // frees the image on `dev`, the current device (it was never handed out)
+  void release();      // every device's: unbound first if get() bound it, then hipSetDevice and hipFree
+  size_t count() const { return by_dev_.size(); }
+
+ private:
+  std::map<int, void *> by_dev_;
+  bool bound_ = false;
+};
+
 struct DecodeEntry {
   lsec::gf8::DecodePlan dp;
   bool xor_only = false;  // GF(2^8) rows of 0 / 1 only (XOR of survivors)
-  std::map<int, CoefCell *> dev_cells;  // device -> e x k cells
-  std::vector<uint32_t> masks;          // bitmatrix codes: (e*w) x k row masks; wordwise: e x k x w products
-  std::map<int, uint32_t *> dev_masks;
-  std::vector<uint32_t> wrows;          // wordwise: the e x k GF(2^w) decode rows (XOR networks)
+  std::vector<uint32_t> masks;  // bitmatrix codes: (e*w) x k row masks; wordwise: e x k x w products
+  std::vector<uint32_t> wrows;  // wordwise: the e x k GF(2^w) decode rows (XOR networks)
+  DevImage image;  // that u32 image for a u32 kind's entry that is not xor_only, else the e x k cells: never both
 };
 
 // The table of a per-stripe-pattern call shape (lsec_decode_dev_patterns / _rotated): one record
@@ -83,11 +108,11 @@ struct PatternTable {
   std::vector<lsec::PatRecord> recs;
   std::vector<CoefCell> cells;
   std::vector<char> reachable;  // rotated: 0 for a rotation (first_stripe + s) * n_shift mod n never takes
-  struct Dev {
-    lsec::PatRecord *recs = nullptr;
-    CoefCell *cells = nullptr;
+  DevImage dev_recs, dev_cells;  // both uploaded, per device: a device has both or neither
+  struct Dev {                   // the pair on one device, as enqueue_patterns takes it
+    const lsec::PatRecord *recs = nullptr;
+    const CoefCell *cells = nullptr;
   };
-  std::map<int, Dev> dev;  // device -> uploaded table
 };
 
 constexpr int kFastDevs = 16;  // devices whose encode image pointer is cached lock-free
@@ -109,14 +134,24 @@ struct PlanImpl {
   lsec::gf8::Mat coding;   // GF(2^8) matrix the kernels apply (m x k)
   lsec::gfw::Mat coding_w; // GF(2^16) / GF(2^32) matrix codes (m x k)
   bool coding_ready = false;
-  std::map<int, CoefCell *> enc_cells;                   // device -> m x k cells
   std::vector<uint32_t> enc_masks;                       // bitmatrix codes: (m*w) x k row masks;
                                                          // wordwise: m x k x w products
-  std::map<int, uint32_t *> enc_dev_masks;
+  DevImage enc_image;                                    // enc_masks for the u32 kinds, else the m x k cells of coding
   lsec::gf8::Mat ratio;                                  // lsec_locate_dev: Q[r-1][j] = g[r][j] / g[0][j], (m-1) x k
-  std::map<int, CoefCell *> ratio_cells;                 // device -> (m-1) x k cells of it
+  DevImage ratio_image;                                  // the (m-1) x k cells of it
   std::map<std::vector<int>, DecodeEntry> decode_cache;  // sorted erased ids -> entry
   std::map<std::vector<int>, PatternTable> pattern_cache;  // PatternTable::key -> table (kept until the plan is destroyed)
+  // every per-device image the plan owns (et_destroy_plan, lsec_test_plan_images): a new one is added here
+  template <typename F>
+  void for_each_image(F &&f) {
+    f(enc_image);
+    f(ratio_image);
+    for (auto &ent : decode_cache) f(ent.second.image);
+    for (auto &tab : pattern_cache) {
+      f(tab.second.dev_recs);
+      f(tab.second.dev_cells);
+    }
+  }
 };
 
 // The public struct must stay first: callers only ever see &PlanExt::pub, and
@@ -138,11 +173,38 @@ int fp_form_encoding(lio_erasure_plan_t *p);
 int fp_form_decoding(lio_erasure_plan_t *p);
 int ensure_coding(PlanExt *e);
 int encode_rows(const PlanExt *e);
-int encode_cells(PlanExt *e, const void **out);
 int parse_erasures(const lio_erasure_plan_t *p, const int *erasures, std::vector<int> &ids);
-int decode_entry(PlanExt *e, const std::vector<int> &ids, DecodeEntry **out, const void **cells);
-int decode_kind(const PlanExt *e, const DecodeEntry *ent);
 int check_geometry(const lio_erasure_plan_t *p, long long block_size);
+
+// What a call applies, derived once: out_ids[r] = row r of the image over in_ids, on the current device.
+struct CodingJob {
+  int kind = KNONE;             // the kernel that applies the image
+  const void *image = nullptr;  // on the current device, cached on the plan
+  int R = 0;                    // its output rows
+  std::vector<int> in_ids, out_ids;
+};
+int encode_job(PlanExt *e, CodingJob *job);  // in 0..k-1, out k..k+R-1 (R: m; 2 for r6, 1 for raid4)
+// `ids`: parse_erasures' list.  in: the survivors, out: the erased; kind: the plan's, or KBYTEWISE for a
+// field code's pattern that only XORs survivors (its 0 / 1 cells take the bytewise kernel's plain-XOR path)
+int decode_job(PlanExt *e, const std::vector<int> &ids, CodingJob *job);
+
+// Stripes per launch of chunks of C bytes, so that the indices of its tiles (of tile_bytes) stay
+// 32-bit; with `split`, lsec_test_set_pattern_split can lower it.  for_launches cuts a batch into
+// those ranges, fn(s0, n) -> 0 or -1 enqueues stripes [s0, s0 + n); shard_from gives a shard's ref
+// for the launch that starts at stripe s0.
+long long launch_stripes(long long C, bool split, long long tile_bytes = 4096);
+template <typename F>
+int for_launches(long long nstripes, long long per, F &&fn) {
+  for (long long s0 = 0; s0 < nstripes; s0 += per)
+    if (fn(s0, static_cast<int>(std::min(per, nstripes - s0)))) return -1;
+  return 0;
+}
+inline ShardRef shard_from(const lsec_shard_t &sh, long long s0) {
+  return {reinterpret_cast<uint64_t>(sh.base) + static_cast<uint64_t>(s0) * sh.stride, sh.stride};
+}
+inline ShardRef shard_from(const ShardRef &sh, long long s0) {
+  return {sh.base + static_cast<uint64_t>(s0) * sh.stride, sh.stride};
+}
 int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in, const ShardRef *out, int nstripes,
                   long long size, int packet, hipStream_t st, int w = 8);
 int encode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, hipStream_t st);

@@ -105,9 +105,12 @@ int kernel_kind(int method, int w) {
 bool uses_u32_image(int kind) { return kind == KBITMATRIX || kind == KWORDWISE || kind == KBITSLICEDW; }
 bool packet_kind(int kind) { return kind == KBITSLICED || kind == KBITMATRIX || kind == KBITSLICEDW; }
 
-int *to_int_array(const lsec::gfw::Mat &m) {
-  int *a = static_cast<int *>(malloc(sizeof(int) * m.size()));
-  for (size_t i = 0; i < m.size(); ++i) a[i] = static_cast<int>(m[i]);
+// a malloc'd int copy (the public struct's matrices are the caller's to free()) of a GF(2^8) or
+// GF(2^w) matrix, or of a bitmatrix
+template <typename V>
+int *to_int_array(const V &v) {
+  int *a = static_cast<int *>(malloc(sizeof(int) * v.size()));
+  for (size_t i = 0; i < v.size(); ++i) a[i] = static_cast<int>(v[i]);
   return a;
 }
 
@@ -153,18 +156,6 @@ void group_image(std::vector<T> &img, int rows, int K, int unit) {
     }
   }
   img.swap(out);
-}
-
-int *to_int_array(const lsec::gf8::Mat &m) {
-  int *a = static_cast<int *>(malloc(sizeof(int) * m.size()));
-  for (size_t i = 0; i < m.size(); ++i) a[i] = m[i];
-  return a;
-}
-
-int *to_int_array(const std::vector<int> &v) {
-  int *a = static_cast<int *>(malloc(sizeof(int) * v.size()));
-  std::memcpy(a, v.data(), sizeof(int) * v.size());
-  return a;
 }
 
 int **schedule_array(const std::vector<std::array<int, 5>> &ops) {
@@ -229,10 +220,6 @@ int form_matrices(lio_erasure_plan_t *p, bool with_schedule) {
           p->encode_bitmatrix = to_int_array(lsec::gfw::to_bitmatrix(k, m, w, wm));
         }
       }
-      if (with_schedule && !p->encode_schedule) {
-        std::vector<int> bm(p->encode_bitmatrix, p->encode_bitmatrix + static_cast<size_t>(k) * m * w * w);
-        p->encode_schedule = schedule_array(lsec::gf8::smart_schedule(k, m, w, bm));
-      }
       break;
     }
     case BLAUM_ROTH:
@@ -245,14 +232,15 @@ int form_matrices(lio_erasure_plan_t *p, bool with_schedule) {
         if (bm.empty()) return fail("cannot form %s bitmatrix for k=%d w=%d", JE_method[p->method], k, w);
         p->encode_bitmatrix = to_int_array(bm);
       }
-      if (with_schedule && !p->encode_schedule) {
-        std::vector<int> bm(p->encode_bitmatrix, p->encode_bitmatrix + static_cast<size_t>(k) * m * w * w);
-        p->encode_schedule = schedule_array(lsec::gf8::smart_schedule(k, m, w, bm));
-      }
       break;
     }
     default:
       return fail("invalid method %d", p->method);
+  }
+  const bool bitmatrix_code = p->method == CAUCHY_ORIG || p->method == CAUCHY_GOOD || liberation_family(p->method);
+  if (bitmatrix_code && with_schedule && !p->encode_schedule) {
+    std::vector<int> bm(p->encode_bitmatrix, p->encode_bitmatrix + static_cast<size_t>(k) * m * w * w);
+    p->encode_schedule = schedule_array(lsec::gf8::smart_schedule(k, m, w, bm));
   }
   if (e->impl->coding_ready) return 0;
   const int kind = kernel_kind(p->method, w);
@@ -320,16 +308,95 @@ void host_cells(const lsec::gf8::Mat &mat, int rows, int cols, std::vector<CoefC
   }
 }
 
-int upload_cells(const std::vector<CoefCell> &h, CoefCell **out) {
-  CoefCell *d = nullptr;
-  HIP_OK(hipMalloc(&d, sizeof(CoefCell) * h.size()));
-  hipError_t err = hipMemcpy(d, h.data(), sizeof(CoefCell) * h.size(), hipMemcpyHostToDevice);
+int upload(const void *host, size_t nbytes, const char *what, void **out) {
+  void *d = nullptr;
+  HIP_OK(hipMalloc(&d, nbytes));
+  hipError_t err = hipMemcpy(d, host, nbytes, hipMemcpyHostToDevice);
   if (err != hipSuccess) {
     (void)hipFree(d);
-    return fail("hipMemcpy(cells): %s", hipGetErrorString(err));
+    return fail("%s: %s", what, hipGetErrorString(err));
   }
   *out = d;
   return 0;
+}
+
+int DevImage::get(int dev, const void *host, size_t nbytes, const char *what,
+                  const std::function<void(const void *)> &on_first_upload, const void **out) {
+  auto it = by_dev_.find(dev);
+  if (it == by_dev_.end()) {
+    void *d = nullptr;
+    if (upload(host, nbytes, what, &d)) return -1;
+    it = by_dev_.emplace(dev, d).first;
+    if (on_first_upload) {
+      bound_ = true;
+      on_first_upload(d);
+    }
+  }
+  *out = it->second;
+  return 0;
+}
+
+void DevImage::drop(int dev) {
+  const auto it = by_dev_.find(dev);
+  if (it == by_dev_.end()) return;
+  if (bound_) lsec::jit::unbind(it->second);
+  (void)hipFree(it->second);
+  by_dev_.erase(it);
+}
+
+void DevImage::release() {
+  for (auto &kv : by_dev_) {
+    if (bound_) lsec::jit::unbind(kv.second);  // before the address can be handed out again
+    (void)hipSetDevice(kv.first);
+    (void)hipFree(kv.second);
+  }
+  by_dev_.clear();
+}
+
+// The network of an R x K image just uploaded to `d`, compiled in the background from what the kind's
+// generator reads: the GF(2^8) rows, the GF(2^w) rows or the row masks.
+void bind_network(int kind, const void *d, const uint8_t *gf8_rows, const uint32_t *gfw_rows, const uint32_t *masks, int R, int K,
+                  int w, int packet) {
+  if (kind == KBYTEWISE) {  // RS / r6 at w = 8, raid4: an XOR network for the wide codes
+    lsec::jit::bind(d, gf8_rows, R, K);
+  } else if (kind == KBITSLICED) {  // Cauchy w = 8: a packet network (A/B knob)
+    std::vector<uint32_t> c32(gf8_rows, gf8_rows + static_cast<size_t>(R) * K);
+    lsec::jit::bind_pkt_field(d, c32.data(), R, K, 8, packet);
+  } else if (kind == KWORDWISE) {  // RS / r6 at w = 16 / 32: a bit-sliced network
+    lsec::jit::bind_w(d, gfw_rows, R, K, w);
+  } else if (kind == KBITMATRIX) {  // liberation family: a packet network
+    lsec::jit::bind_pkt(d, masks, R, K, w, packet);
+  } else if (kind == KBITSLICEDW) {  // Cauchy at w = 16 / 32: the same
+    lsec::jit::bind_pkt_field(d, gfw_rows, R, K, w, packet);
+  }
+}
+
+// What an R x K image is built from.  `u32`: the host image `masks` as it is; else CoefCell[R][K] of gf8_rows.
+// binds: a fresh upload gets the kind's network (bind_network).
+struct CoefSource {
+  int kind;
+  bool u32, binds;
+  const lsec::gf8::Mat &gf8_rows;
+  const lsec::gfw::Mat &gfw_rows;
+  const std::vector<uint32_t> &masks;
+  int R, K;
+};
+
+// the image on device `dev`, the current one: built and uploaded at its first use there (the plan's mutex is held)
+int coef_image(const PlanExt *e, DevImage &img, int dev, const CoefSource &c, const void **out) {
+  if ((*out = img.find(dev))) return 0;
+  std::vector<CoefCell> h;
+  if (!c.u32) {
+    host_cells(c.gf8_rows, c.R, c.K, h);
+    group_image(h, c.R, c.K, 1);
+  }
+  std::function<void(const void *)> bind;
+  if (c.binds)
+    bind = [&](const void *d) {
+      bind_network(c.kind, d, c.gf8_rows.data(), c.gfw_rows.data(), c.masks.data(), c.R, c.K, e->pub.w, e->pub.packet_size);
+    };
+  return c.u32 ? img.get(dev, c.masks.data(), sizeof(uint32_t) * c.masks.size(), "hipMemcpy(masks)", bind, out)
+               : img.get(dev, h.data(), sizeof(CoefCell) * h.size(), "hipMemcpy(cells)", bind, out);
 }
 
 // output rows of the encode image (m; 2 for r6, 1 for raid4)
@@ -340,22 +407,9 @@ int encode_rows(const PlanExt *e) {
   return static_cast<int>(e->impl->coding.size()) / e->pub.data_strips;
 }
 
-int upload_masks(const std::vector<uint32_t> &h, uint32_t **out) {
-  uint32_t *d = nullptr;
-  HIP_OK(hipMalloc(&d, sizeof(uint32_t) * h.size()));
-  hipError_t err = hipMemcpy(d, h.data(), sizeof(uint32_t) * h.size(), hipMemcpyHostToDevice);
-  if (err != hipSuccess) {
-    (void)hipFree(d);
-    return fail("hipMemcpy(masks): %s", hipGetErrorString(err));
-  }
-  *out = d;
-  return 0;
-}
-
-int encode_cells_locked(PlanExt *e, int dev, const void **out);
-
-// encode image on the current device: CoefCell[m][k] (matrix codes) or row masks (bitmatrix)
-int encode_cells(PlanExt *e, const void **out) {
+// encode image on the current device: CoefCell[m][k] (matrix codes at w = 8, raid4), row masks
+// (bitmatrix) or word products (matrix codes at w = 16 / 32)
+int encode_image(PlanExt *e, const void **out) {
   if (ensure_coding(e)) return -1;
   int dev = 0;
   HIP_OK(hipGetDevice(&dev));
@@ -365,49 +419,23 @@ int encode_cells(PlanExt *e, const void **out) {
       return 0;
     }
   std::lock_guard<std::mutex> lk(e->impl->mu);
-  const int rc = encode_cells_locked(e, dev, out);
+  const int kind = kernel_kind(e->pub.method, e->pub.w);
+  const CoefSource src = {kind,           uses_u32_image(kind), true, e->impl->coding, e->impl->coding_w, e->impl->enc_masks,
+                          encode_rows(e), e->pub.data_strips};
+  const int rc = coef_image(e, e->impl->enc_image, dev, src, out);
   if (rc == 0 && dev >= 0 && dev < kFastDevs) e->impl->enc_fast[dev].store(*out, std::memory_order_release);
   return rc;
 }
 
-int encode_cells_locked(PlanExt *e, int dev, const void **out) {
-  if (uses_u32_image(kernel_kind(e->pub.method, e->pub.w))) {
-    auto it = e->impl->enc_dev_masks.find(dev);
-    if (it == e->impl->enc_dev_masks.end()) {
-      uint32_t *d = nullptr;
-      if (upload_masks(e->impl->enc_masks, &d)) return -1;
-      it = e->impl->enc_dev_masks.emplace(dev, d).first;
-      if (kernel_kind(e->pub.method, e->pub.w) == KWORDWISE)  // RS / r6 at w = 16 / 32: a bit-sliced network
-        lsec::jit::bind_w(d, e->impl->coding_w.data(), encode_rows(e), e->pub.data_strips, e->pub.w);
-      else if (kernel_kind(e->pub.method, e->pub.w) == KBITMATRIX)  // liberation family: a packet network
-        lsec::jit::bind_pkt(d, e->impl->enc_masks.data(), encode_rows(e), e->pub.data_strips, e->pub.w, e->pub.packet_size);
-      else if (kernel_kind(e->pub.method, e->pub.w) == KBITSLICEDW)  // Cauchy at w = 16 / 32: the same
-        lsec::jit::bind_pkt_field(d, e->impl->coding_w.data(), encode_rows(e), e->pub.data_strips, e->pub.w,
-                                  e->pub.packet_size);
-    }
-    *out = it->second;
-    return 0;
-  }
-  auto it = e->impl->enc_cells.find(dev);
-  if (it != e->impl->enc_cells.end()) {
-    *out = it->second;
-    return 0;
-  }
+int encode_job(PlanExt *e, CodingJob *job) {
+  if (encode_image(e, &job->image)) return -1;
   const int k = e->pub.data_strips;
-  const int rows = static_cast<int>(e->impl->coding.size()) / k;
-  std::vector<CoefCell> h;
-  host_cells(e->impl->coding, rows, k, h);
-  group_image(h, rows, k, 1);
-  CoefCell *d = nullptr;
-  if (upload_cells(h, &d)) return -1;
-  e->impl->enc_cells[dev] = d;
-  if (kernel_kind(e->pub.method, e->pub.w) == KBYTEWISE) {  // wide codes: an XOR network, compiled in the background
-    lsec::jit::bind(d, e->impl->coding.data(), rows, k);
-  } else if (kernel_kind(e->pub.method, e->pub.w) == KBITSLICED) {  // Cauchy w = 8: a packet network (A/B knob)
-    std::vector<uint32_t> c32(e->impl->coding.begin(), e->impl->coding.end());
-    lsec::jit::bind_pkt_field(d, c32.data(), rows, k, 8, e->pub.packet_size);
-  }
-  *out = d;
+  job->kind = kernel_kind(e->pub.method, e->pub.w);
+  job->R = encode_rows(e);
+  job->in_ids.resize(k);
+  job->out_ids.resize(job->R);
+  for (int j = 0; j < k; ++j) job->in_ids[j] = j;
+  for (int r = 0; r < job->R; ++r) job->out_ids[r] = k + r;
   return 0;
 }
 
@@ -511,57 +539,27 @@ int decode_host_locked(PlanExt *e, const std::vector<int> &ids, DecodeEntry **ou
 
 int decode_entry_locked(PlanExt *e, const std::vector<int> &ids, int dev, DecodeEntry **out, const void **cells) {
   const int kind = kernel_kind(e->pub.method, e->pub.w);
-  const bool bitm = uses_u32_image(kind);
-  DecodeEntry *host = nullptr;
-  if (decode_host_locked(e, ids, &host)) return -1;
-  DecodeEntry &ent = *host;
-  if (bitm && !ent.xor_only) {
-    auto dm = ent.dev_masks.find(dev);
-    if (dm == ent.dev_masks.end()) {
-      uint32_t *d = nullptr;
-      if (upload_masks(ent.masks, &d)) return -1;
-      dm = ent.dev_masks.emplace(dev, d).first;
-      if (kind == KWORDWISE)
-        lsec::jit::bind_w(d, ent.wrows.data(), static_cast<int>(ent.dp.erased.size()), e->pub.data_strips, e->pub.w);
-      else if (kind == KBITMATRIX)
-        lsec::jit::bind_pkt(d, ent.masks.data(), static_cast<int>(ent.dp.erased.size()), e->pub.data_strips, e->pub.w,
-                            e->pub.packet_size);
-      else if (kind == KBITSLICEDW)
-        lsec::jit::bind_pkt_field(d, ent.wrows.data(), static_cast<int>(ent.dp.erased.size()), e->pub.data_strips,
-                                  e->pub.w, e->pub.packet_size);
-    }
-    *out = &ent;
-    *cells = dm->second;
-    return 0;
-  }
-  auto dc = ent.dev_cells.find(dev);
-  if (dc == ent.dev_cells.end()) {
-    std::vector<CoefCell> h;
-    host_cells(ent.dp.rows, static_cast<int>(ent.dp.erased.size()), e->pub.data_strips, h);
-    group_image(h, static_cast<int>(ent.dp.erased.size()), e->pub.data_strips, 1);
-    CoefCell *d = nullptr;
-    if (upload_cells(h, &d)) return -1;
-    dc = ent.dev_cells.emplace(dev, d).first;
-    if (!ent.xor_only && kernel_kind(e->pub.method, e->pub.w) == KBYTEWISE) {
-      lsec::jit::bind(d, ent.dp.rows.data(), static_cast<int>(ent.dp.erased.size()), e->pub.data_strips);
-    } else if (!ent.xor_only && kernel_kind(e->pub.method, e->pub.w) == KBITSLICED) {
-      std::vector<uint32_t> c32(ent.dp.rows.begin(), ent.dp.rows.end());
-      lsec::jit::bind_pkt_field(d, c32.data(), static_cast<int>(ent.dp.erased.size()), e->pub.data_strips, 8,
-                                e->pub.packet_size);
-    }
-  }
-  *out = &ent;
-  *cells = dc->second;
-  return 0;
+  if (decode_host_locked(e, ids, out)) return -1;
+  DecodeEntry &ent = **out;
+  // a u32 kind's XOR-only entry takes cells (decode_job sends it to the bytewise kernel), and no entry that only XORs binds a network
+  const CoefSource src = {kind,      uses_u32_image(kind) && !ent.xor_only,      !ent.xor_only,     ent.dp.rows,
+                          ent.wrows, ent.masks, static_cast<int>(ent.dp.erased.size()), e->pub.data_strips};
+  return coef_image(e, ent.image, dev, src, cells);
 }
 
 // A decode that only XORs survivors (a lost data shard rebuilt from P0, whose Cauchy-good /
 // RS row is all ones) is layout- and field-agnostic, so Cauchy packets and GF(2^16) / GF(2^32)
 // words go through the bytewise kernel's plain-XOR path (0 / 1 cells) instead.
-int decode_kind(const PlanExt *e, const DecodeEntry *ent) {
+int decode_job(PlanExt *e, const std::vector<int> &ids, CodingJob *job) {
+  DecodeEntry *ent = nullptr;
+  if (decode_entry(e, ids, &ent, &job->image)) return -1;
   const int kind = kernel_kind(e->pub.method, e->pub.w);
   const bool field = kind == KBITSLICED || kind == KWORDWISE || kind == KBITSLICEDW;
-  return field && ent->xor_only ? KBYTEWISE : kind;
+  job->kind = field && ent->xor_only ? KBYTEWISE : kind;
+  job->R = static_cast<int>(ent->dp.erased.size());
+  job->in_ids = ent->dp.survivors;
+  job->out_ids = ent->dp.erased;
+  return 0;
 }
 
 int check_geometry(const lio_erasure_plan_t *p, long long block_size) {
@@ -597,13 +595,14 @@ int cauchy8_bitsliced_dw(int K, int R, long long size) {
   return 1;
 }
 
-// Stripes per launch of chunks of C bytes: batches split so that tile indices stay 32-bit.  With
-// `split`, lsec_test_set_pattern_split can lower it: the patterned calls, the repair behind a
-// locate, every launch of the rotated check and locate, and the parity update.
+// Stripes per launch of chunks of C bytes: batches split so that the indices of their tiles (of
+// tile_bytes: 4096, or the stripe-magic calls' 8192) stay 32-bit.  With `split`,
+// lsec_test_set_pattern_split can lower it: the patterned calls, the repair behind a locate, every
+// launch of the rotated check and locate, and the parity update.
 std::atomic<int> g_pattern_split{0};  // stripes per launch, 0 = the 32-bit tile limit only
 
-long long launch_stripes(long long C, bool split) {
-  long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / 4096 + 1));
+long long launch_stripes(long long C, bool split, long long tile_bytes) {
+  long long per = std::max(1LL, (1LL << 30) / std::max(1LL, C / tile_bytes + 1));
   const int hook = split ? g_pattern_split.load(std::memory_order_relaxed) : 0;
   if (hook > 0) per = std::min<long long>(per, hook);
   return per;
@@ -626,16 +625,16 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
     if (hipFunction_t fn = lsec::jit::ready(image, R, K)) {  // the matrix's compiled XOR network
       // w = 16 / 32 networks take whole tiles only: the tail columns go to the generic kernel
       const long long whole = kind == KWORDWISE ? size / lsec::jit::gfw_tile(w, R) * lsec::jit::gfw_tile(w, R) : size;
-      const long long per = launch_stripes(size, false);
       ShardRef bi[lsec::jit::kMaxCols], bo[lsec::jit::kMaxRows];
-      for (int s0 = 0; whole > 0 && s0 < nstripes; s0 += static_cast<int>(std::min<long long>(per, nstripes))) {
-        const int n = static_cast<int>(std::min<long long>(per, nstripes - s0));
-        for (int j = 0; j < K; ++j) bi[j] = {in[j].base + static_cast<uint64_t>(s0) * in[j].stride, in[j].stride};
-        for (int r = 0; r < R; ++r) bo[r] = {out[r].base + static_cast<uint64_t>(s0) * out[r].stride, out[r].stride};
-        const hipError_t err = lsec::jit::launch(fn, R, K, bi, bo, n, whole, st, kind == KWORDWISE ? w : 8);
-        if (err != hipSuccess) return fail("xor network launch failed: %s", hipGetErrorString(err));
-        tl_apply_path |= 1;
-      }
+      if (whole > 0 && for_launches(nstripes, launch_stripes(size, false), [&](long long s0, int n) {
+            for (int j = 0; j < K; ++j) bi[j] = shard_from(in[j], s0);
+            for (int r = 0; r < R; ++r) bo[r] = shard_from(out[r], s0);
+            const hipError_t err = lsec::jit::launch(fn, R, K, bi, bo, n, whole, st, kind == KWORDWISE ? w : 8);
+            if (err != hipSuccess) return fail("xor network launch failed: %s", hipGetErrorString(err));
+            tl_apply_path |= 1;
+            return 0;
+          }))
+        return -1;
       if (whole == size) return 0;
       for (int j = 0; j < K; ++j) tin[j] = {in[j].base + static_cast<uint64_t>(whole), in[j].stride};
       for (int r = 0; r < R; ++r) tout[r] = {out[r].base + static_cast<uint64_t>(whole), out[r].stride};
@@ -674,43 +673,43 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
       } else {
         a.cells = static_cast<const CoefCell *>(image) + at;
       }
-      a.nstripes = nstripes;
       a.size = size;
       a.packet = packet;
-      for (int j = 0; j < kg; ++j) a.in[j] = in[k0 + j];
-      for (int r = 0; r < a.R; ++r) a.out[r] = out[r0 + r];
-      const long long per = launch_stripes(size, false);
-      for (int s0 = 0; s0 < nstripes; s0 += static_cast<int>(std::min<long long>(per, nstripes))) {
-        lsec::ApplyArgs b = a;
-        b.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
-        for (int j = 0; j < kg; ++j) b.in[j].base = in[k0 + j].base + static_cast<uint64_t>(s0) * in[k0 + j].stride;
-        for (int r = 0; r < b.R; ++r) b.out[r].base = out[r0 + r].base + static_cast<uint64_t>(s0) * out[r0 + r].stride;
-        const hipError_t err = kind == KBYTEWISE    ? lsec::launch_bytewise(b, st)
-                               : kind == KBITMATRIX ? lsec::launch_bitmatrix(b, st)
-                               : kind == KWORDWISE  ? lsec::launch_wordwise(b, st)
-                               : kind == KBITSLICEDW ? lsec::launch_gfw_bitsliced(b, st)
-                                                    : lsec::launch_bitsliced(b, st, 0, c8_dw);
-        if (err != hipSuccess) return fail("kernel launch failed: %s", hipGetErrorString(err));
-        tl_apply_path |= 4;
-      }
+      if (for_launches(nstripes, launch_stripes(size, false), [&](long long s0, int n) {
+            a.nstripes = n;
+            for (int j = 0; j < kg; ++j) a.in[j] = shard_from(in[k0 + j], s0);
+            for (int r = 0; r < a.R; ++r) a.out[r] = shard_from(out[r0 + r], s0);
+            const hipError_t err = kind == KBYTEWISE     ? lsec::launch_bytewise(a, st)
+                                   : kind == KBITMATRIX  ? lsec::launch_bitmatrix(a, st)
+                                   : kind == KWORDWISE   ? lsec::launch_wordwise(a, st)
+                                   : kind == KBITSLICEDW ? lsec::launch_gfw_bitsliced(a, st)
+                                                         : lsec::launch_bitsliced(a, st, 0, c8_dw);
+            if (err != hipSuccess) return fail("kernel launch failed: %s", hipGetErrorString(err));
+            tl_apply_path |= 4;
+            return 0;
+          }))
+        return -1;
     }
   }
   return 0;
 }
 
 // ---------------------------------------------------------------- device-resident core
-int encode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, hipStream_t st) {
-  lio_erasure_plan_t *p = &e->pub;
-  if (check_geometry(p, C)) return -1;
-  if (nstripes <= 0 || C == 0) return 0;
-  const void *cells = nullptr;
-  if (encode_cells(e, &cells)) return -1;
-  const int k = p->data_strips;
-  const int R = encode_rows(e);  // m (2 for r6, 1 for raid4)
+// a job over device-resident shards: sh[id] for every id of the job
+int apply_job(const PlanExt *e, const CodingJob &job, const lsec_shard_t *sh, int nstripes, long long C, hipStream_t st) {
   ShardRef in[kMaxDevs], out[kMaxDevs];
-  for (int j = 0; j < k; ++j) in[j] = {reinterpret_cast<uint64_t>(sh[j].base), sh[j].stride};
-  for (int r = 0; r < R; ++r) out[r] = {reinterpret_cast<uint64_t>(sh[k + r].base), sh[k + r].stride};
-  return enqueue_apply(kernel_kind(p->method, p->w), cells, k, R, in, out, nstripes, C, p->packet_size, st, p->w);
+  const int K = static_cast<int>(job.in_ids.size());
+  for (int j = 0; j < K; ++j) in[j] = shard_from(sh[job.in_ids[j]], 0);
+  for (int r = 0; r < job.R; ++r) out[r] = shard_from(sh[job.out_ids[r]], 0);
+  return enqueue_apply(job.kind, job.image, K, job.R, in, out, nstripes, C, e->pub.packet_size, st, e->pub.w);
+}
+
+int encode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, hipStream_t st) {
+  if (check_geometry(&e->pub, C)) return -1;
+  if (nstripes <= 0 || C == 0) return 0;
+  CodingJob job;
+  if (encode_job(e, &job)) return -1;
+  return apply_job(e, job, sh, nstripes, C, st);
 }
 
 // returns 0 (done or nothing to do) / -1
@@ -724,21 +723,9 @@ int decode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
   if (check_geometry(p, C)) return -1;
   if (p->method == RAID4 && ids[0] >= p->data_strips) return 0;  // raid4.c:48 leaves lost parity alone
   if (nstripes <= 0 || C == 0) return 0;
-  DecodeEntry *ent = nullptr;
-  const void *cells = nullptr;
-  if (decode_entry(e, ids, &ent, &cells)) return -1;
-  const int k = p->data_strips;
-  ShardRef in[kMaxDevs], out[kMaxDevs];
-  for (int j = 0; j < k; ++j) {
-    const lsec_shard_t &s = sh[ent->dp.survivors[j]];
-    in[j] = {reinterpret_cast<uint64_t>(s.base), s.stride};
-  }
-  const int R = static_cast<int>(ent->dp.erased.size());
-  for (int r = 0; r < R; ++r) {
-    const lsec_shard_t &s = sh[ent->dp.erased[r]];
-    out[r] = {reinterpret_cast<uint64_t>(s.base), s.stride};
-  }
-  return enqueue_apply(decode_kind(e, ent), cells, k, R, in, out, nstripes, C, p->packet_size, st, p->w);
+  CodingJob job;
+  if (decode_job(e, ids, &job)) return -1;
+  return apply_job(e, job, sh, nstripes, C, st);
 }
 
 // ---------------------------------------------------------------- per-stripe erasure patterns
@@ -910,18 +897,6 @@ int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const in
 
 namespace {
 
-int upload_records(const std::vector<lsec::PatRecord> &h, lsec::PatRecord **out) {
-  lsec::PatRecord *d = nullptr;
-  HIP_OK(hipMalloc(&d, sizeof(lsec::PatRecord) * h.size()));
-  hipError_t err = hipMemcpy(d, h.data(), sizeof(lsec::PatRecord) * h.size(), hipMemcpyHostToDevice);
-  if (err != hipSuccess) {
-    (void)hipFree(d);
-    return fail("hipMemcpy(pattern records): %s", hipGetErrorString(err));
-  }
-  *out = d;
-  return 0;
-}
-
 // the call shape's table on the current device: cached on the plan, built and uploaded once
 int pattern_table_dev(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift,
                       const PatternTable **out_tab, PatternTable::Dev *out_dev) {
@@ -929,42 +904,34 @@ int pattern_table_dev(PlanExt *e, const int *patterns, int npatterns, const int 
   if (parse_pattern_lists(&e->pub, patterns, npatterns, lost, n_shift, pl)) return -1;  // every argument check, before any HIP call
   int dev = 0;
   HIP_OK(hipGetDevice(&dev));
+  const auto on_dev = [&](const PatternTable &tab) {  // both images or neither
+    *out_tab = &tab;
+    *out_dev = {static_cast<const lsec::PatRecord *>(tab.dev_recs.find(dev)), static_cast<const CoefCell *>(tab.dev_cells.find(dev))};
+    return out_dev->cells != nullptr;
+  };
   {
     std::lock_guard<std::mutex> lk(e->impl->mu);
-    auto it = e->impl->pattern_cache.find(pl.key);
-    if (it != e->impl->pattern_cache.end()) {
-      auto d = it->second.dev.find(dev);
-      if (d != it->second.dev.end()) {  // the repeated call: no matrix work, no upload
-        *out_tab = &it->second;
-        *out_dev = d->second;
-        return 0;
-      }
-    }
+    const auto it = e->impl->pattern_cache.find(pl.key);
+    if (it != e->impl->pattern_cache.end() && on_dev(it->second)) return 0;  // the repeated call: no matrix work, no upload
   }
   PatternTable fresh;
   if (fill_pattern_table(e, pl, fresh)) return -1;  // (takes the plan's mutex per pattern)
   std::lock_guard<std::mutex> lk(e->impl->mu);
   // (map nodes never move and live until the plan is destroyed, as decode_cache's)
   PatternTable &tab = e->impl->pattern_cache.emplace(fresh.key, std::move(fresh)).first->second;
-  auto d = tab.dev.find(dev);
-  if (d == tab.dev.end()) {
-    PatternTable::Dev nd;
-    if (upload_records(tab.recs, &nd.recs)) return -1;
-    if (upload_cells(tab.cells, &nd.cells)) {
-      (void)hipFree(nd.recs);
-      return -1;
-    }
-    d = tab.dev.emplace(dev, nd).first;
+  if (on_dev(tab)) return 0;
+  const void *recs = nullptr, *cells = nullptr;
+  if (tab.dev_recs.get(dev, tab.recs.data(), sizeof(lsec::PatRecord) * tab.recs.size(), "hipMemcpy(pattern records)", nullptr, &recs))
+    return -1;
+  if (tab.dev_cells.get(dev, tab.cells.data(), sizeof(CoefCell) * tab.cells.size(), "hipMemcpy(cells)", nullptr, &cells)) {
+    tab.dev_recs.drop(dev);
+    return -1;
   }
-  *out_tab = &tab;
-  *out_dev = d->second;
+  on_dev(tab);
   return 0;
 }
 
-// a shard's ref for the launch that starts at stripe s0, and that launch's first rotation
-ShardRef shard_from(const lsec_shard_t &sh, long long s0) {
-  return {reinterpret_cast<uint64_t>(sh.base) + static_cast<uint64_t>(s0) * sh.stride, sh.stride};
-}
+// the first rotation of the launch that starts at stripe s0
 uint32_t rot0_from(uint32_t rot0, uint32_t rot_step, int n, long long s0) {
   return static_cast<uint32_t>((rot0 + (s0 % n) * rot_step) % n);
 }
@@ -993,9 +960,8 @@ int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::De
   a.rot_n = rotates ? static_cast<uint32_t>(n) : 0;
   // a Cauchy plan's patterns all take the bit-sliced kernel, 0 / 1 rows too (the same bytes in either layout)
   const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
-  const long long per = launch_stripes(C, true);
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
+  return for_launches(nstripes, launch_stripes(C, true), [&](long long s0, int ns) {
+    a.nstripes = ns;
     for (int i = 0; i < n; ++i) a.sh[i] = shard_from(sh[i], s0);
     a.stripe_pattern = stripe_pattern ? stripe_pattern + s0 : nullptr;
     a.rot0 = rotates ? rot0_from(rot0, rot_step, n, s0) : 0;
@@ -1006,8 +972,8 @@ int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::De
       const hipError_t err = sliced ? lsec::launch_pattern_bitsliced(a, tab.rmax, st) : lsec::launch_pattern_bytewise(a, tab.rmax, st);
       if (err != hipSuccess) return fail("pattern kernel launch failed: %s", hipGetErrorString(err));
     }
-  }
-  return 0;
+    return 0;
+  });
 }
 
 }  // namespace
@@ -1095,15 +1061,11 @@ int ratio_cells_dev(PlanExt *e, const CoefCell **out) {
   int dev = 0;
   HIP_OK(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(e->impl->mu);
-  auto it = e->impl->ratio_cells.find(dev);
-  if (it == e->impl->ratio_cells.end()) {
-    std::vector<CoefCell> h;
-    host_cells(*q, e->pub.parity_strips - 1, e->pub.data_strips, h);
-    CoefCell *d = nullptr;
-    if (upload_cells(h, &d)) return -1;
-    it = e->impl->ratio_cells.emplace(dev, d).first;
-  }
-  *out = it->second;
+  static const std::vector<uint32_t> none;
+  const CoefSource src = {KNONE, false, false, *q, none, none, e->pub.parity_strips - 1, e->pub.data_strips};  // (k <= kMaxK: one group)
+  const void *d = nullptr;
+  if (coef_image(e, e->impl->ratio_image, dev, src, &d)) return -1;
+  *out = static_cast<const CoefCell *>(d);
   return 0;
 }
 
@@ -1123,10 +1085,10 @@ struct ScrubCall {
 
 // the fields of an argument struct that change from launch to launch, for the one that starts at stripe s0
 template <typename Args>
-void scrub_launch_fields(Args &a, const ScrubCall &c, const lsec_shard_t *sh, unsigned *syndrome, long long s0, long long per,
-                         int nstripes, uint32_t rot0) {
+void scrub_launch_fields(Args &a, const ScrubCall &c, const lsec_shard_t *sh, unsigned *syndrome, long long s0, int nstripes,
+                         uint32_t rot0) {
   const int n = a.K + a.R;
-  a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
+  a.nstripes = nstripes;
   a.syndrome = syndrome + s0;
   if constexpr (lsec::kLocArgs<Args>) a.hyp = c.hyp + s0;
   if constexpr (lsec::kRotArgs<Args>) {
@@ -1159,14 +1121,13 @@ int enqueue_scrub(const ScrubCall &c, const lio_erasure_plan_t *p, const void *c
   // the encode's dwords per lane for this shape (0: its packet network, which the check has no form of)
   const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
   const int dw = sliced ? cauchy8_bitsliced_dw(a.K, a.R, C) : 0;
-  const long long per = launch_stripes(C, c.rotated);
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    scrub_launch_fields(a, c, sh, syndrome, s0, per, nstripes, rot0);
+  return for_launches(nstripes, launch_stripes(C, c.rotated), [&](long long s0, int ns) {
+    scrub_launch_fields(a, c, sh, syndrome, s0, ns, rot0);
     const hipError_t err = sliced ? lsec::launch_scrub_bitsliced(a, st, dw) : lsec::launch_scrub_bytewise(a, st);
     if (err != hipSuccess)
       return fail("%s%s kernel launch failed: %s", c.rotated ? "rotated " : "", c.locates ? "locate" : "check", hipGetErrorString(err));
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // Every limit's message names the limit; nothing is enqueued when one is passed.
@@ -1225,7 +1186,7 @@ int scrub_dev(PlanExt *e, const ScrubCall &c, const lsec_shard_t *sh, int nstrip
   }
   if (nstripes == 0) return 0;
   const void *cells = nullptr;
-  if (encode_cells(e, &cells)) return -1;
+  if (encode_image(e, &cells)) return -1;
   const int R = encode_rows(e);
   if (R != m) return fail("%s: the plan encodes %d parity rows, m=%d", c.name, R, m);
   const CoefCell *ratio = nullptr;
@@ -1330,7 +1291,7 @@ int update_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
   if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
   if (nstripes == 0) return 0;
   const void *cells = nullptr;
-  if (encode_cells(e, &cells)) return -1;
+  if (encode_image(e, &cells)) return -1;
   const int R = encode_rows(e);
   if (R != m) return fail("lsec_update_dev: the plan encodes %d parity rows, m=%d", R, m);
   if (C == 0) return 0;
@@ -1344,9 +1305,8 @@ int update_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
   // the encode's dwords per lane for this shape (0: its packet network, which the update has no form of)
   const bool sliced = kind == KBITSLICED;
   const int dw = sliced ? cauchy8_bitsliced_dw(k, m, C) : 0;
-  const long long per = launch_stripes(C, true);
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    a.nstripes = static_cast<int>(std::min<long long>(per, nstripes - s0));
+  return for_launches(nstripes, launch_stripes(C, true), [&](long long s0, int ns) {
+    a.nstripes = ns;
     for (int i = 0; i < c; ++i) {
       a.old[i] = shard_from(sh[cols[i]], s0);
       a.fresh[i] = shard_from(fresh[i], s0);
@@ -1354,8 +1314,8 @@ int update_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
     for (int r = 0; r < m; ++r) a.par[r] = shard_from(sh[k + r], s0);
     const hipError_t err = sliced ? lsec::launch_update_bitsliced(a, st, dw) : lsec::launch_update_bytewise(a, st);
     if (err != hipSuccess) return fail("update kernel launch failed: %s", hipGetErrorString(err));
-  }
-  return 0;
+    return 0;
+  });
 }
 
 }  // namespace eng
@@ -1470,38 +1430,7 @@ void et_destroy_plan(lio_erasure_plan_t *p) {
   if (e) {
     int cur = -1;
     (void)hipGetDevice(&cur);
-    for (auto &kv : e->impl->enc_cells) {
-      lsec::jit::unbind(kv.second);  // before the address can be handed out again
-      (void)hipSetDevice(kv.first);
-      (void)hipFree(kv.second);
-    }
-    for (auto &kv : e->impl->enc_dev_masks) {
-      lsec::jit::unbind(kv.second);
-      (void)hipSetDevice(kv.first);
-      (void)hipFree(kv.second);
-    }
-    for (auto &kv : e->impl->ratio_cells) {
-      (void)hipSetDevice(kv.first);
-      (void)hipFree(kv.second);
-    }
-    for (auto &ent : e->impl->decode_cache) {
-      for (auto &kv : ent.second.dev_cells) {
-        lsec::jit::unbind(kv.second);
-        (void)hipSetDevice(kv.first);
-        (void)hipFree(kv.second);
-      }
-      for (auto &kv : ent.second.dev_masks) {
-        lsec::jit::unbind(kv.second);
-        (void)hipSetDevice(kv.first);
-        (void)hipFree(kv.second);
-      }
-    }
-    for (auto &tab : e->impl->pattern_cache)
-      for (auto &kv : tab.second.dev) {
-        (void)hipSetDevice(kv.first);
-        (void)hipFree(kv.second.recs);
-        (void)hipFree(kv.second.cells);
-      }
+    e->impl->for_each_image([](DevImage &img) { img.release(); });
     if (cur >= 0) (void)hipSetDevice(cur);
     delete e->impl;
     e->magic = 0;
@@ -1721,19 +1650,18 @@ int lsec_prepare_decode(lio_erasure_plan_t *plan, const int *erasures) {
   std::vector<int> ids;
   const int pr = parse_erasures(plan, erasures, ids);
   if (pr != 0) return pr < 0 ? -1 : 0;
-  DecodeEntry *ent = nullptr;
-  const void *cells = nullptr;
-  if (decode_entry(e, ids, &ent, &cells)) return -1;
-  (void)lsec::jit::wait(cells, 30000);  // a wide code's XOR network, if it has one
+  CodingJob job;
+  if (decode_job(e, ids, &job)) return -1;
+  (void)lsec::jit::wait(job.image, 30000);  // a wide code's XOR network, if it has one
   return 0;
 }
 
 int lsec_prepare_encode(lio_erasure_plan_t *plan) {
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
-  const void *cells = nullptr;
-  if (encode_cells(e, &cells)) return -1;
-  (void)lsec::jit::wait(cells, 30000);
+  CodingJob job;
+  if (encode_job(e, &job)) return -1;
+  (void)lsec::jit::wait(job.image, 30000);
   return 0;
 }
 
@@ -1746,20 +1674,12 @@ int lsec_plan_jit(lio_erasure_plan_t *plan, const int *erasures) {
                             ? lsec::bitsliced_variant() != 0
                             : true)
     return 0;
-  const void *cells = nullptr;
-  int R = 0;
-  if (!erasures) {
-    if (encode_cells(e, &cells)) return 0;
-    R = encode_rows(e);
-  } else {
-    std::vector<int> ids;
-    DecodeEntry *ent = nullptr;
-    if (parse_erasures(plan, erasures, ids) != 0 || decode_entry(e, ids, &ent, &cells)) return 0;
-    R = static_cast<int>(ent->dp.erased.size());
-  }
+  CodingJob job;
+  std::vector<int> ids;
+  if (erasures ? parse_erasures(plan, erasures, ids) != 0 || decode_job(e, ids, &job) : encode_job(e, &job)) return 0;
   // Cauchy w = 8 shapes the bit-sliced kernel serves (at the plan's chunk size) run no network
-  if (kind == KBITSLICED && plan->w == 8 && cauchy8_bitsliced_dw(plan->data_strips, R, plan->strip_size) > 0) return 0;
-  return lsec::jit::ready(cells, R, plan->data_strips) != nullptr ? 1 : 0;
+  if (kind == KBITSLICED && plan->w == 8 && cauchy8_bitsliced_dw(plan->data_strips, job.R, plan->strip_size) > 0) return 0;
+  return lsec::jit::ready(job.image, job.R, plan->data_strips) != nullptr ? 1 : 0;
 }
 
 int lsec_plan_kernel(lio_erasure_plan_t *plan) { return plan ? kernel_kind(plan->method, plan->w) : 0; }
@@ -1877,6 +1797,17 @@ int lsec_test_locate_ratio(lio_erasure_plan_t *plan, int r, int j) {
   if (r < 0 || r >= plan->parity_strips - 1 || j < 0 || j >= plan->data_strips)
     return fail("lsec_test_locate_ratio: [%d][%d] outside %d x %d", r, j, plan->parity_strips - 1, plan->data_strips);
   return (*q)[static_cast<size_t>(r) * plan->data_strips + j];
+}
+
+// Test hook, not in include/: the device allocations the plan owns now, summed over every DevImage
+// (an image counts once per device it was uploaded to), or -1 with a message.
+int lsec_test_plan_images(lio_erasure_plan_t *plan) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  size_t n = 0;
+  e->impl->for_each_image([&](const DevImage &img) { n += img.count(); });
+  return static_cast<int>(n);
 }
 
 // Test hook, not in include/: the rotation of a rotated call's first stripe, as the call computes it

@@ -228,8 +228,8 @@ int run_direct(PlanExt *e, char **ptrs, long long C, const std::vector<int> &in_
 // device set.  Then a batch above the coalescing limit is cut into contiguous stripe ranges,
 // one per device, each driven by its own thread through that device's staging pipeline and
 // PCIe link -- SURVEY §8e's static partition inside one LStore process -- and smaller calls go
-// to the devices' dispatchers in turn.  Matrix images are per device (encode_cells /
-// decode_entry are called on the device that runs the range).
+// to the devices' dispatchers in turn.  Matrix images are per device (encode_job /
+// decode_job are called on the device that runs the range).
 std::mutex g_devs_mu;
 std::vector<int> g_host_devs;  // empty: the caller's current device
 
@@ -318,14 +318,10 @@ int encode_stripes_impl(PlanExt *e, char **ptrs, int nstripes, long long C) {
   }
   if (ensure_coding(e)) return -1;
   const int k = p->data_strips, km = k + p->parity_strips;
-  const int R = encode_rows(e);
-  std::vector<int> in_ids(k), out_ids(R);
-  for (int j = 0; j < k; ++j) in_ids[j] = j;
-  for (int r = 0; r < R; ++r) out_ids[r] = k + r;
-  return on_host_devices(nstripes, static_cast<size_t>(nstripes) * (k + R) * C, [&](int s0, int n) {
-    const void *cells = nullptr;
-    if (encode_cells(e, &cells)) return -1;
-    return route_host(e, ptrs + static_cast<size_t>(s0) * km, n, C, in_ids, out_ids, cells, kernel_kind(p->method, p->w));
+  return on_host_devices(nstripes, static_cast<size_t>(nstripes) * (k + encode_rows(e)) * C, [&](int s0, int n) {
+    CodingJob job;  // (the image is its device's)
+    if (encode_job(e, &job)) return -1;
+    return route_host(e, ptrs + static_cast<size_t>(s0) * km, n, C, job.in_ids, job.out_ids, job.image, job.kind);
   });
 }
 
@@ -352,11 +348,9 @@ int decode_stripes_impl(PlanExt *e, char **ptrs, int nstripes, long long C, cons
   }
   const int km = p->data_strips + p->parity_strips;
   return on_host_devices(nstripes, static_cast<size_t>(nstripes) * (p->data_strips + ids.size()) * C, [&](int s0, int n) {
-    DecodeEntry *ent = nullptr;
-    const void *cells = nullptr;
-    if (decode_entry(e, ids, &ent, &cells)) return -1;
-    return route_host(e, ptrs + static_cast<size_t>(s0) * km, n, C, ent->dp.survivors, ent->dp.erased, cells,
-                         decode_kind(e, ent));
+    CodingJob job;
+    if (decode_job(e, ids, &job)) return -1;
+    return route_host(e, ptrs + static_cast<size_t>(s0) * km, n, C, job.in_ids, job.out_ids, job.image, job.kind);
   });
 }
 
@@ -367,15 +361,11 @@ int encode_stripes_magic_impl(PlanExt *e, char **ptrs, int nstripes, long long C
   if (nstripes <= 0 || C == 0) return 0;
   if (ensure_coding(e)) return -1;
   const int k = p->data_strips, km = k + p->parity_strips;
-  const int R = encode_rows(e);
-  if (R != p->parity_strips) return fail("stripe magic needs m parity rows");
-  std::vector<int> in_ids(k), out_ids(R);
-  for (int j = 0; j < k; ++j) in_ids[j] = j;
-  for (int r = 0; r < R; ++r) out_ids[r] = k + r;
+  if (encode_rows(e) != p->parity_strips) return fail("stripe magic needs m parity rows");
   return on_host_devices(nstripes, static_cast<size_t>(nstripes) * km * C, [&](int s0, int n) {
-    const void *cells = nullptr;
-    if (encode_cells(e, &cells)) return -1;
-    return run_host(e, ptrs + static_cast<size_t>(s0) * km, n, C, in_ids, out_ids, cells, kernel_kind(p->method, p->w),
+    CodingJob job;
+    if (encode_job(e, &job)) return -1;
+    return run_host(e, ptrs + static_cast<size_t>(s0) * km, n, C, job.in_ids, job.out_ids, job.image, job.kind,
                     magic + 4 * static_cast<size_t>(s0));
   });
 }
@@ -408,15 +398,15 @@ int magic_dev_impl(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C
   ma.size = C;
   ma.col0 = 0;
   ma.chunk = C;
-  const int per = static_cast<int>(std::max(1LL, (1LL << 30) / std::max(1LL, C / 8192 + 1)));
   ShardRef msh[kMaxDevs];
-  for (int s0 = 0; s0 < nstripes; s0 += per) {
-    ma.nstripes = std::min(per, nstripes - s0);
-    ma.acc = acc + 2ull * s0;
-    for (int i = 0; i < km; ++i)
-      msh[i] = {reinterpret_cast<uint64_t>(sh[i].base) + static_cast<uint64_t>(s0) * sh[i].stride, sh[i].stride};
-    HIP_OK(launch_magic_groups(ma, msh, km, st));
-  }
+  if (for_launches(nstripes, launch_stripes(C, false, 8192), [&](long long s0, int n) {
+        ma.nstripes = n;
+        ma.acc = acc + 2ull * s0;
+        for (int i = 0; i < km; ++i) msh[i] = shard_from(sh[i], s0);
+        HIP_OK(launch_magic_groups(ma, msh, km, st));
+        return 0;
+      }))
+    return -1;
   HIP_OK(lsec::launch_magic_finalize(acc, nstripes, static_cast<int64_t>(km) * C, magic, st));
   HIP_OK(hipFreeAsync(acc, st));
   return 0;
@@ -434,24 +424,9 @@ int retry_direct(PlanExt *e, char **ptr, long long C, const std::vector<int> &id
     tl_err = first;  // device pointers (or mixed): nothing to retry with another transport
     return -1;
   }
-  int rc;
-  if (ids.empty()) {  // encode
-    const int k = p->data_strips;
-    const void *cells = nullptr;
-    rc = encode_cells(e, &cells);
-    if (rc == 0) {
-      const int R = encode_rows(e);
-      std::vector<int> in_ids(k), out_ids(R);
-      for (int j = 0; j < k; ++j) in_ids[j] = j;
-      for (int r = 0; r < R; ++r) out_ids[r] = k + r;
-      rc = run_direct(e, ptr, C, in_ids, out_ids, cells, kernel_kind(p->method, p->w));
-    }
-  } else {
-    DecodeEntry *ent = nullptr;
-    const void *cells = nullptr;
-    rc = decode_entry(e, ids, &ent, &cells);
-    if (rc == 0) rc = run_direct(e, ptr, C, ent->dp.survivors, ent->dp.erased, cells, decode_kind(e, ent));
-  }
+  CodingJob job;
+  int rc = ids.empty() ? encode_job(e, &job) : decode_job(e, ids, &job);  // (no erasures: the encode)
+  if (rc == 0) rc = run_direct(e, ptr, C, job.in_ids, job.out_ids, job.image, job.kind);
   if (rc == 0) {
     static std::atomic<bool> warned{false};
     if (!warned.exchange(true))
@@ -724,30 +699,28 @@ int lsec_encode_magic_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, 
   const bool fuse = kind == KBYTEWISE || kind == KBITSLICED;
   if (fuse && m <= 8 && k <= lsec::kMaxK && !check_geometry(plan, block_size) && k + m <= lsec::kMaxMagicShards) {
     if (nstripes <= 0 || block_size == 0) return 0;
-    const void *cells = nullptr;
-    if (encode_cells(e, &cells)) return -1;
-    if (encode_rows(e) != m) return fail("stripe magic needs m parity rows");
+    CodingJob job;
+    if (encode_job(e, &job)) return -1;
+    if (job.R != m) return fail("stripe magic needs m parity rows");
     unsigned long long *acc = nullptr;
     HIP_OK(hipMallocAsync(reinterpret_cast<void **>(&acc), 16ull * nstripes, st));
     HIP_OK(hipMemsetAsync(acc, 0, 16ull * nstripes, st));
     lsec::ApplyArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.cells = static_cast<const CoefCell *>(cells);
+    a.cells = static_cast<const CoefCell *>(job.image);
     a.K = k;
     a.R = m;
     a.size = block_size;
     a.packet = plan->packet_size;
-    const int per = static_cast<int>(std::max(1LL, (1LL << 30) / std::max(1LL, block_size / 8192 + 1)));
-    for (int s0 = 0; s0 < nstripes; s0 += per) {
-      a.nstripes = std::min(per, nstripes - s0);
-      a.magic_acc = acc + 2ull * s0;
-      for (int j = 0; j < k; ++j)
-        a.in[j] = {reinterpret_cast<uint64_t>(shards[j].base) + static_cast<uint64_t>(s0) * shards[j].stride, shards[j].stride};
-      for (int r = 0; r < m; ++r)
-        a.out[r] = {reinterpret_cast<uint64_t>(shards[k + r].base) + static_cast<uint64_t>(s0) * shards[k + r].stride,
-                    shards[k + r].stride};
-      HIP_OK(kind == KBITSLICED ? lsec::launch_bitsliced(a, st) : lsec::launch_bytewise_magic(a, st));
-    }
+    if (for_launches(nstripes, launch_stripes(block_size, false, 8192), [&](long long s0, int n) {
+          a.nstripes = n;
+          a.magic_acc = acc + 2ull * s0;
+          for (int j = 0; j < k; ++j) a.in[j] = shard_from(shards[j], s0);
+          for (int r = 0; r < m; ++r) a.out[r] = shard_from(shards[k + r], s0);
+          HIP_OK(kind == KBITSLICED ? lsec::launch_bitsliced(a, st) : lsec::launch_bytewise_magic(a, st));
+          return 0;
+        }))
+      return -1;
     HIP_OK(lsec::launch_magic_finalize(acc, nstripes, static_cast<int64_t>(k + m) * block_size,
                                        static_cast<uint8_t *>(magic), st));
     HIP_OK(hipFreeAsync(acc, st));

@@ -154,6 +154,7 @@ def lib():
     L.lsec_update_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.POINTER(ShardRef),
                                   C.c_int, C.c_void_p]
     L.lsec_test_locate_ratio.argtypes = [P, C.c_int, C.c_int]
+    L.lsec_test_plan_images.argtypes = [P]
     L.lsec_test_set_pattern_split.argtypes = [C.c_int]
     L.lsec_test_set_pattern_split.restype = None
     L.lsec_test_pattern_table.argtypes = [P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
@@ -823,3 +824,8 @@ def host_unpin_drain() -> None:
 def locate_ratio(plan: "Plan", r: int, j: int) -> int:
     """Test hook (no GPU): Q[r][j] = g[r+1][j] / g[0][j] of the host ratio image lsec_locate_dev uploads."""
     return _check_nonneg(lib().lsec_test_locate_ratio(plan.ptr, r, j), "lsec_test_locate_ratio")
+
+
+def plan_images(plan: "Plan") -> int:
+    """Test hook: the device allocations the plan owns now, over every per-device image (one per device it is on)."""
+    return _check_nonneg(lib().lsec_test_plan_images(plan.ptr), "lsec_test_plan_images")

@@ -38,6 +38,10 @@ long long lsec_test_pinned_budget(int ndev, long long budget_mb, long long slot_
 int lsec_test_lattices(const uint64_t *dst, const uint64_t *src, const uint64_t *bytes, int n, int64_t *out,
                        int out_cap);
 int lsec_test_jit_compile(int shape, int R, int K, int w, int packet, unsigned seed);
+int lsec_test_pattern_table(lio_erasure_plan_t *plan, const int *patterns, int npatterns, const int *lost, int n_shift,
+                            int pattern_id, int *nout, int *in_sel, int *out_sel, int *coef);
+int lsec_test_locate_ratio(lio_erasure_plan_t *plan, int r, int j);
+int lsec_test_plan_images(lio_erasure_plan_t *plan);
 
 static int g_checks, g_fails;
 static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;
@@ -188,6 +192,40 @@ static void cpu_part(void) {
                 strstr(lsec_last_error(), "dev_faults 0x"), "rotated locate dev_faults");
       et_destroy_plan(p);
     }
+  }
+  { /* a plan of each kernel kind through the host side of its images: matrices, a pattern table and the
+       locate's ratio by the no-device hooks (both refused, with a message, for the plans they do not serve).
+       No device is touched, so the plan owns no device image when it is destroyed. */
+    static const struct {
+      const char *name;
+      int method, k, m, w, packet, kernel;
+    } kinds[] = {{"RS w=8", REED_SOL_VAN, 6, 3, 8, 0, 1},        {"Cauchy w=8", CAUCHY_GOOD, 6, 3, 8, 64, 2},
+                 {"RS w=16", REED_SOL_VAN, 6, 3, 16, 0, 4},      {"Cauchy w=16", CAUCHY_GOOD, 4, 2, 16, 32, 5},
+                 {"liberation", LIBERATION, 5, 2, 5, 64, 3},     {"raid4", RAID4, 6, 1, 8, 0, 1}};
+    for (size_t i = 0; i < sizeof kinds / sizeof kinds[0]; ++i) {
+      const int k = kinds[i].k, m = kinds[i].m, method = kinds[i].method;
+      lio_erasure_plan_t *p = et_new_plan(method, 4096, k, m, kinds[i].w, kinds[i].packet, method == RAID4 ? 1 : 8);
+      CHECK(p != NULL, "plan %s", kinds[i].name);
+      if (!p) continue;
+      CHECK(p->form_encoding_matrix(p) == 0 && p->form_decoding_matrix(p) == 0, "%s: matrices", kinds[i].name);
+      CHECK(lsec_plan_kernel(p) == kinds[i].kernel, "%s: kernel %d", kinds[i].name, lsec_plan_kernel(p));
+      const int gf8 = kinds[i].kernel == 1 || kinds[i].kernel == 2;
+      const int patterns[] = {0, -1, 1, k, -1}, one[] = {2, -1, 0, -1};
+      int nout = 0, in_sel[8], out_sel[8], coef[64];
+      const int rc = lsec_test_pattern_table(p, m > 1 ? patterns : one, 2, NULL, 0, 1, &nout, in_sel, out_sel, coef);
+      if (gf8)
+        CHECK(rc == 0 && nout == (m > 1 ? 2 : 1), "%s: pattern table entry 1 (rc %d, %d rows)", kinds[i].name, rc, nout);
+      else
+        CHECK(rc == -1 && strstr(lsec_last_error(), "per-stripe patterns need"), "%s: pattern table refused", kinds[i].name);
+      const int q = lsec_test_locate_ratio(p, 0, 0);
+      if (gf8 && m > 1)
+        CHECK(q > 0, "%s: ratio[0][0] = %d", kinds[i].name, q);
+      else
+        CHECK(q == -1, "%s: ratio refused", kinds[i].name);
+      CHECK(lsec_test_plan_images(p) == 0, "%s: %d device images without a device call", kinds[i].name, lsec_test_plan_images(p));
+      et_destroy_plan(p);
+    }
+    CHECK(lsec_test_plan_images(NULL) == -1, "plan images of no plan");
   }
   if (getenv("LSEC_JITC")) { /* the network compiler's child and its queue, one shape per generator */
     CHECK(lsec_test_jit_compile(0, 6, 20, 8, 0, 7) == 0, "jit w=8");
