@@ -1,4 +1,4 @@
-"""CPU tests of the network generators (ec_jit.cpp): every generator shape -- w = 8 XOR networks,
+"""CPU tests of the network generators (ec_netgen.cpp): every generator shape -- w = 8 XOR networks,
 w = 16 / 32 bit-sliced networks in the one-wave form and the wave-pair split, and the packet
 networks of bitmatrix and Cauchy codes -- generated for pseudo-random matrices and compiled for
 gfx950 by hipRTC on the host (lsec_test_jit_compile; no GPU).  The GPU tests run the networks of

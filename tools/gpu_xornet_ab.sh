@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of w = 8 XOR-network (K1b) variants on wide RS codes, interleaved on one box, after the
 # parity cases.  Usage: tools/gpu_xornet_ab.sh <tag> <variant> [...]
-# (the first variant is the baseline; LSEC_JIT_VARIANT bits, see ec_jit.cpp); CFGS="config:lost ..." overrides
+# (the first variant is the baseline; LSEC_JIT_VARIANT bits, see struct Variant in ec_netgen.h); CFGS="config:lost ..." overrides
 # the codes timed; the parity cases run under the default variant
 set -o pipefail
 tag=$1; shift

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compile the XOR networks of a matrix code offline for every LSEC_JIT_VARIANT given and print
 the kernel resource usage (VGPRs, spills, occupancy) and the VALU instruction count of the
-tile loop.  Needs build/jit_src (tools/jit_src.cpp)."""
+tile loop.  Needs build/jit_src (make -C lstore_amd/csrc jit_src)."""
 import argparse
 import os
 import re
