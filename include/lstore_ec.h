@@ -332,7 +332,8 @@ int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
  * - Nothing is allocated and nothing is uploaded per call: the kernel indexes the plan's cached
  *   encode image by column.
  * - One column list per call: stripes that change in different chunks take separate calls.  There
- *   are no per-stripe lists and there is no form over the physical devices of a rotated LUN.
+ *   are no per-stripe lists.  The form over the physical devices of a rotated LUN is
+ *   lsec_update_dev_rotated, below.
  * - Every refusal -- plan kernels 3-5; k or m out of range; a NULL shards, cols or fresh; an empty
  *   list; an id < 0, an id >= k (a parity id) or a duplicate; more than k ids; unknown flag bits; a
  *   misaligned base, or a misaligned stride with nstripes > 1; a bad block_size; a negative
@@ -344,6 +345,64 @@ int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
 int lsec_update_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
                     long long block_size, const int *cols, const lsec_shard_t *fresh,
                     int flags, void *stream);
+
+/* Encode and parity update over the PHYSICAL devices of a rotated LUN, one pass each: the write
+ * side of lsec_check_dev_rotated / lsec_locate_dev_rotated / lsec_decode_dev_rotated, so that a
+ * caller that keeps device images on the GPU writes to them without splitting its stripes into
+ * classes that share a chunk-to-device map.  Purely additive too: the version stays 3, a caller
+ * detects the calls by their symbols.
+ *
+ * Both calls:
+ * - devs[i] (i < k+m) is physical device i, exactly as for lsec_check_dev_rotated.  With
+ *   rot_s = ((first_stripe + s) * n_shift) mod (k+m), logical chunk c of stripe s lives in
+ *   devs[(c - rot_s) mod (k+m)].  n_shift >= k+m is taken mod k+m; n_shift < 0 and
+ *   first_stripe < 0 return -1; first_stripe may be anything up to 2^63 - 1.
+ * - Plans: lsec_plan_kernel 1 (bytewise GF(2^8): RS, r6, raid4) and 2 (bit-sliced GF(2^8): Cauchy
+ *   at w = 8), k <= 64, 1 <= m <= 8.
+ * - Layout, alignment and block_size rules are those of lsec_encode_dev (lsec_shard_t, above; for
+ *   Cauchy block_size is a multiple of 8 * packet_size).  All k+m entries of devs are validated in
+ *   every call: under rotation every device holds data in some stripes and parity in others.
+ * - nstripes == 0 validates everything, returns 0 and touches no GPU; all bases may then be NULL,
+ *   cols may not.
+ * - Every refusal returns -1 with a message for lsec_last_error that names the limit, and nothing
+ *   is enqueued.  There is no fallback.
+ * - Nothing is allocated and nothing is uploaded per call: the kernels use the plan's cached
+ *   encode image.
+ * Enqueued on `stream`; return without synchronising.  0 / -1.
+ *
+ * lsec_encode_dev_rotated: for every stripe, reads the k logical data chunks from the devices that
+ * hold them and writes the m parity chunks to the devices that hold them.
+ * - The parity bytes are exactly what lsec_encode_dev writes for the logical view of the stripe;
+ *   n_shift == 0 behaves exactly as lsec_encode_dev over devs.
+ * - The data chunks are only read, and no byte outside the m parity chunks of each stripe is
+ *   written.
+ * - For Cauchy at w = 8 the bit-sliced table kernel runs even where lsec_encode_dev would run a
+ *   compiled packet network, as for the check; the bytes are identical.
+ *
+ * lsec_update_dev_rotated: lsec_update_dev with the old chunks and the parity on the devices.
+ * - `cols` is a -1 terminated list of c distinct LOGICAL data chunk ids, 1 <= c <= k, each in
+ *   0..k-1, in any order, as for lsec_update_dev.  fresh[i] is the new content of logical chunk
+ *   cols[i]: a logical buffer with its own base and stride, not rotated.
+ * - Effect, per stripe and byte column: the parity chunk of row r, wherever the rotation puts it,
+ *   takes ^= sum_i g[r][cols[i]] * (old_i ^ fresh_i), with old_i read from
+ *   devs[(cols[i] - rot_s) mod (k+m)].  Both numbered guarantees of lsec_update_dev carry over:
+ *   a consistent stripe comes out with the parity lsec_encode_dev_rotated writes for the data with
+ *   those chunks replaced, and any stripe keeps its syndrome under lsec_check_dev_rotated.
+ * - With LSEC_UPDATE_STORE fresh[i] also goes over the old chunk on its device, in the same pass,
+ *   from the registers that hold the fresh bytes.  Without it only parity is written.
+ * - The chunks that do not change are not read, although they live in devs.
+ * - fresh must not overlap devs.
+ * - Refused: everything lsec_update_dev refuses -- plan kernels 3-5; k or m out of range; a NULL
+ *   devs, cols or fresh; an empty list; an id < 0, an id >= k or a duplicate; more than k ids;
+ *   unknown flag bits; a misaligned base (on any of the k+m devices or of fresh), or a misaligned
+ *   stride with nstripes > 1; a bad block_size; a negative nstripes -- and a negative n_shift or
+ *   first_stripe. */
+int lsec_encode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                            long long block_size, int n_shift, long long first_stripe, void *stream);
+
+int lsec_update_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                            long long block_size, int n_shift, long long first_stripe,
+                            const int *cols, const lsec_shard_t *fresh, int flags, void *stream);
 
 /* Per-stripe "magic": the 4-byte little-endian zlib adler32 over the concatenation of a
  * stripe's k+m chunks that LStore's erasure segment stores in front of every chunk

@@ -225,6 +225,12 @@ int check_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long l
 int locate_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
                        unsigned *syndrome, unsigned long long *hyp, unsigned char *located, unsigned char *located_dev,
                        unsigned *counts, unsigned *dev_faults, int flags, hipStream_t st);
+// the write side over the same k+m physical devices: the parity rows stored where each stripe's rotation puts them, and
+// the parity update with old_i taken from the device that holds chunk cols[i] (fresh stays logical); all devs are used
+int encode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                       hipStream_t st);
+int update_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                       const int *cols, const lsec_shard_t *fresh, int flags, hipStream_t st);
 // stripes that do not share an erasure pattern, one launch per 32-bit range of tiles
 int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift, PatternTable &tab);
 uint32_t pattern_rot0(int n, int n_shift, long long first_stripe);

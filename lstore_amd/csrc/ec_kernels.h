@@ -235,8 +235,11 @@ struct LocateRotArgs : CheckRotArgs {
 // bodies alike: a locate struct adds ratio and hyp, a rotated one takes its refs from sh.
 template <typename Args>
 constexpr bool kLocArgs = std::is_same<Args, LocateArgs>::value || std::is_same<Args, LocateRotArgs>::value;
+struct EncodeRotArgs;
+struct UpdateRotArgs;
 template <typename Args>
-constexpr bool kRotArgs = std::is_base_of<CheckRotArgs, Args>::value;
+constexpr bool kRotArgs = std::is_base_of<CheckRotArgs, Args>::value || std::is_same<Args, EncodeRotArgs>::value ||
+                          std::is_same<Args, UpdateRotArgs>::value;
 
 // The accumulate launch of a check or locate, for each of CheckArgs, LocateArgs, CheckRotArgs and
 // LocateRotArgs.  R <= 8 (a locate: 2 <= R); the launch shape is the encode's for the same K x R
@@ -298,6 +301,60 @@ hipError_t launch_update_bytewise(const UpdateArgs &a, hipStream_t stream);
 // dw_pref: dwords per lane (1, 2, 4; 0 = 1), as launch_bitsliced
 hipError_t launch_update_bitsliced(const UpdateArgs &a, hipStream_t stream, int dw_pref = 0);
 
+// Encode and parity update over the physical devices of a rotated LUN (lsec_encode_dev_rotated /
+// lsec_update_dev_rotated): the write side of what CheckRotArgs reads.  The refs are the K + R
+// devices, and a tile finds logical chunk c of its stripe in sh[(c - rot_s) mod rot_n], rot_s from
+// rot0 / rot_step / rot_n exactly as the rotated check works it out (rot_back, ChkShards): scalar
+// arithmetic and dynamic-offset scalar loads from the kernel arguments.  Argument structs of their
+// own: every other struct keeps its layout.
+//
+// The encode forms the R parity rows of every stripe from the K logical data chunks, as the check
+// does, and stores them where the check would load and compare: to sh[(K + r - rot_s) mod rot_n].
+// The data chunks are only read.
+struct EncodeRotArgs {
+  const CoefCell *cells;  // the encode image, R x K, row-major (device memory)
+  int K, R;
+  int nstripes;
+  int packet;             // bit-sliced: packet size P (bytes)
+  int64_t size;           // bytes per shard (chunk C)
+  unsigned *tiles;        // as ApplyArgs
+  uint32_t tiles_pre;
+  uint32_t tile_phase;
+  uint32_t rot0, rot_step, rot_n;  // rot0, rot_step < rot_n = K + R
+  ShardRef sh[kRotMaxShards];      // the K + R physical devices
+};
+
+// UpdateArgs with old[] and par[] replaced by the devices: old_i is read from (and with `store`
+// written to) sh[(col[i] - rot_s) mod rot_n], parity row r is sh[(K + r - rot_s) mod rot_n].  fresh is
+// logical and not rotated.  The chunks that do not change have refs here -- under rotation every
+// device holds a changed chunk in some stripe -- but no kernel forms an address from them in a
+// stripe where they do not change.
+struct UpdateRotArgs {
+  const CoefCell *cells;  // as UpdateArgs, up to col
+  int K, R;
+  int c;
+  int nstripes;
+  int packet;
+  int store;
+  int64_t size;
+  unsigned *tiles;
+  uint32_t tiles_pre;
+  uint32_t tile_phase;
+  uint32_t rot0, rot_step, rot_n;  // rot0, rot_step < rot_n = K + R
+  alignas(4) uint8_t col[kMaxK];
+  ShardRef fresh[kMaxK];           // the new contents of the changed chunks (only read)
+  ShardRef sh[kRotMaxShards];      // the K + R physical devices
+};
+static_assert(sizeof(UpdateRotArgs) == 2312, "UpdateRotArgs: well under the 4 KiB of kernel arguments");
+static_assert(sizeof(EncodeRotArgs) == 1216, "EncodeRotArgs layout");
+
+// R <= 8.  The encode's launch shape is the rotated check's for the same K x R (chk_bytewise_form,
+// scrub_lane_dwords), the update's is the unrotated update's (upd_bytewise_form, update_lane_dwords).
+hipError_t launch_encode_rot_bytewise(const EncodeRotArgs &a, hipStream_t stream);
+hipError_t launch_encode_rot_bitsliced(const EncodeRotArgs &a, hipStream_t stream, int dw_pref = 0);
+hipError_t launch_update_rot_bytewise(const UpdateRotArgs &a, hipStream_t stream);
+hipError_t launch_update_rot_bitsliced(const UpdateRotArgs &a, hipStream_t stream, int dw_pref = 0);
+
 // Which kernel ran (test hooks lsec_test_launch_record / lsec_test_predict_forms, ec_plan.cpp).  The
 // check, locate, patterned, rotated and update calls are families of separately compiled kernels; a form
 // names one of them by its template arguments: bytewise R, KC (0: K at run time), IT, VW, BF; or
@@ -305,7 +362,7 @@ hipError_t launch_update_bitsliced(const UpdateArgs &a, hipStream_t stream, int 
 // functions record the form at the one place where the template arguments are known; the record
 // is the calling thread's, holds the launches since launch_record_reset() in order (the engine
 // resets it on entry to each of those calls) and costs a few host stores per launch.
-enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd };
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot };
 struct LaunchForm {
   int family, sliced, R, KC, IT, VW, BF, DW;
 };

@@ -562,6 +562,63 @@ hipError_t launch_update_bitsliced(const UpdateArgs &a, hipStream_t st, int dw_p
   return by_r(a.R, [&](auto r) { return dispatch_upd_bitsliced<decltype(r)::value>(a, st, grid, dw); });
 }
 
+// ------------------------------------------------------------------ encode and update over a rotated LUN
+namespace {
+bool update_rot_args_ok(const UpdateRotArgs &a) {
+  if (!(a.K >= 1 && a.K <= kMaxK && a.R >= 1 && a.R <= 8 && a.c >= 1 && a.c <= a.K && a.cells && a.size % 8 == 0)) return false;
+  if (!rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.K + a.R)) return false;
+  for (int i = 0; i < a.c; ++i)
+    if (a.col[i] >= a.K) return false;
+  return true;
+}
+
+bool encode_rot_args_ok(const EncodeRotArgs &a) {
+  return a.K >= 1 && a.K <= kMaxK && a.R >= 1 && a.R <= 8 && a.cells && a.size % 8 == 0 &&
+         rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.K + a.R);
+}
+
+// dwords per lane of a bit-sliced rotated encode (more than kEncRotWideRows rows: one)
+int encode_rot_lane_dwords(int R, int dw_pref, int packet) { return lane_dwords(R <= kEncRotWideRows ? dw_pref : 1, packet); }
+}  // namespace
+
+hipError_t launch_update_rot_bytewise(const UpdateRotArgs &a, hipStream_t st) {
+  if (!update_rot_args_ok(a)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const BwForm f = upd_bytewise_form(a.R);
+  const int grid = tile_grid(BwShape{f.it, f.vw, f.bf}.tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_updrot_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_update_rot_bitsliced(const UpdateRotArgs &a, hipStream_t st, int dw_pref) {
+  if (!update_rot_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int dw = update_lane_dwords(a.R, dw_pref, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_updrot_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+}
+
+hipError_t launch_encode_rot_bytewise(const EncodeRotArgs &a, hipStream_t st) {
+  if (!encode_rot_args_ok(a)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const BwForm f = chk_bytewise_form(a.K, a.R);
+  const int grid = tile_grid(BwShape{f.it, f.vw, f.bf}.tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_encrot_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_encode_rot_bitsliced(const EncodeRotArgs &a, hipStream_t st, int dw_pref) {
+  if (!encode_rot_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int dw = encode_rot_lane_dwords(a.R, dw_pref, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_encrot_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+}
+
 // ------------------------------------------------------------------ which kernel ran (test hooks)
 namespace {
 thread_local LaunchForm tl_forms[kLaunchRecordMax];
@@ -583,12 +640,16 @@ int launch_record(LaunchForm *out, int max) {
 bool predict_launch(int family, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out) {
   const bool pat = family == kFormPat || family == kFormPatRot;
   const bool loc = family == kFormLoc || family == kFormLocRot;
-  const bool upd = family == kFormUpd;
-  if (family < kFormChk || family > kFormUpd || K < 1 || K > kMaxK || R < 1 || R > (pat ? kPatMaxOut : 8)) return false;
+  const bool upd = family == kFormUpd || family == kFormUpdRot;  // (the rotated update takes the update's forms,
+  const bool enc = family == kFormEncRot;                        //  the rotated encode the check's bytewise ones)
+  if (family < kFormChk || family > kFormUpdRot || K < 1 || K > kMaxK || R < 1 || R > (pat ? kPatMaxOut : 8)) return false;
   if ((loc && R < 2) || (family == kFormPatRot && R != 1)) return false;
   if (sliced) {
     if (packet <= 0 || packet % 4 != 0) return false;
-    const int dw = pat ? 1 : upd ? update_lane_dwords(R, dw_pref, packet) : scrub_lane_dwords(loc, R, dw_pref, packet);
+    const int dw = pat   ? 1
+                   : upd ? update_lane_dwords(R, dw_pref, packet)
+                   : enc ? encode_rot_lane_dwords(R, dw_pref, packet)
+                         : scrub_lane_dwords(loc, R, dw_pref, packet);
     *out = LaunchForm{family, 1, R, 0, 0, 0, 0, dw};
     return true;
   }

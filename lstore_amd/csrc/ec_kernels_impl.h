@@ -2338,6 +2338,410 @@ LSEC_DECLARE_UPD_R(1) LSEC_DECLARE_UPD_R(2) LSEC_DECLARE_UPD_R(3) LSEC_DECLARE_U
 LSEC_DECLARE_UPD_R(5) LSEC_DECLARE_UPD_R(6) LSEC_DECLARE_UPD_R(7) LSEC_DECLARE_UPD_R(8)
 #endif
 
+// lsec_update_dev_rotated (ec_kernels.h, UpdateRotArgs): the update over the K + R physical devices
+// of a rotated LUN, in the update's own forms.
+__device__ __forceinline__ uint32_t upd_col(const UpdateRotArgs &a, int i) {
+  uint32_t w;
+  __builtin_memcpy(&w, a.col + (i & ~3), 4);
+  return (w >> (8 * (i & 3))) & 0xFFu;
+}
+
+// Where a tile of stripe s takes the ref of changed chunk i as stored / parity row r from:
+// sh[(col[i] - rot_s) mod n] / sh[(K + r - rot_s) mod n], by the rotated check's ChkShards.
+struct UpdShards {
+  const UpdateRotArgs &a;
+  const ChkShards<UpdateRotArgs> sh;
+  __device__ __forceinline__ UpdShards(const UpdateRotArgs &a_, uint32_t s) : a(a_), sh(a_, s) {}
+  __device__ __forceinline__ ShardRef old(int i) const { return sh.in(static_cast<int>(upd_col(a, i))); }
+  __device__ __forceinline__ ShardRef par(int r) const { return sh.par(r); }
+};
+
+// upd_bytewise_tiles over the devices of a rotated LUN: a second body, differing in where a tile takes
+// its refs from (UpdShards).  (Shared with the unrotated kernels through a template parameter, the
+// body moved the code of some of their instantiations; their objects are to stay as they are.)
+template <int R, int IT, int VW, bool BF>
+__device__ __forceinline__ void updrot_bytewise_tiles(const UpdateRotArgs &a) {
+  typedef typename VecT<VW>::type V;
+  constexpr int kStep = BwTile<IT, VW>::kStep;
+  constexpr int kTile = BwTile<IT, VW>::kBytes;
+  constexpr int kLane = 4 * VW;
+  const int K = a.K;
+  const int64_t C = a.size;
+  const uint32_t tiles_per_stripe = static_cast<uint32_t>((C + kTile - 1) / kTile);
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+  const bool store = a.store != 0;  // uniform over the launch
+
+  for_tiles<(kTile >= 8192 ? 1 : 8192 / kTile)>(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const UpdShards sh(a, s);
+    const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
+    const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
+
+    V acc[IT][R];
+    if (full) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off0;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) acc[it][r] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
+      }
+      for (int i = 0; i < a.c; ++i) {
+        const ShardRef old = sh.old(i), fresh = a.fresh[i];
+        const uint64_t po = old.base + s * old.stride + off0, pf = fresh.base + s * fresh.stride + off0;
+        V d[IT], f[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+          d[it] = __builtin_nontemporal_load(gptr<V>(po + it * kStep));
+          f[it] = __builtin_nontemporal_load(gptr<V>(pf + it * kStep));
+        }
+        if (store) {
+#pragma unroll
+          for (int it = 0; it < IT; ++it) put_nt<false, V>(po + it * kStep, f[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) d[it] ^= f[it];
+        bw_acc1<R, IT, VW, BF, false>(acc, d, cells, K, static_cast<int>(upd_col(a, i)));
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off0;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) put_nt<false, V>(q + it * kStep, acc[it][r]);
+      }
+    } else {
+      // ragged last tile: units past C read as zero and are not stored, a half unit moves 8 bytes
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) acc[it][r] = load_ragged<VW>(q, off0 + it * kStep, C);
+      }
+      for (int i = 0; i < a.c; ++i) {
+        const ShardRef old = sh.old(i), fresh = a.fresh[i];
+        const uint64_t po = old.base + s * old.stride, pf = fresh.base + s * fresh.stride;
+        V d[IT], f[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+          d[it] = load_ragged<VW>(po, off0 + it * kStep, C);
+          f[it] = load_ragged<VW>(pf, off0 + it * kStep, C);
+        }
+        if (store) {
+#pragma unroll
+          for (int it = 0; it < IT; ++it) store_ragged<false, VW>(po, off0 + it * kStep, C, f[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) d[it] ^= f[it];
+        bw_acc1<R, IT, VW, BF, false>(acc, d, cells, K, static_cast<int>(upd_col(a, i)));
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
+      }
+    }
+  }, a.tile_phase);
+}
+
+template <int R, int IT, int VW, bool BF>
+__global__ __launch_bounds__(kBlock) void k_updrot_bytewise(UpdateRotArgs a) {
+  updrot_bytewise_tiles<R, IT, VW, BF>(a);
+}
+
+// k_upd_bitsliced over the devices of a rotated LUN, a second body as updrot_bytewise_tiles is.
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_updrot_bitsliced(UpdateRotArgs a) {
+  typedef typename VecT<DW>::type V;
+  const int K = a.K;
+  const uint32_t P = static_cast<uint32_t>(a.packet);
+  const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
+  constexpr uint32_t kTile = kBlock * 4 * DW;
+  const uint32_t tiles_per_stripe = (col_bytes + kTile - 1) / kTile;
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+  const bool store = a.store != 0;  // uniform over the launch
+
+  for_tiles(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const UpdShards sh(a, s);
+    const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * (4 * DW);
+    if (colb >= col_bytes) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
+    const uint32_t sp = colb / P;
+    const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+
+    V acc[R][8];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const ShardRef par = sh.par(r);
+      const uint64_t q = par.base + s * par.stride + off;
+#pragma unroll
+      for (int x = 0; x < 8; ++x) acc[r][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
+    }
+    for (int i = 0; i < a.c; ++i) {
+      const ShardRef old = sh.old(i), fresh = a.fresh[i];
+      const uint64_t po = old.base + s * old.stride + off, pf = fresh.base + s * fresh.stride + off;
+      V e[8], f[8];
+#pragma unroll
+      for (int x = 0; x < 8; ++x) {
+        e[x] = __builtin_nontemporal_load(gptr<V>(po + x * P));
+        f[x] = __builtin_nontemporal_load(gptr<V>(pf + x * P));
+      }
+      if (store) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) put_nt<false, V>(po + x * P, f[x]);
+      }
+#pragma unroll
+      for (int x = 0; x < 8; ++x) e[x] ^= f[x];
+      const uint32_t j = upd_col(a, i);
+      uint32_t c[R];
+      uint32_t cm = 0;  // bits used by any row: no doublings past the highest one
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        c[r] = cells[r * K + j].coef;
+        cm |= c[r];
+      }
+      gf8_sliced_mul_acc<0>(acc, e, c, cm);
+    }
+    // The stores go to the addresses the parity loads came from.  Kept from there to here they are
+    // 16 * R VGPRs, more than the accumulators at one dword per lane (R = 8: 236 VGPRs, 2 waves per
+    // SIMD); formed again from an offset the compiler cannot see through, they cost two adds each.
+    int64_t off_st = off;
+    asm volatile("" : "+v"(off_st));
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const ShardRef par = sh.par(r);
+      const uint64_t q = par.base + s * par.stride + off_st;
+#pragma unroll
+      for (int x = 0; x < 8; ++x) put_nt<false, V>(q + x * P, acc[r][x]);
+    }
+  }, a.tile_phase);
+}
+
+template <int R>
+hipError_t dispatch_updrot_bytewise(const UpdateRotArgs &a, hipStream_t st, int grid) {
+  constexpr BwForm f = upd_bytewise_form(R);
+  record_launch({kFormUpdRot, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0});
+  return launch_tiled(&k_updrot_bytewise<R, f.it, f.vw, f.bf>, grid, st, a);
+}
+
+template <int R, int DW>
+hipError_t updrot_bitsliced_kernel(const UpdateRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormUpdRot, 1, R, 0, 0, 0, 0, DW});
+  return launch_tiled(&k_updrot_bitsliced<R, DW>, grid, st, a);
+}
+
+template <int R>
+hipError_t dispatch_updrot_bitsliced(const UpdateRotArgs &a, hipStream_t st, int grid, int dw) {
+  if constexpr (R <= kUpdWideRows) {
+    if (dw == 4) return updrot_bitsliced_kernel<R, 4>(a, st, grid);
+    if (dw == 2) return updrot_bitsliced_kernel<R, 2>(a, st, grid);
+  }
+  return dw == 1 ? updrot_bitsliced_kernel<R, 1>(a, st, grid) : hipErrorInvalidValue;
+}
+
+// instantiated per R in ec_update_rot_inst.hip
+#define LSEC_DECLARE_UPDROT_R(RR)                                                                   \
+  extern template hipError_t dispatch_updrot_bytewise<RR>(const UpdateRotArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_updrot_bitsliced<RR>(const UpdateRotArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_UPDROT
+LSEC_DECLARE_UPDROT_R(1) LSEC_DECLARE_UPDROT_R(2) LSEC_DECLARE_UPDROT_R(3) LSEC_DECLARE_UPDROT_R(4)
+LSEC_DECLARE_UPDROT_R(5) LSEC_DECLARE_UPDROT_R(6) LSEC_DECLARE_UPDROT_R(7) LSEC_DECLARE_UPDROT_R(8)
+#endif
+
+// ------------------------------------------------------------------ encode over a rotated LUN
+// lsec_encode_dev_rotated (ec_kernels.h, EncodeRotArgs): the rotated check's tile bodies -- its
+// tile loop, its rotated input addresses (ChkShards), bw_inputs / bw_acc1, the bit-sliced lanes and
+// doubling loop -- with the accumulators stored to the devices that hold the stripe's parity rows
+// where the check loads the stored rows and compares.  No stored-parity registers (the check's pv),
+// no votes, no atomics.
+
+// BF, X0, KC as chk_bytewise_tiles.
+template <int R, int KC, int IT, bool BF, int VW, bool X0>
+__device__ __forceinline__ void encrot_bytewise_tiles(const EncodeRotArgs &a) {
+  typedef typename VecT<VW>::type V;
+  constexpr int kStep = BwTile<IT, VW>::kStep;
+  constexpr int kTile = BwTile<IT, VW>::kBytes;
+  constexpr int kLane = 4 * VW;
+  const int K = KC ? KC : a.K;
+  const int64_t C = a.size;
+  const uint32_t tiles_per_stripe = static_cast<uint32_t>((C + kTile - 1) / kTile);
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+
+  for_tiles<(kTile >= 8192 ? 1 : 8192 / kTile)>(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const ChkShards<EncodeRotArgs> sh(a, s);
+    const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
+    const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
+
+    V acc[IT][R];
+#pragma unroll
+    for (int it = 0; it < IT; ++it)
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[it][r] = 0u;
+
+    if (full) {
+      bw_inputs<R, KC, IT, VW, BF, X0>(
+          acc, cells, K,
+          [&](int j) LSEC_INLINE {
+            const ShardRef in = sh.in(j);
+            return in.base + s * in.stride + off0;
+          },
+          NoLoads());
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off0;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) put_nt<false, V>(q + it * kStep, acc[it][r]);
+      }
+    } else {
+      // ragged last tile: units past C read as zero and are not stored, a half unit moves 8 bytes
+      for (int j = 0; j < K; ++j) {
+        const ShardRef in = sh.in(j);
+        const uint64_t p = in.base + s * in.stride;
+        V v[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) v[it] = load_ragged<VW>(p, off0 + it * kStep, C);
+        bw_acc1<R, IT, VW, BF, X0>(acc, v, cells, K, j);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
+      }
+    }
+  }, a.tile_phase);
+}
+
+// the XOR-row flag picks one of two whole instantiations, by k_gf8_bytewise's rule
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_encrot_bytewise(EncodeRotArgs a) {
+  if constexpr (BF && R >= 2 && (KC == 0 || KC * R >= 40)) {
+    if (const_cells(a.cells)->pad & kCellXorRow) {
+      encrot_bytewise_tiles<R, KC, IT, BF, VW, true>(a);
+      return;
+    }
+  }
+  encrot_bytewise_tiles<R, KC, IT, BF, VW, false>(a);
+}
+
+// k_gf8_bitsliced's lanes and doubling loop.  Lanes past the end of a ragged last tile leave the tile body.
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_encrot_bitsliced(EncodeRotArgs a) {
+  typedef typename VecT<DW>::type V;
+  const int K = a.K;
+  const uint32_t P = static_cast<uint32_t>(a.packet);
+  const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
+  constexpr uint32_t kTile = kBlock * 4 * DW;
+  const uint32_t tiles_per_stripe = (col_bytes + kTile - 1) / kTile;
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+
+  for_tiles(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    const ChkShards<EncodeRotArgs> sh(a, s);
+    const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * (4 * DW);
+    if (colb >= col_bytes) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
+    const uint32_t sp = colb / P;
+    const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+
+    V acc[R][8];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
+
+    for (int j = 0; j < K; ++j) {
+      const ShardRef in = sh.in(j);
+      const uint64_t p = in.base + s * in.stride + off;
+      V e[8];
+#pragma unroll
+      for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<V>(p + x * P));
+      uint32_t c[R];
+      uint32_t cm = 0;  // bits used by any output: no doublings past the highest one
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        c[r] = cells[r * K + j].coef;
+        cm |= c[r];
+      }
+      gf8_sliced_mul_acc<0>(acc, e, c, cm);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const ShardRef par = sh.par(r);
+      const uint64_t q = par.base + s * par.stride + off;
+#pragma unroll
+      for (int x = 0; x < 8; ++x) put_nt<false, V>(q + x * P, acc[r][x]);
+    }
+  }, a.tile_phase);
+}
+
+template <int R, int KC, int IT, bool BF, int VW>
+hipError_t encrot_bytewise_kernel(const EncodeRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormEncRot, 0, R, KC, IT, VW, BF ? 1 : 0, 0});
+  return launch_tiled(&k_encrot_bytewise<R, KC, IT, BF, VW>, grid, st, a);
+}
+
+template <int R, int DW>
+hipError_t encrot_bitsliced_kernel(const EncodeRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormEncRot, 1, R, 0, 0, 0, 0, DW});
+  return launch_tiled(&k_encrot_bitsliced<R, DW>, grid, st, a);
+}
+
+// the form is the rotated check's for the same K x R (chk_bytewise_form), switched on as dispatch_scrub_bytewise does
+template <int R>
+hipError_t dispatch_encrot_bytewise(const EncodeRotArgs &a, hipStream_t st, int grid) {
+  const BwForm f = chk_bytewise_form(a.K, R);
+  switch (f.kc) {
+#define LSEC_ENCROT_K(KK)                                                        \
+  case KK: {                                                                     \
+    constexpr BwForm ff = chk_bytewise_form(KK, R);                              \
+    if constexpr (ff.kc == KK)                                                   \
+      return encrot_bytewise_kernel<R, KK, ff.it, ff.bf, ff.vw>(a, st, grid);    \
+    break;                                                                       \
+  }
+    LSEC_FIXED_K(LSEC_ENCROT_K)
+#undef LSEC_ENCROT_K
+    default: break;
+  }
+  if constexpr (R == 1) {
+    return encrot_bytewise_kernel<1, 0, 1, false, 2>(a, st, grid);
+  } else {
+    if (f.it == 1) return encrot_bytewise_kernel<R, 0, 1, true, 4>(a, st, grid);
+    return encrot_bytewise_kernel<R, 0, 2, true, 4>(a, st, grid);
+  }
+}
+
+// dw dwords per lane, as the rotated check wherever the encode's policy sends it (cauchy8_bitsliced_dw
+// asks for more than one dword up to kEncRotWideRows rows only; the wider forms beyond, 256 VGPRs of
+// accumulators at eight rows, are not instantiated)
+constexpr int kEncRotWideRows = kLocWideRows;
+template <int R>
+hipError_t dispatch_encrot_bitsliced(const EncodeRotArgs &a, hipStream_t st, int grid, int dw) {
+  if constexpr (R <= kEncRotWideRows) {
+    if (dw == 4) return encrot_bitsliced_kernel<R, 4>(a, st, grid);
+    if (dw == 2) return encrot_bitsliced_kernel<R, 2>(a, st, grid);
+  }
+  return dw == 1 ? encrot_bitsliced_kernel<R, 1>(a, st, grid) : hipErrorInvalidValue;
+}
+
+// instantiated per R in ec_encode_rot_inst.hip
+#define LSEC_DECLARE_ENCROT_R(RR)                                                                   \
+  extern template hipError_t dispatch_encrot_bytewise<RR>(const EncodeRotArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_encrot_bitsliced<RR>(const EncodeRotArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_ENCROT
+LSEC_DECLARE_ENCROT_R(1) LSEC_DECLARE_ENCROT_R(2) LSEC_DECLARE_ENCROT_R(3) LSEC_DECLARE_ENCROT_R(4)
+LSEC_DECLARE_ENCROT_R(5) LSEC_DECLARE_ENCROT_R(6) LSEC_DECLARE_ENCROT_R(7) LSEC_DECLARE_ENCROT_R(8)
+#endif
+
 #define LSEC_DECLARE_R(RR)                                                                         \
   extern template hipError_t dispatch_bytewise<RR>(const ApplyArgs &, hipStream_t, int, int);      \
   extern template hipError_t dispatch_bitsliced<RR>(const ApplyArgs &, hipStream_t, int, int);         \

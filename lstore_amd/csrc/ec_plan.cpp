@@ -598,7 +598,7 @@ int cauchy8_bitsliced_dw(int K, int R, long long size) {
 // Stripes per launch of chunks of C bytes: batches split so that the indices of their tiles (of
 // tile_bytes: 4096, or the stripe-magic calls' 8192) stay 32-bit.  With `split`,
 // lsec_test_set_pattern_split can lower it: the patterned calls, the repair behind a locate, every
-// launch of the rotated check and locate, and the parity update.
+// launch of the rotated check and locate, the parity update and the rotated encode and update.
 std::atomic<int> g_pattern_split{0};  // stripes per launch, 0 = the 32-bit tile limit only
 
 long long launch_stripes(long long C, bool split, long long tile_bytes) {
@@ -1240,61 +1240,38 @@ int locate_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
   return scrub_dev(e, c, devs, nstripes, C, syndrome, nullptr, st);
 }
 
-// ---------------------------------------------------------------- parity update
+// ---------------------------------------------------------------- parity update, rotated or not
 // lsec_update_dev: parity_r ^= sum_i g[r][cols[i]] * (old_i ^ fresh_i), and with LSEC_UPDATE_STORE
 // old_i <- fresh_i, over the cached encode image: one launch per 32-bit range of tiles (as
 // enqueue_scrub), nothing allocated or uploaded per call.  Only the c changed chunks, their fresh
 // contents and the m parity chunks are looked at: every other entry of sh is never read, here or in
 // the kernel.  One validation ladder, in the order of the header's refusal list; it touches no device.
-int update_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *cols, const lsec_shard_t *fresh,
-               int flags, hipStream_t st) {
-  lsec::launch_record_reset();  // (lsec_test_launch_record)
-  lio_erasure_plan_t *p = &e->pub;
-  const int kind = kernel_kind(p->method, p->w);
-  if (kind != KBYTEWISE && kind != KBITSLICED)
-    return fail("lsec_update_dev needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d",
-                JE_method[p->method], p->w, kind);
-  const int k = p->data_strips, m = p->parity_strips;
-  if (k < 1 || k > lsec::kMaxK) return fail("lsec_update_dev: k=%d outside 1..%d (one launch's columns)", k, lsec::kMaxK);
-  if (m < 1 || m > 8) return fail("lsec_update_dev: m=%d outside 1..8 (one launch's parity rows)", m);
-  if (!sh) return fail("shards is NULL");
-  if (!cols) return fail("cols is NULL");
-  if (!fresh) return fail("fresh is NULL");
-  if (cols[0] == -1) return fail("lsec_update_dev: cols is empty (1..k=%d changed data chunks)", k);
-  lsec::UpdateArgs a;
+//
+// lsec_update_dev_rotated: the same over the k+m physical devices of a rotated LUN.  The kernels
+// work each stripe's rotation out themselves (ec_kernels.h, UpdateRotArgs); every device holds a
+// changed chunk or parity in some stripe, so all k+m entries are validated and travel.  Each later
+// launch's rot0 advances by (s0 mod n) * rot_step, as the rotated check's.
+//
+// The two calls are one path (update_path) that an UpdateCall steers.
+namespace {
+
+// What tells the two calls apart.  The unrotated call leaves the rotation at 0.
+struct UpdateCall {
+  const char *name;  // for messages
+  bool rotated;
+  int n_shift;
+  long long first_stripe;
+};
+
+// the launches: one per 32-bit range of tiles, in the update's own launch shape for R rows
+template <typename Args>
+int enqueue_update(const UpdateCall &uc, const lio_erasure_plan_t *p, const void *cells, const uint8_t *col, int c,
+                   const lsec_shard_t *sh, const int *cols, const lsec_shard_t *fresh, int nstripes, long long C, int flags,
+                   hipStream_t st) {
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  Args a;
   std::memset(static_cast<void *>(&a), 0, sizeof(a));
-  unsigned long long seen = 0;
-  int c = 0;
-  for (; cols[c] != -1; ++c) {
-    if (c == k) return fail("lsec_update_dev: cols lists more than k=%d chunks", k);
-    const int id = cols[c];
-    if (id < 0) return fail("lsec_update_dev: cols[%d] = %d is negative (data chunk ids are 0..%d)", c, id, k - 1);
-    if (id >= k)
-      return fail("lsec_update_dev: cols[%d] = %d is not a data chunk (ids are 0..%d; %d..%d are parity)", c, id, k - 1, k, k + m - 1);
-    if (seen >> id & 1) return fail("lsec_update_dev: cols lists chunk %d twice (ids must be distinct)", id);
-    seen |= 1ull << id;
-    a.col[c] = static_cast<uint8_t>(id);
-  }
-  if (flags & ~LSEC_UPDATE_STORE) return fail("lsec_update_dev: flags %#x has bits other than LSEC_UPDATE_STORE", flags);
-  const auto aligned = [&](const char *what, int i, const lsec_shard_t &s) {
-    if (reinterpret_cast<uintptr_t>(s.base) % 8 != 0)
-      return fail("%s %d: base %p is not a multiple of 8 bytes (lsec_shard_t)", what, i, s.base);
-    if (nstripes > 1 && s.stride % 8 != 0)
-      return fail("%s %d: stride %lld is not a multiple of 8 bytes (lsec_shard_t)", what, i, s.stride);
-    return 0;
-  };
-  for (int i = 0; i < c; ++i)
-    if (aligned("shard", cols[i], sh[cols[i]]) || aligned("fresh", i, fresh[i])) return -1;
-  for (int r = 0; r < m; ++r)
-    if (aligned("shard", k + r, sh[k + r])) return -1;
-  if (check_geometry(p, C)) return -1;
-  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
-  if (nstripes == 0) return 0;
-  const void *cells = nullptr;
-  if (encode_image(e, &cells)) return -1;
-  const int R = encode_rows(e);
-  if (R != m) return fail("lsec_update_dev: the plan encodes %d parity rows, m=%d", R, m);
-  if (C == 0) return 0;
+  std::memcpy(a.col, col, static_cast<size_t>(c));
   a.cells = static_cast<const CoefCell *>(cells);
   a.K = k;
   a.R = m;
@@ -1302,18 +1279,157 @@ int update_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, co
   a.size = C;
   a.packet = p->packet_size;
   a.store = (flags & LSEC_UPDATE_STORE) ? 1 : 0;
+  uint32_t rot0 = 0;
+  if constexpr (lsec::kRotArgs<Args>) {
+    a.rot_step = static_cast<uint32_t>(uc.n_shift % n);
+    a.rot_n = static_cast<uint32_t>(n);
+    rot0 = pattern_rot0(n, uc.n_shift, uc.first_stripe);
+  }
   // the encode's dwords per lane for this shape (0: its packet network, which the update has no form of)
+  const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
+  const int dw = sliced ? cauchy8_bitsliced_dw(k, m, C) : 0;
+  return for_launches(nstripes, launch_stripes(C, true), [&](long long s0, int ns) {
+    a.nstripes = ns;
+    for (int i = 0; i < c; ++i) a.fresh[i] = shard_from(fresh[i], s0);
+    hipError_t err;
+    if constexpr (lsec::kRotArgs<Args>) {
+      a.rot0 = rot0_from(rot0, a.rot_step, n, s0);
+      for (int i = 0; i < n; ++i) a.sh[i] = shard_from(sh[i], s0);
+      err = sliced ? lsec::launch_update_rot_bitsliced(a, st, dw) : lsec::launch_update_rot_bytewise(a, st);
+    } else {
+      for (int i = 0; i < c; ++i) a.old[i] = shard_from(sh[cols[i]], s0);
+      for (int r = 0; r < m; ++r) a.par[r] = shard_from(sh[k + r], s0);
+      err = sliced ? lsec::launch_update_bitsliced(a, st, dw) : lsec::launch_update_bytewise(a, st);
+    }
+    if (err != hipSuccess) return fail("%supdate kernel launch failed: %s", uc.rotated ? "rotated " : "", hipGetErrorString(err));
+    return 0;
+  });
+}
+
+int update_path(PlanExt *e, const UpdateCall &uc, const lsec_shard_t *sh, int nstripes, long long C, const int *cols,
+                const lsec_shard_t *fresh, int flags, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("%s needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d", uc.name,
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips;
+  if (k < 1 || k > lsec::kMaxK) return fail("%s: k=%d outside 1..%d (one launch's columns)", uc.name, k, lsec::kMaxK);
+  if (m < 1 || m > 8) return fail("%s: m=%d outside 1..8 (one launch's parity rows)", uc.name, m);
+  if (!sh) return fail("%s is NULL", uc.rotated ? "devs" : "shards");
+  if (!cols) return fail("cols is NULL");
+  if (!fresh) return fail("fresh is NULL");
+  if (cols[0] == -1) return fail("%s: cols is empty (1..k=%d changed data chunks)", uc.name, k);
+  uint8_t col[lsec::kMaxK];
+  unsigned long long seen = 0;
+  int c = 0;
+  for (; cols[c] != -1; ++c) {
+    if (c == k) return fail("%s: cols lists more than k=%d chunks", uc.name, k);
+    const int id = cols[c];
+    if (id < 0) return fail("%s: cols[%d] = %d is negative (data chunk ids are 0..%d)", uc.name, c, id, k - 1);
+    if (id >= k)
+      return fail("%s: cols[%d] = %d is not a data chunk (ids are 0..%d; %d..%d are parity)", uc.name, c, id, k - 1, k, k + m - 1);
+    if (seen >> id & 1) return fail("%s: cols lists chunk %d twice (ids must be distinct)", uc.name, id);
+    seen |= 1ull << id;
+    col[c] = static_cast<uint8_t>(id);
+  }
+  if (flags & ~LSEC_UPDATE_STORE) return fail("%s: flags %#x has bits other than LSEC_UPDATE_STORE", uc.name, flags);
+  if (uc.n_shift < 0) return fail("n_shift %d is negative", uc.n_shift);
+  if (uc.first_stripe < 0) return fail("first_stripe %lld is negative", uc.first_stripe);
+  const auto aligned = [&](const char *what, int i, const lsec_shard_t &s) {
+    if (reinterpret_cast<uintptr_t>(s.base) % 8 != 0)
+      return fail("%s %d: base %p is not a multiple of 8 bytes (lsec_shard_t)", what, i, s.base);
+    if (nstripes > 1 && s.stride % 8 != 0)
+      return fail("%s %d: stride %lld is not a multiple of 8 bytes (lsec_shard_t)", what, i, s.stride);
+    return 0;
+  };
+  if (uc.rotated) {
+    // every device holds a changed chunk in some stripe and parity in others: all k+m are used
+    for (int i = 0; i < k + m; ++i)
+      if (aligned("device", i, sh[i])) return -1;
+    for (int i = 0; i < c; ++i)
+      if (aligned("fresh", i, fresh[i])) return -1;
+  } else {
+    for (int i = 0; i < c; ++i)
+      if (aligned("shard", cols[i], sh[cols[i]]) || aligned("fresh", i, fresh[i])) return -1;
+    for (int r = 0; r < m; ++r)
+      if (aligned("shard", k + r, sh[k + r])) return -1;
+  }
+  if (check_geometry(p, C)) return -1;
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_image(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("%s: the plan encodes %d parity rows, m=%d", uc.name, R, m);
+  if (C == 0) return 0;
+  const auto enqueue = uc.rotated ? enqueue_update<lsec::UpdateRotArgs> : enqueue_update<lsec::UpdateArgs>;
+  return enqueue(uc, p, cells, col, c, sh, cols, fresh, nstripes, C, flags, st);
+}
+
+}  // namespace
+
+int update_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *cols, const lsec_shard_t *fresh,
+               int flags, hipStream_t st) {
+  const UpdateCall uc = {"lsec_update_dev"};
+  return update_path(e, uc, sh, nstripes, C, cols, fresh, flags, st);
+}
+
+int update_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                       const int *cols, const lsec_shard_t *fresh, int flags, hipStream_t st) {
+  const UpdateCall uc = {"lsec_update_dev_rotated", true, n_shift, first_stripe};
+  return update_path(e, uc, devs, nstripes, C, cols, fresh, flags, st);
+}
+
+// ---------------------------------------------------------------- encode over a rotated LUN
+// lsec_encode_dev_rotated: the parity rows lsec_encode_dev writes for the logical view of every
+// stripe, written to the devices that hold them (ec_kernels.h, EncodeRotArgs).  Validated as the
+// rotated check, minus its outputs; the launches are the rotated check's too (one per 32-bit range
+// of tiles, rot0 advancing from launch to launch), over the cached encode image.  A Cauchy plan
+// takes the bit-sliced table kernel at every shape, as the check does: the compiled packet
+// networks have no rotated form, and the bytes are the same.
+int encode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                       hipStream_t st) {
+  static const char *const name = "lsec_encode_dev_rotated";
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("%s needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d", name,
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  if (k < 1 || k > lsec::kMaxK) return fail("%s: k=%d outside 1..%d (one launch's inputs)", name, k, lsec::kMaxK);
+  if (m < 1 || m > 8) return fail("%s: m=%d outside 1..8 (one launch's parity rows)", name, m);
+  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (n_shift < 0) return fail("n_shift %d is negative", n_shift);
+  if (first_stripe < 0) return fail("first_stripe %lld is negative", first_stripe);
+  if (check_geometry(p, C)) return -1;
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_image(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("%s: the plan encodes %d parity rows, m=%d", name, R, m);
+  if (C == 0) return 0;
+  lsec::EncodeRotArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  a.cells = static_cast<const CoefCell *>(cells);
+  a.K = k;
+  a.R = m;
+  a.size = C;
+  a.packet = p->packet_size;
+  a.rot_step = static_cast<uint32_t>(n_shift % n);
+  a.rot_n = static_cast<uint32_t>(n);
+  const uint32_t rot0 = pattern_rot0(n, n_shift, first_stripe);
+  // the encode's dwords per lane for this shape (0: its packet network, which the rotated encode has no form of)
   const bool sliced = kind == KBITSLICED;
   const int dw = sliced ? cauchy8_bitsliced_dw(k, m, C) : 0;
   return for_launches(nstripes, launch_stripes(C, true), [&](long long s0, int ns) {
     a.nstripes = ns;
-    for (int i = 0; i < c; ++i) {
-      a.old[i] = shard_from(sh[cols[i]], s0);
-      a.fresh[i] = shard_from(fresh[i], s0);
-    }
-    for (int r = 0; r < m; ++r) a.par[r] = shard_from(sh[k + r], s0);
-    const hipError_t err = sliced ? lsec::launch_update_bitsliced(a, st, dw) : lsec::launch_update_bytewise(a, st);
-    if (err != hipSuccess) return fail("update kernel launch failed: %s", hipGetErrorString(err));
+    a.rot0 = rot0_from(rot0, a.rot_step, n, s0);
+    for (int i = 0; i < n; ++i) a.sh[i] = shard_from(devs[i], s0);
+    const hipError_t err = sliced ? lsec::launch_encode_rot_bitsliced(a, st, dw) : lsec::launch_encode_rot_bytewise(a, st);
+    if (err != hipSuccess) return fail("rotated encode kernel launch failed: %s", hipGetErrorString(err));
     return 0;
   });
 }
@@ -1706,7 +1822,8 @@ int lsec_test_apply_path(void) { return tl_apply_path; }
 
 // Test hook, not in include/: the kernel forms (ec_kernels.h, LaunchForm) that the calling thread's last
 // lsec_check_dev, lsec_locate_dev, lsec_decode_dev_patterns, lsec_decode_dev_rotated,
-// lsec_check_dev_rotated, lsec_locate_dev_rotated or lsec_update_dev launched, in order: a locate with repair its
+// lsec_check_dev_rotated, lsec_locate_dev_rotated, lsec_update_dev, lsec_encode_dev_rotated or
+// lsec_update_dev_rotated launched, in order: a locate with repair its
 // patterned decode too, a split call every launch; the finalize launch, which has one form, is not
 // among them.  forms: 8 ints each (family, bit-sliced, R, KC, IT, VW, BF, DW).  Returns the number
 // of launches; at most min(that, max_forms, 16) are written.
@@ -1721,7 +1838,8 @@ int lsec_test_launch_record(int *forms, int max_forms) {
 }
 
 // Test hook, not in include/ (no GPU): the form a launch of `family` (1 check, 2 locate, 3 rotated
-// check, 4 rotated locate, 5 patterned decode, 6 rotated repair, 7 parity update) takes for a plan of kernel 1
+// check, 4 rotated locate, 5 patterned decode, 6 rotated repair, 7 parity update, 8 rotated encode, 9 rotated
+// parity update) takes for a plan of kernel 1
 // (bytewise) or 2 (bit-sliced) with K inputs and R rows (patterned: the table's largest erasure
 // count) at that packet and chunk size, as 8 ints.  It asks the functions the dispatch calls
 // (cauchy8_bitsliced_dw here, lsec::predict_launch for the rest).  0, or -1 with a message.
@@ -1749,7 +1867,8 @@ void lsec_test_set_cauchy8_policy(int mode) { g_c8_policy.store(mode == 1 ? 1 : 
 // A/B runs in one allocation.
 void lsec_test_set_tile_phase(int mode) { lsec::set_tile_phase(mode); }
 
-// Test hook, not in include/: a patterned call (and lsec_update_dev) launches at most `stripes` stripes at a time
+// Test hook, not in include/: a patterned call (and lsec_update_dev, lsec_encode_dev_rotated and
+// lsec_update_dev_rotated) launches at most `stripes` stripes at a time
 // (0, the default: only the 32-bit tile limit splits), so a small batch exercises the split.
 void lsec_test_set_pattern_split(int stripes) { g_pattern_split.store(std::max(0, stripes), std::memory_order_relaxed); }
 

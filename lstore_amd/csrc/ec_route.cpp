@@ -661,6 +661,25 @@ int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
                             counts, dev_faults, flags, static_cast<hipStream_t>(stream));
 }
 
+int lsec_encode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                            int n_shift, long long first_stripe, void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!devs) return fail("devs is NULL");
+  if (check_shards(plan, devs, nstripes)) return -1;
+  return encode_dev_rotated(e, devs, nstripes, block_size, n_shift, first_stripe, static_cast<hipStream_t>(stream));
+}
+
+// (no check_shards: update_path's ladder validates all k+m devices where lsec_update_dev's validates its shards)
+int lsec_update_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                            int n_shift, long long first_stripe, const int *cols, const lsec_shard_t *fresh, int flags,
+                            void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  return update_dev_rotated(e, devs, nstripes, block_size, n_shift, first_stripe, cols, fresh, flags,
+                            static_cast<hipStream_t>(stream));
+}
+
 int et_encode_stripes_magic(lio_erasure_plan_t *plan, char **ptrs, int nstripes, int block_size, char *magic) {
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");

@@ -83,7 +83,8 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_set_kernel_variant", "lsec_set_host_devices", "lsec_hbm_copy_dev", "lsec_hbm_mix_dev", "lsec_prepare_encode", "lsec_plan_jit", "lsec_device_numa",
            "lsec_set_tile_sharing", "lsec_tile_sharing", "lsec_host_unpin_drain", "lsec_hbm_decode_shape_dev",
            "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev", "lsec_locate_dev",
-           "lsec_check_dev_rotated", "lsec_locate_dev_rotated", "lsec_update_dev")
+           "lsec_check_dev_rotated", "lsec_locate_dev_rotated", "lsec_update_dev",
+           "lsec_encode_dev_rotated", "lsec_update_dev_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -153,6 +154,9 @@ def lib():
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.lsec_update_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.POINTER(ShardRef),
                                   C.c_int, C.c_void_p]
+    L.lsec_encode_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p]
+    L.lsec_update_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
+                                          C.POINTER(C.c_int), C.POINTER(ShardRef), C.c_int, C.c_void_p]
     L.lsec_test_locate_ratio.argtypes = [P, C.c_int, C.c_int]
     L.lsec_test_plan_images.argtypes = [P]
     L.lsec_test_set_pattern_split.argtypes = [C.c_int]
@@ -658,6 +662,24 @@ class Plan:
         fresh_refs = [(fresh.data_ptr() + i * fresh.stride(1), fresh.stride(0)) for i in range(len(cols))]
         self.update_dev_refs(refs, n, size, cols, fresh_refs, store, _stream_handle(stream))
 
+    def encode_dev_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
+                                stream: int = 0) -> None:
+        """lsec_encode_dev_rotated: encode_dev_refs over the PHYSICAL devices of a rotated LUN (refs[i]: device i,
+        as check_dev_rotated_refs takes them): each stripe's parity goes to the devices its rotation names.
+        refs None: NULL."""
+        _check(lib().lsec_encode_dev_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                             n_shift, first_stripe, stream), "lsec_encode_dev_rotated")
+
+    def update_dev_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int, cols,
+                                fresh_refs, store: bool = False, stream: int = 0) -> None:
+        """lsec_update_dev_rotated: update_dev_refs over the PHYSICAL devices of a rotated LUN.  cols are logical
+        data chunk ids and fresh_refs[i] is a logical buffer (not rotated); the old chunks and the parity are
+        taken from, and written to, the devices each stripe's rotation names.  refs / cols / fresh_refs None: NULL."""
+        _check(lib().lsec_update_dev_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                             n_shift, first_stripe, None if cols is None else _erasure_array(cols),
+                                             None if fresh_refs is None else self.shard_refs(fresh_refs),
+                                             UPDATE_STORE if store else 0, stream), "lsec_update_dev_rotated")
+
     def prepare_decode(self, erasures) -> None:
         _check(lib().lsec_prepare_decode(self._p, _erasure_array(erasures)), "lsec_prepare_decode")
 
@@ -736,7 +758,7 @@ def apply_path() -> int:
     return int(lib().lsec_test_apply_path())
 
 
-FORM_FAMILIES = ("chk", "loc", "chkrot", "locrot", "pat", "patrot", "upd")
+FORM_FAMILIES = ("chk", "loc", "chkrot", "locrot", "pat", "patrot", "upd", "encrot", "updrot")
 Form = collections.namedtuple("Form", "family sliced R KC IT VW BF DW")
 Form.__doc__ = """One separately compiled kernel of the check / locate / patterned / rotated / update calls: family (one of
 FORM_FAMILIES), sliced (plan kernel 2), R rows; bytewise: KC (0 = K at run time), IT steps of VW dwords
@@ -749,7 +771,7 @@ def _form(v) -> Form:
 
 def launch_record() -> list:
     """Test hook: the Forms this thread's last check_dev / locate_dev / decode_dev_patterns / decode_dev_rotated
-    / check_dev_rotated / locate_dev_rotated / update_dev call launched, in order (a locate with repair: its patterned
+    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated call launched, in order (a locate with repair: its patterned
     decode too; a split call: every launch)."""
     buf = (C.c_int * (8 * 16))()
     n = lib().lsec_test_launch_record(buf, 16)
@@ -785,7 +807,7 @@ def fixed_k() -> tuple:
 
 
 def set_pattern_split(stripes: int = 0) -> None:
-    """Test hook: a patterned decode (and update_dev) launches at most `stripes` stripes at a time (0: no extra split)."""
+    """Test hook: a patterned decode (and update_dev, encode_dev_rotated, update_dev_rotated) launches at most `stripes` stripes at a time (0: no extra split)."""
     lib().lsec_test_set_pattern_split(int(stripes))
 
 
