@@ -331,9 +331,9 @@ int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
  *   cols may not.
  * - Nothing is allocated and nothing is uploaded per call: the kernel indexes the plan's cached
  *   encode image by column.
- * - One column list per call: stripes that change in different chunks take separate calls.  There
- *   are no per-stripe lists.  The form over the physical devices of a rotated LUN is
- *   lsec_update_dev_rotated, below.
+ * - One column list per call.  Stripes that change in different chunks take
+ *   lsec_update_dev_masked, below: one 64-bit word per stripe names its changed chunks, in one
+ *   launch.  The form over the physical devices of a rotated LUN is lsec_update_dev_rotated, below.
  * - Every refusal -- plan kernels 3-5; k or m out of range; a NULL shards, cols or fresh; an empty
  *   list; an id < 0, an id >= k (a parity id) or a duplicate; more than k ids; unknown flag bits; a
  *   misaligned base, or a misaligned stride with nstripes > 1; a bad block_size; a negative
@@ -403,6 +403,63 @@ int lsec_encode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
 int lsec_update_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
                             long long block_size, int n_shift, long long first_stripe,
                             const int *cols, const lsec_shard_t *fresh, int flags, void *stream);
+
+/* The parity update with a changed set PER STRIPE, one pass: lsec_update_dev and
+ * lsec_update_dev_rotated for a batch whose stripes do not change in the same chunks -- the first
+ * and the last stripe of a contiguous byte-range write, or a batch of small random writes -- without
+ * sorting the stripes into classes and launching once per class.  Purely additive too: the version
+ * stays 3, a caller detects the calls by their symbols.
+ *
+ * Both calls:
+ * - `stripe_cols` is device memory: nstripes 64-bit words, 8-byte aligned.  Bit j (j < k) of
+ *   stripe_cols[s] means "data chunk j of stripe s changes".  It is only read; the caller must not
+ *   change it while the call is in flight; it must not overlap shards / devs or fresh.
+ * - `fresh` has k entries INDEXED BY LOGICAL CHUNK ID: fresh[j] is the new content of chunk j, under
+ *   the layout rule of lsec_shard_t.  (lsec_update_dev's fresh[i] goes with cols[i]; this one does
+ *   not.)  The usual write buffer is fresh[j] = {wbuf + j*C, k*C}.  fresh is never written.
+ * - Column j is ENABLED when fresh[j].base != NULL.  Only enabled columns are validated (base and
+ *   stride alignment of fresh[j], and in the unrotated call of shards[j], whose base must not be
+ *   NULL either); shards[j] of a column that is not enabled is ignored entirely, as lsec_update_dev
+ *   ignores the chunks that do not change.  The m parity entries are always validated; in the
+ *   rotated call all k+m devs are, as for lsec_update_dev_rotated.
+ * - The effective mask of stripe s is stripe_cols[s] & enabled & (the k low bits).  Bits >= k and
+ *   bits of columns that are not enabled are ignored: no address is ever formed from a ref the
+ *   call was not given, and the coding matrix is never indexed past column k-1.
+ * - Effect, per stripe and byte column: parity_r ^= sum over j in the effective mask of
+ *   g[r][j] * (old_j ^ fresh_j) for every r < m (for Cauchy the bit-sliced product over packets, as
+ *   the encode forms it).  The bytes left in a stripe are exactly those lsec_update_dev (or
+ *   lsec_update_dev_rotated) leaves for that stripe with cols = the set bits, the changed chunks
+ *   under LSEC_UPDATE_STORE included, and both numbered guarantees of lsec_update_dev carry over
+ *   per stripe: a consistent stripe gets the reference's parity for the replaced data, and any
+ *   stripe keeps its syndrome.
+ * - A stripe whose effective mask is 0 is neither read nor written, apart from its mask word.
+ *   Chunks outside the mask are not read.
+ * - `flags` is LSEC_UPDATE_STORE or 0, uniform over the call.
+ * - Plans, limits (k <= 64, 1 <= m <= 8, plan kernels 1 and 2), layout, alignment and block_size
+ *   rules are those of lsec_update_dev.  nstripes == 0 validates everything, returns 0 and touches
+ *   no GPU; all bases and stripe_cols may then be NULL (shards / devs and fresh themselves may not).
+ * - Nothing is allocated and nothing is uploaded per call: the masks are read where they lie, and
+ *   the kernel indexes the plan's cached encode image by column.
+ * - Every refusal -- plan kernels 3-5; k or m out of range; a NULL shards / devs or fresh; unknown
+ *   flag bits; a negative n_shift or first_stripe; with nstripes > 0 no enabled column; a
+ *   misaligned base of an enabled column's fresh or shard, of a parity chunk or of a device, or
+ *   such a stride with nstripes > 1; with nstripes > 0 an enabled column whose shards[j].base is
+ *   NULL (unrotated call); a NULL or misaligned stripe_cols with nstripes > 0; a bad block_size; a
+ *   negative nstripes -- returns -1 with a message for lsec_last_error that names the call and the
+ *   limit, and nothing is enqueued.  There is no fallback.
+ * Enqueued on `stream`; return without synchronising.  0 / -1.
+ *
+ * lsec_update_dev_masked_rotated: devs, n_shift and first_stripe mean what they mean for
+ * lsec_update_dev_rotated; the masks and fresh are logical.  Old chunk j of stripe s is read from
+ * devs[(j - rot_s) mod (k+m)], and with LSEC_UPDATE_STORE written there. */
+int lsec_update_dev_masked(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
+                           long long block_size, const unsigned long long *stripe_cols,
+                           const lsec_shard_t *fresh, int flags, void *stream);
+
+int lsec_update_dev_masked_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                                   long long block_size, int n_shift, long long first_stripe,
+                                   const unsigned long long *stripe_cols,
+                                   const lsec_shard_t *fresh, int flags, void *stream);
 
 /* Per-stripe "magic": the 4-byte little-endian zlib adler32 over the concatenation of a
  * stripe's k+m chunks that LStore's erasure segment stores in front of every chunk

@@ -231,6 +231,13 @@ int encode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
                        hipStream_t st);
 int update_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
                        const int *cols, const lsec_shard_t *fresh, int flags, hipStream_t st);
+// the update with a changed set per stripe: stripe_cols[s] bit j = data chunk j of stripe s changes (device memory),
+// fresh[j] by logical chunk id, a NULL base: column j is not enabled; rotated: over the k+m physical devices
+int update_dev_masked(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const unsigned long long *stripe_cols,
+                      const lsec_shard_t *fresh, int flags, hipStream_t st);
+int update_dev_masked_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift,
+                              long long first_stripe, const unsigned long long *stripe_cols, const lsec_shard_t *fresh,
+                              int flags, hipStream_t st);
 // stripes that do not share an erasure pattern, one launch per 32-bit range of tiles
 int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift, PatternTable &tab);
 uint32_t pattern_rot0(int n, int n_shift, long long first_stripe);

@@ -355,6 +355,40 @@ hipError_t launch_encode_rot_bitsliced(const EncodeRotArgs &a, hipStream_t strea
 hipError_t launch_update_rot_bytewise(const UpdateRotArgs &a, hipStream_t stream);
 hipError_t launch_update_rot_bitsliced(const UpdateRotArgs &a, hipStream_t stream, int dw_pref = 0);
 
+// The parity update with a changed set per stripe (lsec_update_dev_masked / _masked_rotated): bit j of
+// stripe_cols[s] says that data chunk j of stripe s changes.  One kernel family and one struct for
+// both calls: the refs are the K + R devices as in UpdateRotArgs, and the unrotated call passes its
+// logical chunks with rot_step = 0, which makes every rotation 0.  fresh is indexed by logical chunk
+// id (fresh[j] goes with chunk j, not with a list position).  A tile reads its stripe's word through
+// a uniform address, ANDs it with `allowed` -- the columns that have a fresh buffer, below K -- and
+// on 0 touches nothing more; otherwise it walks the set bits, lowest first, as the update walks
+// col[].  So no address is ever formed from fresh[j] or from a chunk's ref for a j outside
+// `allowed`: those entries are zero here.  Argument struct of its own: every other struct keeps its
+// layout.
+struct UpdateMaskArgs {
+  const CoefCell *cells;  // the encode image, R x K, row-major (device memory)
+  int K, R;
+  int nstripes;
+  int packet;             // bit-sliced: packet size P (bytes)
+  int store;              // != 0: old_j <- fresh_j in the same pass
+  int64_t size;           // bytes per shard (chunk C)
+  unsigned *tiles;        // as ApplyArgs
+  uint32_t tiles_pre;
+  uint32_t tile_phase;
+  uint32_t rot0, rot_step, rot_n;  // rot0, rot_step < rot_n = K + R; the unrotated call: 0, 0
+  unsigned long long allowed;      // bit j: fresh[j] is there and j < K
+  const unsigned long long *stripe_cols;  // nstripes words (device memory, only read)
+  ShardRef fresh[kMaxK];           // by logical chunk id (only read)
+  ShardRef sh[kRotMaxShards];      // the K + R physical devices (unrotated: the logical chunks)
+};
+static_assert(sizeof(UpdateMaskArgs) == 2264, "UpdateMaskArgs layout");
+static_assert(sizeof(UpdateMaskArgs) < 4096, "UpdateMaskArgs: under the 4 KiB of kernel arguments");
+
+// R <= 8, K <= kMaxK, allowed != 0 with no bit at or above K.  The launch shapes are the masked
+// update's own (updmask_bytewise_form, update_masked_lane_dwords): they depend on R alone.
+hipError_t launch_update_masked_bytewise(const UpdateMaskArgs &a, hipStream_t stream);
+hipError_t launch_update_masked_bitsliced(const UpdateMaskArgs &a, hipStream_t stream, int dw_pref = 0);
+
 // Which kernel ran (test hooks lsec_test_launch_record / lsec_test_predict_forms, ec_plan.cpp).  The
 // check, locate, patterned, rotated and update calls are families of separately compiled kernels; a form
 // names one of them by its template arguments: bytewise R, KC (0: K at run time), IT, VW, BF; or
@@ -362,7 +396,7 @@ hipError_t launch_update_rot_bitsliced(const UpdateRotArgs &a, hipStream_t strea
 // functions record the form at the one place where the template arguments are known; the record
 // is the calling thread's, holds the launches since launch_record_reset() in order (the engine
 // resets it on entry to each of those calls) and costs a few host stores per launch.
-enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot };
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask };
 struct LaunchForm {
   int family, sliced, R, KC, IT, VW, BF, DW;
 };
@@ -374,6 +408,8 @@ int launch_record(LaunchForm *out, int max);  // -> launches recorded; out[0 .. 
 // the functions the dispatch itself calls; dw_pref: as launch_*_bitsliced takes it.  No GPU is
 // touched.  false: no such kernel (R or K out of range, a locate of one row, a packet no lane fits).
 bool predict_launch(int family, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
+// the same for the masked update (kFormUpdMask), which predict_launch does not answer for
+bool predict_masked_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // the K with fixed-K forms (LSEC_FIXED_K), ascending -> how many there are; out[0 .. min(that, max))
 int fixed_k_list(int *out, int max);
 

@@ -600,6 +600,38 @@ hipError_t launch_update_rot_bitsliced(const UpdateRotArgs &a, hipStream_t st, i
   return by_r(a.R, [&](auto r) { return dispatch_updrot_bitsliced<decltype(r)::value>(a, st, grid, dw); });
 }
 
+// ------------------------------------------------------------------ parity update, a changed set per stripe
+namespace {
+bool update_masked_args_ok(const UpdateMaskArgs &a) {
+  if (!(a.K >= 1 && a.K <= kMaxK && a.R >= 1 && a.R <= 8 && a.cells && a.stripe_cols && a.size % 8 == 0)) return false;
+  if (!rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.K + a.R)) return false;
+  // at least one column, none at or above K: the kernels index fresh, sh and the image by these bits alone
+  return a.allowed != 0 && (a.K == 64 || (a.allowed >> a.K) == 0);
+}
+
+// dwords per lane of a bit-sliced masked update (more than kUpdMaskWideRows rows: one)
+int update_masked_lane_dwords(int R, int dw_pref, int packet) { return lane_dwords(R <= kUpdMaskWideRows ? dw_pref : 1, packet); }
+}  // namespace
+
+hipError_t launch_update_masked_bytewise(const UpdateMaskArgs &a, hipStream_t st) {
+  if (!update_masked_args_ok(a)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const BwForm f = updmask_bytewise_form(a.R);
+  const int grid = tile_grid(BwShape{f.it, f.vw, f.bf}.tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_updmask_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_update_masked_bitsliced(const UpdateMaskArgs &a, hipStream_t st, int dw_pref) {
+  if (!update_masked_args_ok(a) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int dw = update_masked_lane_dwords(a.R, dw_pref, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_updmask_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+}
+
 hipError_t launch_encode_rot_bytewise(const EncodeRotArgs &a, hipStream_t st) {
   if (!encode_rot_args_ok(a)) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
@@ -655,6 +687,18 @@ bool predict_launch(int family, bool sliced, int K, int R, int packet, int dw_pr
   }
   const BwForm f = pat ? pat_bytewise_form(K, R) : upd ? upd_bytewise_form(R) : chk_bytewise_form(K, R);
   *out = LaunchForm{family, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
+  return true;
+}
+
+bool predict_masked_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out) {
+  if (K < 1 || K > kMaxK || R < 1 || R > 8) return false;
+  if (sliced) {
+    if (packet <= 0 || packet % 4 != 0) return false;
+    *out = LaunchForm{kFormUpdMask, 1, R, 0, 0, 0, 0, update_masked_lane_dwords(R, dw_pref, packet)};
+    return true;
+  }
+  const BwForm f = updmask_bytewise_form(R);
+  *out = LaunchForm{kFormUpdMask, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
   return true;
 }
 

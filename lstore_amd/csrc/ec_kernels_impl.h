@@ -2553,6 +2553,249 @@ LSEC_DECLARE_UPDROT_R(1) LSEC_DECLARE_UPDROT_R(2) LSEC_DECLARE_UPDROT_R(3) LSEC_
 LSEC_DECLARE_UPDROT_R(5) LSEC_DECLARE_UPDROT_R(6) LSEC_DECLARE_UPDROT_R(7) LSEC_DECLARE_UPDROT_R(8)
 #endif
 
+// ------------------------------------------------------------------ parity update, a changed set per stripe
+// lsec_update_dev_masked / _masked_rotated (ec_kernels.h, UpdateMaskArgs): the update's tile bodies
+// with the column loop replaced by a walk over the set bits of the stripe's mask word.  The stripe is
+// uniform over the workgroup, so the word is read through a uniform address and made scalar; ANDed
+// with `allowed` it is the stripe's effective mask.  A tile of a stripe whose effective mask is 0
+// leaves the tile body before any other load.  Otherwise the bits are taken lowest first (find
+// first set, clear it): bit j loads the lane's units of old_j and fresh_j, stores fresh over old
+// under the launch-uniform flag, XORs the two once and multiplies once per row with
+// cells[r * K + j], a scalar load.  The refs are the rotated update's (sh, rot_back once per tile);
+// the unrotated call has rot_step = 0.  No atomics, no LDS, no cross-lane traffic.
+
+// the effective mask of stripe s (s uniform over the workgroup): scalar
+__device__ __forceinline__ uint64_t updmask_word(const UpdateMaskArgs &a, uint32_t s) {
+  const uint64_t w = *gptr<uint64_t>(reinterpret_cast<uint64_t>(a.stripe_cols) + 8ull * s);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(w));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(w >> 32));
+  return ((static_cast<uint64_t>(hi) << 32) | lo) & a.allowed;
+}
+
+// Where a tile of stripe s takes the ref of data chunk j / parity row r from: sh[(j - rot_s) mod n] /
+// sh[(K + r - rot_s) mod n], as ChkShards over a rotated struct.
+struct UpdMaskShards {
+  const UpdateMaskArgs &a;
+  const uint32_t back;
+  __device__ __forceinline__ UpdMaskShards(const UpdateMaskArgs &a_, uint32_t s) : a(a_), back(rot_back(a_, s)) {}
+  __device__ __forceinline__ ShardRef old(uint32_t j) const { return at(j); }
+  __device__ __forceinline__ ShardRef par(int r) const { return at(static_cast<uint32_t>(a.K + r)); }
+
+ private:
+  __device__ __forceinline__ ShardRef at(uint32_t c) const {
+    uint32_t i = c + back;
+    if (i >= a.rot_n) i -= a.rot_n;
+    return a.sh[i];
+  }
+};
+
+// BF as k_gf8_bytewise: the branch-free coefficient path, or per-cell branches (R = 1).
+template <int R, int IT, int VW, bool BF>
+__device__ __forceinline__ void updmask_bytewise_tiles(const UpdateMaskArgs &a) {
+  typedef typename VecT<VW>::type V;
+  constexpr int kStep = BwTile<IT, VW>::kStep;
+  constexpr int kTile = BwTile<IT, VW>::kBytes;
+  constexpr int kLane = 4 * VW;
+  const int K = a.K;
+  const int64_t C = a.size;
+  const uint32_t tiles_per_stripe = static_cast<uint32_t>((C + kTile - 1) / kTile);
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+  const bool store = a.store != 0;  // uniform over the launch
+
+  for_tiles<(kTile >= 8192 ? 1 : 8192 / kTile)>(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    uint64_t mask = updmask_word(a, s);
+    if (mask == 0) return;  // nothing of this stripe changes: neither read nor written
+    const UpdMaskShards sh(a, s);
+    const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
+    const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
+
+    V acc[IT][R];
+    if (full) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off0;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) acc[it][r] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
+      }
+      do {
+        const uint32_t j = static_cast<uint32_t>(__builtin_ctzll(mask));
+        mask &= mask - 1;
+        const ShardRef old = sh.old(j), fresh = a.fresh[j];
+        const uint64_t po = old.base + s * old.stride + off0, pf = fresh.base + s * fresh.stride + off0;
+        V d[IT], f[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+          d[it] = __builtin_nontemporal_load(gptr<V>(po + it * kStep));
+          f[it] = __builtin_nontemporal_load(gptr<V>(pf + it * kStep));
+        }
+        if (store) {
+#pragma unroll
+          for (int it = 0; it < IT; ++it) put_nt<false, V>(po + it * kStep, f[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) d[it] ^= f[it];
+        bw_acc1<R, IT, VW, BF, false>(acc, d, cells, K, static_cast<int>(j));
+      } while (mask);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off0;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) put_nt<false, V>(q + it * kStep, acc[it][r]);
+      }
+    } else {
+      // ragged last tile: units past C read as zero and are not stored, a half unit moves 8 bytes
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) acc[it][r] = load_ragged<VW>(q, off0 + it * kStep, C);
+      }
+      do {
+        const uint32_t j = static_cast<uint32_t>(__builtin_ctzll(mask));
+        mask &= mask - 1;
+        const ShardRef old = sh.old(j), fresh = a.fresh[j];
+        const uint64_t po = old.base + s * old.stride, pf = fresh.base + s * fresh.stride;
+        V d[IT], f[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+          d[it] = load_ragged<VW>(po, off0 + it * kStep, C);
+          f[it] = load_ragged<VW>(pf, off0 + it * kStep, C);
+        }
+        if (store) {
+#pragma unroll
+          for (int it = 0; it < IT; ++it) store_ragged<false, VW>(po, off0 + it * kStep, C, f[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) d[it] ^= f[it];
+        bw_acc1<R, IT, VW, BF, false>(acc, d, cells, K, static_cast<int>(j));
+      } while (mask);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
+      }
+    }
+  }, a.tile_phase);
+}
+
+template <int R, int IT, int VW, bool BF>
+__global__ __launch_bounds__(kBlock) void k_updmask_bytewise(UpdateMaskArgs a) {
+  updmask_bytewise_tiles<R, IT, VW, BF>(a);
+}
+
+// k_upd_bitsliced's lanes and doubling loop under the stripe's mask.  The mask is looked at first;
+// lanes past the end of a ragged last tile leave the tile body behind that.
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_updmask_bitsliced(UpdateMaskArgs a) {
+  typedef typename VecT<DW>::type V;
+  const int K = a.K;
+  const uint32_t P = static_cast<uint32_t>(a.packet);
+  const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
+  constexpr uint32_t kTile = kBlock * 4 * DW;
+  const uint32_t tiles_per_stripe = (col_bytes + kTile - 1) / kTile;
+  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  ConstCell *cells = const_cells(a.cells);
+  const bool store = a.store != 0;  // uniform over the launch
+
+  for_tiles(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
+    const uint32_t s = t / tiles_per_stripe;
+    uint64_t mask = updmask_word(a, s);
+    if (mask == 0) return;  // nothing of this stripe changes: neither read nor written
+    const UpdMaskShards sh(a, s);
+    const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * (4 * DW);
+    if (colb >= col_bytes) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
+    const uint32_t sp = colb / P;
+    const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+
+    V acc[R][8];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const ShardRef par = sh.par(r);
+      const uint64_t q = par.base + s * par.stride + off;
+#pragma unroll
+      for (int x = 0; x < 8; ++x) acc[r][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
+    }
+    do {
+      const uint32_t j = static_cast<uint32_t>(__builtin_ctzll(mask));
+      mask &= mask - 1;
+      const ShardRef old = sh.old(j), fresh = a.fresh[j];
+      const uint64_t po = old.base + s * old.stride + off, pf = fresh.base + s * fresh.stride + off;
+      V e[8], f[8];
+#pragma unroll
+      for (int x = 0; x < 8; ++x) {
+        e[x] = __builtin_nontemporal_load(gptr<V>(po + x * P));
+        f[x] = __builtin_nontemporal_load(gptr<V>(pf + x * P));
+      }
+      if (store) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) put_nt<false, V>(po + x * P, f[x]);
+      }
+#pragma unroll
+      for (int x = 0; x < 8; ++x) e[x] ^= f[x];
+      uint32_t c[R];
+      uint32_t cm = 0;  // bits used by any row: no doublings past the highest one
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        c[r] = cells[r * K + j].coef;
+        cm |= c[r];
+      }
+      gf8_sliced_mul_acc<0>(acc, e, c, cm);
+    } while (mask);
+    // the stores go to the addresses the parity loads came from, formed again (k_upd_bitsliced)
+    int64_t off_st = off;
+    asm volatile("" : "+v"(off_st));
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const ShardRef par = sh.par(r);
+      const uint64_t q = par.base + s * par.stride + off_st;
+#pragma unroll
+      for (int x = 0; x < 8; ++x) put_nt<false, V>(q + x * P, acc[r][x]);
+    }
+  }, a.tile_phase);
+}
+
+// The forms (DESIGN.md 3.6 has their registers): the update's, which depend on R alone.
+constexpr BwForm updmask_bytewise_form(int R) { return upd_bytewise_form(R); }
+constexpr int kUpdMaskWideRows = kUpdWideRows;
+
+template <int R>
+hipError_t dispatch_updmask_bytewise(const UpdateMaskArgs &a, hipStream_t st, int grid) {
+  constexpr BwForm f = updmask_bytewise_form(R);
+  record_launch({kFormUpdMask, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0});
+  return launch_tiled(&k_updmask_bytewise<R, f.it, f.vw, f.bf>, grid, st, a);
+}
+
+template <int R, int DW>
+hipError_t updmask_bitsliced_kernel(const UpdateMaskArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormUpdMask, 1, R, 0, 0, 0, 0, DW});
+  return launch_tiled(&k_updmask_bitsliced<R, DW>, grid, st, a);
+}
+
+template <int R>
+hipError_t dispatch_updmask_bitsliced(const UpdateMaskArgs &a, hipStream_t st, int grid, int dw) {
+  if constexpr (R <= kUpdMaskWideRows) {
+    if (dw == 4) return updmask_bitsliced_kernel<R, 4>(a, st, grid);
+    if (dw == 2) return updmask_bitsliced_kernel<R, 2>(a, st, grid);
+  }
+  return dw == 1 ? updmask_bitsliced_kernel<R, 1>(a, st, grid) : hipErrorInvalidValue;
+}
+
+// instantiated per R in ec_update_masked_inst.hip
+#define LSEC_DECLARE_UPDMASK_R(RR)                                                                    \
+  extern template hipError_t dispatch_updmask_bytewise<RR>(const UpdateMaskArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_updmask_bitsliced<RR>(const UpdateMaskArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_UPDMASK
+LSEC_DECLARE_UPDMASK_R(1) LSEC_DECLARE_UPDMASK_R(2) LSEC_DECLARE_UPDMASK_R(3) LSEC_DECLARE_UPDMASK_R(4)
+LSEC_DECLARE_UPDMASK_R(5) LSEC_DECLARE_UPDMASK_R(6) LSEC_DECLARE_UPDMASK_R(7) LSEC_DECLARE_UPDMASK_R(8)
+#endif
+
 // ------------------------------------------------------------------ encode over a rotated LUN
 // lsec_encode_dev_rotated (ec_kernels.h, EncodeRotArgs): the rotated check's tile bodies -- its
 // tile loop, its rotated input addresses (ChkShards), bw_inputs / bw_acc1, the bit-sliced lanes and

@@ -1382,6 +1382,120 @@ int update_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
   return update_path(e, uc, devs, nstripes, C, cols, fresh, flags, st);
 }
 
+// ---------------------------------------------------------------- parity update, a changed set per stripe
+// lsec_update_dev_masked / lsec_update_dev_masked_rotated: the update with one 64-bit word per stripe
+// (bit j: data chunk j changes) in device memory, and fresh indexed by logical chunk id.  A column is
+// enabled when it has a fresh buffer; the kernels AND every stripe's word with the enabled columns
+// below k (ec_kernels.h, UpdateMaskArgs), so only enabled columns travel and are validated.  One path
+// for both calls, steered by an UpdateCall; the unrotated call runs the same kernels with every
+// rotation 0.  One validation ladder, in the order of the header's refusal list; it touches no
+// device.  Launches as enqueue_update's: per launch the mask pointer advances by s0 words and rot0
+// by (s0 mod n) * rot_step.  Nothing is allocated or uploaded per call.
+namespace {
+
+int update_masked_path(PlanExt *e, const UpdateCall &uc, const lsec_shard_t *sh, int nstripes, long long C,
+                       const unsigned long long *stripe_cols, const lsec_shard_t *fresh, int flags, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("%s needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d", uc.name,
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  if (k < 1 || k > lsec::kMaxK) return fail("%s: k=%d outside 1..%d (one mask word's columns)", uc.name, k, lsec::kMaxK);
+  if (m < 1 || m > 8) return fail("%s: m=%d outside 1..8 (one launch's parity rows)", uc.name, m);
+  if (!sh) return fail("%s: %s is NULL", uc.name, uc.rotated ? "devs" : "shards");
+  if (!fresh) return fail("%s: fresh is NULL", uc.name);
+  if (flags & ~LSEC_UPDATE_STORE) return fail("%s: flags %#x has bits other than LSEC_UPDATE_STORE", uc.name, flags);
+  if (uc.n_shift < 0) return fail("%s: n_shift %d is negative", uc.name, uc.n_shift);
+  if (uc.first_stripe < 0) return fail("%s: first_stripe %lld is negative", uc.name, uc.first_stripe);
+  // the enabled columns below k, in one word (k = 64: every bit, and no shift by 64)
+  unsigned long long allowed = 0;
+  for (int j = 0; j < k; ++j)
+    if (fresh[j].base) allowed |= 1ull << j;
+  if (nstripes > 0 && !allowed)
+    return fail("%s: no enabled column (fresh[j].base is NULL for every j < k=%d)", uc.name, k);
+  const auto aligned = [&](const char *what, int i, const lsec_shard_t &s) {
+    if (reinterpret_cast<uintptr_t>(s.base) % 8 != 0)
+      return fail("%s: %s %d: base %p is not a multiple of 8 bytes (lsec_shard_t)", uc.name, what, i, s.base);
+    if (nstripes > 1 && s.stride % 8 != 0)
+      return fail("%s: %s %d: stride %lld is not a multiple of 8 bytes (lsec_shard_t)", uc.name, what, i, s.stride);
+    return 0;
+  };
+  for (int j = 0; j < k; ++j)
+    if ((allowed >> j & 1) && aligned("fresh", j, fresh[j])) return -1;
+  if (uc.rotated) {
+    // every device holds a changed chunk in some stripe and parity in others: all k+m are used
+    for (int i = 0; i < n; ++i)
+      if (aligned("device", i, sh[i])) return -1;
+  } else {
+    for (int j = 0; j < k; ++j) {
+      if (!(allowed >> j & 1)) continue;  // a column that is not enabled: its entry is ignored entirely
+      if (nstripes > 0 && !sh[j].base) return fail("%s: shard %d: base is NULL, and fresh[%d] is given", uc.name, j, j);
+      if (aligned("shard", j, sh[j])) return -1;
+    }
+    for (int r = 0; r < m; ++r)
+      if (aligned("shard", k + r, sh[k + r])) return -1;
+  }
+  if (nstripes > 0 && !stripe_cols) return fail("%s: stripe_cols is NULL", uc.name);
+  if (nstripes > 0 && reinterpret_cast<uintptr_t>(stripe_cols) % 8 != 0)
+    return fail("%s: stripe_cols %p is not a multiple of 8 bytes (64-bit words)", uc.name, static_cast<const void *>(stripe_cols));
+  if (check_geometry(p, C)) {
+    const std::string why = tl_err;  // the shared rule's message, behind the call's name
+    return fail("%s: %s", uc.name, why.c_str());
+  }
+  if (nstripes < 0) return fail("%s: nstripes %d is negative", uc.name, nstripes);
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_image(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("%s: the plan encodes %d parity rows, m=%d", uc.name, R, m);
+  if (C == 0) return 0;
+  lsec::UpdateMaskArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  a.cells = static_cast<const CoefCell *>(cells);
+  a.K = k;
+  a.R = m;
+  a.size = C;
+  a.packet = p->packet_size;
+  a.store = (flags & LSEC_UPDATE_STORE) ? 1 : 0;
+  a.allowed = allowed;
+  a.rot_step = uc.rotated ? static_cast<uint32_t>(uc.n_shift % n) : 0;
+  a.rot_n = static_cast<uint32_t>(n);
+  const uint32_t rot0 = uc.rotated ? pattern_rot0(n, uc.n_shift, uc.first_stripe) : 0;
+  // the encode's dwords per lane for this shape (0: its packet network, which the update has no form of)
+  const bool sliced = kind == KBITSLICED;
+  const int dw = sliced ? cauchy8_bitsliced_dw(k, m, C) : 0;
+  return for_launches(nstripes, launch_stripes(C, true), [&](long long s0, int ns) {
+    a.nstripes = ns;
+    a.stripe_cols = stripe_cols + s0;
+    a.rot0 = rot0_from(rot0, a.rot_step, n, s0);
+    for (int j = 0; j < k; ++j)
+      if (allowed >> j & 1) a.fresh[j] = shard_from(fresh[j], s0);
+    // (unrotated: the refs of the columns that are not enabled stay zero, and no kernel addresses them)
+    for (int i = 0; i < n; ++i)
+      if (uc.rotated || i >= k || (allowed >> i & 1)) a.sh[i] = shard_from(sh[i], s0);
+    const hipError_t err = sliced ? lsec::launch_update_masked_bitsliced(a, st, dw) : lsec::launch_update_masked_bytewise(a, st);
+    if (err != hipSuccess) return fail("%s: kernel launch failed: %s", uc.name, hipGetErrorString(err));
+    return 0;
+  });
+}
+
+}  // namespace
+
+int update_dev_masked(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const unsigned long long *stripe_cols,
+                      const lsec_shard_t *fresh, int flags, hipStream_t st) {
+  const UpdateCall uc = {"lsec_update_dev_masked"};
+  return update_masked_path(e, uc, sh, nstripes, C, stripe_cols, fresh, flags, st);
+}
+
+int update_dev_masked_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift,
+                              long long first_stripe, const unsigned long long *stripe_cols, const lsec_shard_t *fresh,
+                              int flags, hipStream_t st) {
+  const UpdateCall uc = {"lsec_update_dev_masked_rotated", true, n_shift, first_stripe};
+  return update_masked_path(e, uc, devs, nstripes, C, stripe_cols, fresh, flags, st);
+}
+
 // ---------------------------------------------------------------- encode over a rotated LUN
 // lsec_encode_dev_rotated: the parity rows lsec_encode_dev writes for the logical view of every
 // stripe, written to the devices that hold them (ec_kernels.h, EncodeRotArgs).  Validated as the
@@ -1822,8 +1936,8 @@ int lsec_test_apply_path(void) { return tl_apply_path; }
 
 // Test hook, not in include/: the kernel forms (ec_kernels.h, LaunchForm) that the calling thread's last
 // lsec_check_dev, lsec_locate_dev, lsec_decode_dev_patterns, lsec_decode_dev_rotated,
-// lsec_check_dev_rotated, lsec_locate_dev_rotated, lsec_update_dev, lsec_encode_dev_rotated or
-// lsec_update_dev_rotated launched, in order: a locate with repair its
+// lsec_check_dev_rotated, lsec_locate_dev_rotated, lsec_update_dev, lsec_encode_dev_rotated,
+// lsec_update_dev_rotated or lsec_update_dev_masked(_rotated) launched, in order: a locate with repair its
 // patterned decode too, a split call every launch; the finalize launch, which has one form, is not
 // among them.  forms: 8 ints each (family, bit-sliced, R, KC, IT, VW, BF, DW).  Returns the number
 // of launches; at most min(that, max_forms, 16) are written.
@@ -1855,6 +1969,23 @@ int lsec_test_predict_form(int family, int plan_kernel, int K, int R, int packet
   return 0;
 }
 
+// Test hook, not in include/ (no GPU): lsec_test_predict_form for the masked update (family 10 of the
+// launch record, which that hook keeps refusing): the form lsec_update_dev_masked and
+// lsec_update_dev_masked_rotated launch for a plan of kernel 1 or 2 with K columns and R rows, from
+// the functions the dispatch calls (cauchy8_bitsliced_dw here, lsec::predict_masked_launch).
+int lsec_test_predict_masked_form(int plan_kernel, int K, int R, int packet, long long block_size, int *form) {
+  if (!form) return fail("lsec_test_predict_masked_form: NULL output");
+  if (plan_kernel != KBYTEWISE && plan_kernel != KBITSLICED)
+    return fail("lsec_test_predict_masked_form: plan kernel %d", plan_kernel);
+  const bool sliced = plan_kernel == KBITSLICED;
+  lsec::LaunchForm f;
+  if (!lsec::predict_masked_launch(sliced, K, R, packet, sliced ? cauchy8_bitsliced_dw(K, R, block_size) : 0, &f))
+    return fail("lsec_test_predict_masked_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
+  const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
+  std::memcpy(form, v, sizeof(v));
+  return 0;
+}
+
 // Test hook, not in include/ (no GPU): the K that have fixed-K forms (LSEC_FIXED_K), ascending
 int lsec_test_fixed_k(int *out, int max) { return lsec::fixed_k_list(out, max); }
 
@@ -1867,8 +1998,8 @@ void lsec_test_set_cauchy8_policy(int mode) { g_c8_policy.store(mode == 1 ? 1 : 
 // A/B runs in one allocation.
 void lsec_test_set_tile_phase(int mode) { lsec::set_tile_phase(mode); }
 
-// Test hook, not in include/: a patterned call (and lsec_update_dev, lsec_encode_dev_rotated and
-// lsec_update_dev_rotated) launches at most `stripes` stripes at a time
+// Test hook, not in include/: a patterned call (and lsec_update_dev, lsec_encode_dev_rotated,
+// lsec_update_dev_rotated and lsec_update_dev_masked(_rotated)) launches at most `stripes` stripes at a time
 // (0, the default: only the 32-bit tile limit splits), so a small batch exercises the split.
 void lsec_test_set_pattern_split(int stripes) { g_pattern_split.store(std::max(0, stripes), std::memory_order_relaxed); }
 

@@ -1,0 +1,15 @@
+// ec_update_masked_inst.hip -- explicit instantiation of the parity-update kernels that take a changed
+// set per stripe (lsec_update_dev_masked, lsec_update_dev_masked_rotated) for LSEC_R parity rows.  The
+// Makefile compiles this file once per R = 1..8 with -DLSEC_R=<R>, in units of their own, so the
+// objects of the other *_inst.hip files do not change.
+#define LSEC_INSTANTIATING_UPDMASK 1
+#include "ec_kernels_impl.h"
+
+#ifndef LSEC_R
+#error "compile with -DLSEC_R=<rows>"
+#endif
+
+namespace lsec {
+template hipError_t dispatch_updmask_bytewise<LSEC_R>(const UpdateMaskArgs &, hipStream_t, int);
+template hipError_t dispatch_updmask_bitsliced<LSEC_R>(const UpdateMaskArgs &, hipStream_t, int, int);
+}  // namespace lsec

@@ -84,7 +84,8 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_set_tile_sharing", "lsec_tile_sharing", "lsec_host_unpin_drain", "lsec_hbm_decode_shape_dev",
            "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev", "lsec_locate_dev",
            "lsec_check_dev_rotated", "lsec_locate_dev_rotated", "lsec_update_dev",
-           "lsec_encode_dev_rotated", "lsec_update_dev_rotated")
+           "lsec_encode_dev_rotated", "lsec_update_dev_rotated", "lsec_update_dev_masked",
+           "lsec_update_dev_masked_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -157,6 +158,11 @@ def lib():
     L.lsec_encode_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p]
     L.lsec_update_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
                                           C.POINTER(C.c_int), C.POINTER(ShardRef), C.c_int, C.c_void_p]
+    L.lsec_update_dev_masked.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.POINTER(ShardRef),
+                                         C.c_int, C.c_void_p]
+    L.lsec_update_dev_masked_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
+                                                 C.c_void_p, C.POINTER(ShardRef), C.c_int, C.c_void_p]
+    L.lsec_test_predict_masked_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
     L.lsec_test_locate_ratio.argtypes = [P, C.c_int, C.c_int]
     L.lsec_test_plan_images.argtypes = [P]
     L.lsec_test_set_pattern_split.argtypes = [C.c_int]
@@ -680,6 +686,41 @@ class Plan:
                                              None if fresh_refs is None else self.shard_refs(fresh_refs),
                                              UPDATE_STORE if store else 0, stream), "lsec_update_dev_rotated")
 
+    def update_dev_masked_refs(self, refs, nstripes: int, block_size: int, stripe_cols_ptr: int, fresh_refs,
+                               store: bool = False, stream: int = 0) -> None:
+        """lsec_update_dev_masked: update_dev_refs with a changed set per stripe.  stripe_cols_ptr: device address
+        of nstripes uint64 words, bit j of word s: data chunk j of stripe s changes (0: NULL).  fresh_refs has k
+        entries BY LOGICAL CHUNK ID; (0, 0) leaves column j out of the call, and refs[j] is then ignored.
+        refs / fresh_refs None: NULL."""
+        _check(lib().lsec_update_dev_masked(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                            stripe_cols_ptr or None,
+                                            None if fresh_refs is None else self.shard_refs(fresh_refs),
+                                            UPDATE_STORE if store else 0, stream), "lsec_update_dev_masked")
+
+    def update_dev_masked_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
+                                       stripe_cols_ptr: int, fresh_refs, store: bool = False, stream: int = 0) -> None:
+        """lsec_update_dev_masked_rotated: update_dev_masked_refs over the PHYSICAL devices of a rotated LUN (refs[i]:
+        device i).  The masks and fresh_refs are logical; the old chunks and the parity are taken from, and written
+        to, the devices each stripe's rotation names."""
+        _check(lib().lsec_update_dev_masked_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes,
+                                                    block_size, n_shift, first_stripe, stripe_cols_ptr or None,
+                                                    None if fresh_refs is None else self.shard_refs(fresh_refs),
+                                                    UPDATE_STORE if store else 0, stream), "lsec_update_dev_masked_rotated")
+
+    def update_dev_masked(self, data, parity, stripe_cols, fresh, store=False, stream=None) -> None:
+        """torch: bring parity [N,m,C] up to date for data [N,k,C] where chunk j of stripe s changes to fresh[s, j]
+        whenever bit j of stripe_cols[s] is set; stripe_cols: 64-bit device tensor [N], fresh: uint8 [N,k,C].  data
+        still holds the old bytes, and with store=True receives the fresh ones of the changed chunks."""
+        refs, n, size = self.tensor_refs(data, parity)
+        if stripe_cols.dtype.itemsize != 8 or not stripe_cols.is_cuda or not stripe_cols.is_contiguous() \
+                or stripe_cols.numel() != n:
+            raise ValueError("stripe_cols must be a contiguous 64-bit device tensor with one entry per stripe")
+        if fresh.dtype.itemsize != 1 or not fresh.is_cuda or fresh.dim() != 3 or fresh.shape[0] != n \
+                or fresh.shape[1] != self.k or fresh.shape[2] != size or fresh.stride(2) != 1:
+            raise ValueError("fresh must be a uint8 device tensor [N, k, C] with contiguous rows")
+        fresh_refs = [(fresh.data_ptr() + j * fresh.stride(1), fresh.stride(0)) for j in range(self.k)]
+        self.update_dev_masked_refs(refs, n, size, stripe_cols.data_ptr(), fresh_refs, store, _stream_handle(stream))
+
     def prepare_decode(self, erasures) -> None:
         _check(lib().lsec_prepare_decode(self._p, _erasure_array(erasures)), "lsec_prepare_decode")
 
@@ -765,13 +806,17 @@ FORM_FAMILIES), sliced (plan kernel 2), R rows; bytewise: KC (0 = K at run time)
 per lane, BF branch-free; bit-sliced: DW dwords per lane (the others 0)."""
 
 
+# the families added behind the nine (FORM_FAMILIES stays as it is): family number 10 onwards
+MASKED_FAMILIES = ("updmask",)
+
+
 def _form(v) -> Form:
-    return Form(FORM_FAMILIES[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
+    return Form((FORM_FAMILIES + MASKED_FAMILIES)[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
 
 
 def launch_record() -> list:
     """Test hook: the Forms this thread's last check_dev / locate_dev / decode_dev_patterns / decode_dev_rotated
-    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated call launched, in order (a locate with repair: its patterned
+    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated / update_dev_masked(_rotated) call launched, in order (a locate with repair: its patterned
     decode too; a split call: every launch)."""
     buf = (C.c_int * (8 * 16))()
     n = lib().lsec_test_launch_record(buf, 16)
@@ -787,6 +832,15 @@ def predict_form(family: str, plan_kernel: int, k: int, rows: int, packet: int =
     out = (C.c_int * 8)()
     _check(lib().lsec_test_predict_form(FORM_FAMILIES.index(family) + 1, plan_kernel, k, rows, packet, block_size, out),
            "lsec_test_predict_form")
+    return _form(out)
+
+
+def predict_masked_form(plan_kernel: int, k: int, rows: int, packet: int = 0, block_size: int = 0) -> Form:
+    """Test hook (no GPU): the Form ("updmask") update_dev_masked_refs and update_dev_masked_rotated_refs launch for
+    a plan of kernel 1 or 2 with k columns and `rows` rows, asked of the functions the dispatch itself calls."""
+    out = (C.c_int * 8)()
+    _check(lib().lsec_test_predict_masked_form(plan_kernel, k, rows, packet, block_size, out),
+           "lsec_test_predict_masked_form")
     return _form(out)
 
 

@@ -17,6 +17,9 @@ lsec_locate_dev against lsec_check_dev on the same shapes, clean, corrupt and re
 python tools/kbench.py --update [--rounds R] [--reps N] [--pattern-codes rs63,rs164,cg63]
 lsec_update_dev against a device copy of the fresh chunk followed by lsec_encode_dev: see update_bench.
 
+python tools/kbench.py --update-masked [--rounds R] [--reps N] [--pattern-codes rs63,rs164,cg63]
+lsec_update_dev_masked against lsec_update_dev and the per-class calls it replaces: see update_masked_bench.
+
 python tools/kbench.py --rotated-scrub [--rounds R] [--reps N]
 lsec_check_dev_rotated / lsec_locate_dev_rotated over the devices of a rotated LUN against the unrotated
 calls over the same bytes: see rotated_scrub_bench.
@@ -549,6 +552,99 @@ def update_bench(a):
         torch.cuda.empty_cache()
 
 
+def update_masked_bench(a):
+    """The per-stripe-mask update beside lsec_update_dev, interleaved round by round on the same k+m buffers (one
+    per chunk, C = 1 MiB) and two buffers of fresh bytes that the k fresh refs alternate between:
+      (a) lsec_update_dev, LSEC_UPDATE_STORE, cols = {0}              its own min-max over the rounds is the band
+      (b) lsec_update_dev_masked, the same single bit in every stripe the cost of the per-tile mask read
+      (c) lsec_update_dev_masked, masks 1 << (s mod k), one launch    a different chunk in every stripe
+      (d) what a caller does today for (c): k lsec_update_dev calls over stride-stretched refs
+      (e) lsec_update_dev_masked, bit 0 in 1 % of the stripes         the cost of visiting tiles only to skip them
+    All with the store flag.  Every case is checked before timing: the data chunks named by the masks hold the fresh
+    bytes and the parity is lsec_encode_dev's for the data as it then stands."""
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    C, N = 1 << 20, a.pattern_stripes
+    for name in a.pattern_codes.split(","):
+        meth, k, m = CONFIGS[name][:3]
+        n = k + m
+        plan = L.Plan.for_chunk(meth, k, m, C)
+        bufs = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(n)]
+        fresh = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(2)]
+        refs = [(b.data_ptr(), C) for b in bufs]
+        fresh_refs = [(fresh[j % 2].data_ptr(), C) for j in range(k)]
+        one = [refs[i] if i == 0 or i >= k else (0, 0) for i in range(n)]
+        s_idx = torch.arange(N, dtype=torch.int64, device=dev)
+        masks = {"b": torch.ones(N, dtype=torch.int64, device=dev),
+                 "c": torch.ones(N, dtype=torch.int64, device=dev) << (s_idx % k),
+                 "e": (s_idx % 100 == 0).to(torch.int64)}
+
+        def classes():
+            for j in range(k):  # the stripes s = j mod k: chunk j changes
+                cnt = (N - j + k - 1) // k
+                if cnt > 0:
+                    cls = [(refs[i][0] + j * C, k * C) if i == j or i >= k else (0, 0) for i in range(n)]
+                    plan.update_dev_refs(cls, cnt, C, [j], [(fresh_refs[j][0] + j * C, k * C)], True, sh)
+
+        runs = {"a": lambda: plan.update_dev_refs(one, N, C, [0], fresh_refs[:1], True, sh),
+                "b": lambda: plan.update_dev_masked_refs(refs, N, C, masks["b"].data_ptr(), fresh_refs, True, sh),
+                "c": lambda: plan.update_dev_masked_refs(refs, N, C, masks["c"].data_ptr(), fresh_refs, True, sh),
+                "d": classes,
+                "e": lambda: plan.update_dev_masked_refs(refs, N, C, masks["e"].data_ptr(), fresh_refs, True, sh)}
+        # results first: the changed chunks hold the fresh bytes, the parity is the re-encode's
+        want = [torch.empty((N, C), dtype=torch.uint8, device=dev) for _ in range(m)]
+        for key in runs:
+            for b in bufs[:k]:
+                b.add_(1)  # old bytes that differ from the fresh ones again (five cases: no byte comes back round)
+            plan.encode_dev_refs(refs, N, C, sh)  # consistent stripes
+            runs[key]()
+            torch.cuda.synchronize()
+            word = masks["c" if key == "d" else "b" if key == "a" else key]
+            for j in range(k):
+                hit = (word >> j & 1).bool()
+                assert torch.equal(bufs[j][hit], fresh[j % 2][hit]), f"({key}) data chunk {j}"
+                if not hit.all():  # every stripe outside the mask still differs from the fresh bytes
+                    assert (bufs[j][~hit] != fresh[j % 2][~hit]).any(dim=1).all(), f"({key}) data chunk {j} was stored"
+            plan.encode_dev_refs(refs[:k] + [(w.data_ptr(), C) for w in want], N, C, sh)
+            torch.cuda.synchronize()
+            for r in range(m):
+                assert torch.equal(bufs[k + r], want[r]), f"({key}) parity row {r} differs from the re-encode"
+        del want
+        torch.cuda.empty_cache()
+        times = {key: [] for key in runs}
+        for _ in range(a.rounds):
+            for key, fn in runs.items():
+                fn()  # warm
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.reps):
+                    fn()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[key].append(e0.elapsed_time(e1) / a.reps)
+        lo, hi = min(times["a"]), max(times["a"])
+        what = {"a": "lsec_update_dev, store, c = 1", "b": "masked, bit 0 in every stripe", "c": "masked, 1 << (s mod k)",
+                "d": f"{k} lsec_update_dev calls for (c)", "e": "masked, bit 0 in 1 % of stripes"}
+        per = 2 + m + m + 1  # chunk transfers of a stripe that changes in one chunk
+        touched = {key: N for key in runs}
+        touched["e"] = int(masks["e"].sum().item())
+        med = {key: sorted(ts)[len(ts) // 2] for key, ts in times.items()}
+        for key, ts in times.items():
+            db = per * C * touched[key]
+            band = "" if key == "a" else ("  inside (a)'s band" if lo <= med[key] <= hi else
+                                          f"  {'below' if med[key] < lo else 'above'} (a)'s band by "
+                                          f"{abs(med[key] - (lo if med[key] < lo else hi)) / med[key]:.2%}")
+            print(f"{name} N={N} C={C} ({key}) {what[key]:32s} median {med[key]:7.3f} ms  min {min(ts):7.3f}  max {max(ts):7.3f}  "
+                  f"{touched[key]:5d} stripes {db / med[key] / 1e6:7.1f} GB/s ({db / med[key] / 8e9:5.1%} of 8 TB/s){band}", flush=True)
+        print(f"{name} (a) band: {lo:.3f} .. {hi:.3f} ms ({(hi - lo) / lo:.2%}) over {a.rounds} rounds of {a.reps} launches; "
+              f"(b)/(a) = {med['b'] / med['a']:.3f}, (c)/(a) = {med['c'] / med['a']:.3f}, (d)/(c) = {med['d'] / med['c']:.3f}, "
+              f"(e)/(a) = {med['e'] / med['a']:.3f}", flush=True)
+        del bufs, fresh, masks
+        plan.close()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data-gib", type=float, default=24.0)
@@ -580,7 +676,13 @@ def main():
     ap.add_argument("--update", action="store_true",
                     help="time lsec_update_dev against a device copy + lsec_encode_dev (update_bench; "
                          "--pattern-stripes, --pattern-codes) and exit")
+    ap.add_argument("--update-masked", action="store_true",
+                    help="time lsec_update_dev_masked against lsec_update_dev and the per-class calls it replaces "
+                         "(update_masked_bench; --pattern-stripes, --pattern-codes) and exit")
     a = ap.parse_args()
+    if a.update_masked:
+        update_masked_bench(a)
+        return
     if a.update:
         update_bench(a)
         return
