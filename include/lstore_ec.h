@@ -334,6 +334,9 @@ int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
  * - One column list per call.  Stripes that change in different chunks take
  *   lsec_update_dev_masked, below: one 64-bit word per stripe names its changed chunks, in one
  *   launch.  The form over the physical devices of a rotated LUN is lsec_update_dev_rotated, below.
+ * - This call and lsec_update_dev_rotated leave the stripes' magics to the caller.  The masked
+ *   calls have a form that keeps them current in the same pass (lsec_update_magic_dev_masked,
+ *   below); one word repeated for every stripe expresses any column list.
  * - Every refusal -- plan kernels 3-5; k or m out of range; a NULL shards, cols or fresh; an empty
  *   list; an id < 0, an id >= k (a parity id) or a duplicate; more than k ids; unknown flag bits; a
  *   misaligned base, or a misaligned stride with nstripes > 1; a bad block_size; a negative
@@ -460,6 +463,58 @@ int lsec_update_dev_masked_rotated(lio_erasure_plan_t *plan, const lsec_shard_t 
                                    long long block_size, int n_shift, long long first_stripe,
                                    const unsigned long long *stripe_cols,
                                    const lsec_shard_t *fresh, int flags, void *stream);
+
+/* The masked parity update that also keeps the stripes' magics current, one pass:
+ * lsec_update_dev_masked / lsec_update_dev_masked_rotated, and magic[s] -- the 4-byte adler32 LStore
+ * stores in front of every chunk of stripe s (below) -- moved from the old stripe's to the new
+ * stripe's.  A partial-stripe write changes the magic, and the only other way to the new one is
+ * lsec_stripe_magic_dev over all k+m chunks behind the update: a second pass over exactly the chunks
+ * the update does not read and that need not be on the device.  adler32's two halves are sums over
+ * byte positions, so the write moves them by sums over the changed positions alone, and the update's
+ * kernels hold those bytes -- old and fresh data, parity before and after -- in registers.  Purely
+ * additive too: the version stays 3, a caller detects the calls by their symbols.
+ *
+ * Everything lsec_update_dev_masked and lsec_update_dev_masked_rotated specify holds unchanged: the
+ * arguments, the enabled columns and the effective mask, LSEC_UPDATE_STORE, the bytes left in the
+ * stripes, the layout rules and the limits (plan kernels 1 and 2, k <= 64, 1 <= m <= 8), and that
+ * nstripes == 0 touches no GPU.
+ * - `magic` is device memory, 4*nstripes bytes: word s is 4 little-endian bytes, as
+ *   lsec_stripe_magic_dev writes them.  No alignment requirement, as for that call.  It is read and
+ *   written; it must not overlap shards / devs, fresh or stripe_cols.  NULL with nstripes > 0 is
+ *   refused, NULL with nstripes == 0 is fine.
+ * - Effect, for a stripe whose effective mask is not 0, with A_in / B_in the low / high 16 bits of
+ *   magic[s] on entry: each half comes out as (in + d) mod 65521, d taken over the changed data
+ *   chunks and the m parity chunks: dA = sum (new_p - old_p), dB = sum (L - p)(new_p - old_p) over
+ *   their byte positions p in the LOGICAL stripe -- chunk j at j*block_size, parity row r at
+ *   (k+r)*block_size, L = (k+m)*block_size.  Rotation does not enter: the magic is over logical
+ *   order, as lsec_segment_write computes it.  So if magic[s] was adler32(old stripe) it comes out
+ *   as adler32(new stripe), bit-exact with zlib, whether or not the stripe is consistent; and a half
+ *   that was off by d stays off by d: a wrong magic is neither healed nor hidden, the counterpart of
+ *   "any stripe keeps its syndrome".
+ * - A half of 65521 or more can never be an adler32 half.  It is not folded into a valid one: that
+ *   half comes out as 0xFFFF.  Invalid stays invalid.
+ * - The magic word of a stripe whose effective mask is 0 is neither read nor written, whatever it
+ *   holds.
+ * - With or without LSEC_UPDATE_STORE the magic is that of the stripe with the chunks replaced;
+ *   without the flag the caller puts the fresh bytes in place itself, as for the plain calls.
+ * - Scratch: the per-stripe accumulators, 16 bytes per stripe, come from the stream-ordered
+ *   allocator (hipMallocAsync on `stream`) and go back to it on the stream, exactly as
+ *   lsec_encode_magic_dev's do.  Nothing is uploaded: the masks are read where they lie.
+ * - Only the masked family has this form.  A caller of lsec_update_dev / lsec_update_dev_rotated
+ *   gets it by passing the same word for every stripe (bit cols[i] set, fresh[cols[i]] = its
+ *   fresh[i]).
+ * - Every refusal -- those of the masked calls, in their order, and a NULL magic with nstripes > 0,
+ *   behind the stripe_cols ones -- returns -1 with a message for lsec_last_error that names this
+ *   call and the limit, and nothing is enqueued.  There is no fallback.
+ * Enqueued on `stream`; return without synchronising.  0 / -1. */
+int lsec_update_magic_dev_masked(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
+                                 long long block_size, const unsigned long long *stripe_cols,
+                                 const lsec_shard_t *fresh, int flags, void *magic, void *stream);
+
+int lsec_update_magic_dev_masked_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                                         long long block_size, int n_shift, long long first_stripe,
+                                         const unsigned long long *stripe_cols, const lsec_shard_t *fresh,
+                                         int flags, void *magic, void *stream);
 
 /* Per-stripe "magic": the 4-byte little-endian zlib adler32 over the concatenation of a
  * stripe's k+m chunks that LStore's erasure segment stores in front of every chunk

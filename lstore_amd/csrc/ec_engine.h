@@ -238,6 +238,12 @@ int update_dev_masked(PlanExt *e, const lsec_shard_t *sh, int nstripes, long lon
 int update_dev_masked_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift,
                               long long first_stripe, const unsigned long long *stripe_cols, const lsec_shard_t *fresh,
                               int flags, hipStream_t st);
+// the same, and magic[s] (4 bytes per stripe, device memory, in and out) moved from the old stripe's adler32 to the new one's
+int update_magic_dev_masked(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const unsigned long long *stripe_cols,
+                            const lsec_shard_t *fresh, int flags, uint8_t *magic, hipStream_t st);
+int update_magic_dev_masked_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift,
+                                    long long first_stripe, const unsigned long long *stripe_cols, const lsec_shard_t *fresh,
+                                    int flags, uint8_t *magic, hipStream_t st);
 // stripes that do not share an erasure pattern, one launch per 32-bit range of tiles
 int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift, PatternTable &tab);
 uint32_t pattern_rot0(int n, int n_shift, long long first_stripe);

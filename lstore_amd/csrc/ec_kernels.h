@@ -389,6 +389,33 @@ static_assert(sizeof(UpdateMaskArgs) < 4096, "UpdateMaskArgs: under the 4 KiB of
 hipError_t launch_update_masked_bytewise(const UpdateMaskArgs &a, hipStream_t stream);
 hipError_t launch_update_masked_bitsliced(const UpdateMaskArgs &a, hipStream_t stream, int dw_pref = 0);
 
+// The masked update that also keeps the stripes' adler32 magics current (lsec_update_magic_dev_masked /
+// _masked_rotated).  A write changes the magic's two halves by sums over the changed positions alone,
+//   dA = sum (new_p - old_p),  dB = sum (L - p)(new_p - old_p)   (mod 65521),
+// and those positions are the changed data chunks and the R parity rows: the bytes the update's lanes
+// hold on both sides anyway.  The MG kernels (k_updmagic_*: the masked update's tile bodies under
+// `if constexpr (MG)`) add each tile's dA, dB, reduced into [0, 65521), to magic_acc[2s], [2s + 1]
+// (zeroed before the first launch), at the positions of the LOGICAL stripe: chunk j at j * size, row r
+// at (K + r) * size.  launch_update_magic_finalize folds them into the magic words.  The struct
+// derives from UpdateMaskArgs, whose layout -- and with it every non-MG kernel -- stays as it is.
+struct UpdateMaskMagicArgs : UpdateMaskArgs {
+  unsigned long long *magic_acc;  // 2 per stripe of this launch (8-byte aligned device memory)
+};
+static_assert(sizeof(UpdateMaskMagicArgs) == sizeof(UpdateMaskArgs) + 8, "UpdateMaskMagicArgs layout");
+static_assert(sizeof(UpdateMaskMagicArgs) < 4096, "UpdateMaskMagicArgs: under the 4 KiB of kernel arguments");
+
+// As launch_update_masked_*, and magic_acc != NULL.  The launch shapes are updmagic_bytewise_form and
+// update_magic_lane_dwords.
+hipError_t launch_update_magic_bytewise(const UpdateMaskMagicArgs &a, hipStream_t stream);
+hipError_t launch_update_magic_bitsliced(const UpdateMaskMagicArgs &a, hipStream_t stream, int dw_pref = 0);
+// One launch per call, behind the tile launches: for every stripe s < nstripes of the whole call whose
+// effective mask stripe_cols[s] & allowed is not 0, the 4 little-endian bytes at magic + 4s (no
+// alignment) are read, each 16-bit half h becomes (h + acc) mod 65521 -- or 0xFFFF where h >= 65521,
+// which no adler32 half can be: invalid stays invalid -- and 4 bytes are written.  The word of a
+// stripe whose effective mask is 0 is neither read nor written.
+hipError_t launch_update_magic_finalize(const unsigned long long *acc, const unsigned long long *stripe_cols,
+                                        unsigned long long allowed, int nstripes, uint8_t *magic, hipStream_t stream);
+
 // Which kernel ran (test hooks lsec_test_launch_record / lsec_test_predict_forms, ec_plan.cpp).  The
 // check, locate, patterned, rotated and update calls are families of separately compiled kernels; a form
 // names one of them by its template arguments: bytewise R, KC (0: K at run time), IT, VW, BF; or
@@ -396,7 +423,7 @@ hipError_t launch_update_masked_bitsliced(const UpdateMaskArgs &a, hipStream_t s
 // functions record the form at the one place where the template arguments are known; the record
 // is the calling thread's, holds the launches since launch_record_reset() in order (the engine
 // resets it on entry to each of those calls) and costs a few host stores per launch.
-enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask };
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic };
 struct LaunchForm {
   int family, sliced, R, KC, IT, VW, BF, DW;
 };
@@ -410,6 +437,8 @@ int launch_record(LaunchForm *out, int max);  // -> launches recorded; out[0 .. 
 bool predict_launch(int family, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // the same for the masked update (kFormUpdMask), which predict_launch does not answer for
 bool predict_masked_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
+// and for the masked update with the magic (kFormUpdMaskMagic)
+bool predict_masked_magic_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // the K with fixed-K forms (LSEC_FIXED_K), ascending -> how many there are; out[0 .. min(that, max))
 int fixed_k_list(int *out, int max);
 

@@ -632,6 +632,31 @@ hipError_t launch_update_masked_bitsliced(const UpdateMaskArgs &a, hipStream_t s
   return by_r(a.R, [&](auto r) { return dispatch_updmask_bitsliced<decltype(r)::value>(a, st, grid, dw); });
 }
 
+// ------------------------------------------------------------------ the masked update that keeps the stripe magics
+namespace {
+// dwords per lane of a bit-sliced masked update with the magic (more than kUpdMagicWideRows rows: one)
+int update_magic_lane_dwords(int R, int dw_pref, int packet) { return lane_dwords(R <= kUpdMagicWideRows ? dw_pref : 1, packet); }
+}  // namespace
+
+hipError_t launch_update_magic_bytewise(const UpdateMaskMagicArgs &a, hipStream_t st) {
+  if (!update_masked_args_ok(a) || !a.magic_acc) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const BwForm f = updmagic_bytewise_form(a.R);
+  const int grid = tile_grid(BwShape{f.it, f.vw, f.bf}.tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_updmagic_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_update_magic_bitsliced(const UpdateMaskMagicArgs &a, hipStream_t st, int dw_pref) {
+  if (!update_masked_args_ok(a) || !a.magic_acc || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int dw = update_magic_lane_dwords(a.R, dw_pref, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_updmagic_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+}
+
 hipError_t launch_encode_rot_bytewise(const EncodeRotArgs &a, hipStream_t st) {
   if (!encode_rot_args_ok(a)) return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
@@ -702,6 +727,18 @@ bool predict_masked_launch(bool sliced, int K, int R, int packet, int dw_pref, L
   return true;
 }
 
+bool predict_masked_magic_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out) {
+  if (K < 1 || K > kMaxK || R < 1 || R > 8) return false;
+  if (sliced) {
+    if (packet <= 0 || packet % 4 != 0) return false;
+    *out = LaunchForm{kFormUpdMaskMagic, 1, R, 0, 0, 0, 0, update_magic_lane_dwords(R, dw_pref, packet)};
+    return true;
+  }
+  const BwForm f = updmagic_bytewise_form(R);
+  *out = LaunchForm{kFormUpdMaskMagic, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
+  return true;
+}
+
 int fixed_k_list(int *out, int max) {
   int n = 0;
 #define LSEC_LIST_K(KK)     \
@@ -762,6 +799,29 @@ __global__ void k_magic_finalize(const unsigned long long *acc, int nstripes, ui
   magic[4 * s + 1] = (m >> 8) & 255;
   magic[4 * s + 2] = (m >> 16) & 255;
   magic[4 * s + 3] = m >> 24;
+}
+
+// The masked update's magics (launch_update_magic_finalize, ec_kernels.h): acc holds each stripe's change
+// of the two halves, a sum of per-tile values in [0, M).  A half that is no adler32 half on entry
+// (>= M) comes out as 0xFFFF, never folded into a valid one.
+__device__ __forceinline__ uint32_t magic_half_moved(uint32_t h, unsigned long long d) {
+  return h >= kAdlerMod ? 0xFFFFu : static_cast<uint32_t>((h + d % kAdlerMod) % kAdlerMod);
+}
+
+__global__ void k_update_magic_finalize(const unsigned long long *acc, const unsigned long long *stripe_cols,
+                                        unsigned long long allowed, int nstripes, uint8_t *magic) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nstripes) return;
+  if ((stripe_cols[s] & allowed) == 0) return;  // nothing of this stripe changed: its word is neither read nor written
+  uint8_t *w = magic + 4ll * s;
+  const uint32_t in = w[0] | (w[1] << 8) | (w[2] << 16) | (static_cast<uint32_t>(w[3]) << 24);
+  const uint32_t A = magic_half_moved(in & 0xFFFFu, acc[2 * s]);
+  const uint32_t B = magic_half_moved(in >> 16, acc[2 * s + 1]);
+  const uint32_t m = (B << 16) | A;
+  w[0] = m & 255;
+  w[1] = (m >> 8) & 255;
+  w[2] = (m >> 16) & 255;
+  w[3] = m >> 24;
 }
 
 // one block per (stripe, 8 KiB column tile): OR of a^b over every pair, one flag store per
@@ -1067,6 +1127,14 @@ hipError_t launch_magic_finalize(const unsigned long long *acc, int nstripes, in
   if (nstripes <= 0) return hipSuccess;
   return launch_kernel(&k_magic_finalize, dim3((nstripes + 255) / 256), dim3(256), st, acc, nstripes,
                      static_cast<uint64_t>(total_len), magic);
+}
+
+hipError_t launch_update_magic_finalize(const unsigned long long *acc, const unsigned long long *stripe_cols,
+                                        unsigned long long allowed, int nstripes, uint8_t *magic, hipStream_t st) {
+  if (!acc || !stripe_cols || !magic) return hipErrorInvalidValue;
+  if (nstripes <= 0) return hipSuccess;
+  return launch_kernel(&k_update_magic_finalize, dim3((nstripes + 255) / 256), dim3(256), st, acc, stripe_cols, allowed,
+                       nstripes, magic);
 }
 
 }  // namespace lsec

@@ -415,13 +415,41 @@ __device__ __forceinline__ void ml_add(MagicLane &m, const typename VecT<VW>::ty
   m.js += sh * sum;
 }
 
+// The same sums taken away: the bytes a write replaces (the masked update's magic, below).
+template <int NX, int VW>
+__device__ __forceinline__ void ml_sub(MagicLane &m, const typename VecT<VW>::type (&e)[NX], uint32_t sh) {
+  MagicLane t;
+  ml_add<NX, VW>(t, e, sh);
+  m.a -= t.a;
+  m.js -= t.js;
+  m.xs -= t.xs;
+  m.w -= t.w;
+}
+
+// A tile's change of a stripe magic that exists already (lsec_update_magic_dev_masked): the lane has added
+// the bytes the write leaves (ml_add) and taken away the ones it replaces (ml_sub), in wrapping 32-bit
+// arithmetic, so its four sums read back as signed are new minus old.  Their true magnitudes are far
+// below 2^31: at most 72 shards x 128 bytes of a lane x 255, times a shard index of at most 71.  The
+// signed tile sums go into [0, M) before the block sum, so the per-stripe accumulators only ever grow.
+__device__ __forceinline__ void ml_commit_delta(const MagicLane &m, unsigned long long *acc, uint32_t s, int nsh, int64_t C,
+                                                int64_t off, int64_t X, uint32_t *red) {
+  const int64_t A = static_cast<int32_t>(m.a);
+  const int64_t B = nsh * C * A - (C * static_cast<int32_t>(m.js) + off * A + X * static_cast<int32_t>(m.xs) +
+                                   static_cast<int32_t>(m.w));
+  int64_t am = A % static_cast<int64_t>(kAdlerMod), bm = B % static_cast<int64_t>(kAdlerMod);
+  if (am < 0) am += kAdlerMod;
+  if (bm < 0) bm += kAdlerMod;
+  magic_commit(acc, s, static_cast<uint64_t>(am), static_cast<uint64_t>(bm), red);
+}
+
 // fused stripe magic (bytewise kernel): lane words are the IT steps kStep bytes apart
 template <int R, int IT, int VW>
 __device__ __forceinline__ void bw_magic(MagicLane &ml, const typename VecT<VW>::type (*v)[IT], int nv, int j0) {
   for (int jj = 0; jj < nv; ++jj) ml_add<IT, VW>(ml, v[jj], static_cast<uint32_t>(j0 + jj));
 }
 
-template <int R, int IT, int VW>
+// (NEG: taken away, the stored rows an update is about to replace)
+template <int R, int IT, int VW, bool NEG = false>
 __device__ __forceinline__ void bw_magic_out(MagicLane &ml, int K, const typename VecT<VW>::type (&acc)[IT][R]) {
   typedef typename VecT<VW>::type V;
 #pragma unroll
@@ -429,7 +457,8 @@ __device__ __forceinline__ void bw_magic_out(MagicLane &ml, int K, const typenam
     V o[IT];
 #pragma unroll
     for (int it = 0; it < IT; ++it) o[it] = acc[it][r];
-    ml_add<IT, VW>(ml, o, static_cast<uint32_t>(K + r));
+    if constexpr (NEG) ml_sub<IT, VW>(ml, o, static_cast<uint32_t>(K + r));
+    else ml_add<IT, VW>(ml, o, static_cast<uint32_t>(K + r));
   }
 }
 
@@ -2590,8 +2619,19 @@ struct UpdMaskShards {
 };
 
 // BF as k_gf8_bytewise: the branch-free coefficient path, or per-cell branches (R = 1).
-template <int R, int IT, int VW, bool BF>
-__device__ __forceinline__ void updmask_bytewise_tiles(const UpdateMaskArgs &a) {
+//
+// MG (lsec_update_magic_dev_masked / _rotated): the tile also sums what the write does to the stripe's
+// adler32 magic.  The changed positions are the changed data chunks and the R parity rows, and the lane
+// holds both sides of every one of them: the stored parity units as loaded and the accumulators as
+// stored, old_j and fresh_j before they are XORed.  One MagicLane takes new minus old (ml_add / ml_sub)
+// at the LOGICAL shard index, j or K + r -- the rotation moves addresses, not positions -- and the
+// tile commits once through block_sum into macc[2s], macc[2s + 1] (ml_commit_delta).  block_sum has
+// barriers: every lane of the workgroup reaches it.  The mask == 0 exit is uniform; units past the end
+// of a ragged tile read as zero and add nothing.  red: kBlock / 64 words of LDS.  Without MG macc and
+// red are not looked at and the code is the plain masked update's.
+template <int R, int IT, int VW, bool BF, bool MG = false>
+__device__ __forceinline__ void updmask_bytewise_tiles(const UpdateMaskArgs &a, unsigned long long *macc = nullptr,
+                                                       uint32_t *red = nullptr) {
   typedef typename VecT<VW>::type V;
   constexpr int kStep = BwTile<IT, VW>::kStep;
   constexpr int kTile = BwTile<IT, VW>::kBytes;
@@ -2610,6 +2650,7 @@ __device__ __forceinline__ void updmask_bytewise_tiles(const UpdateMaskArgs &a) 
     const UpdMaskShards sh(a, s);
     const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
     const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
+    MagicLane ml;  // new minus old of the stripe magic (MG only)
 
     V acc[IT][R];
     if (full) {
@@ -2620,6 +2661,7 @@ __device__ __forceinline__ void updmask_bytewise_tiles(const UpdateMaskArgs &a) 
 #pragma unroll
         for (int it = 0; it < IT; ++it) acc[it][r] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
       }
+      if constexpr (MG) bw_magic_out<R, IT, VW, true>(ml, K, acc);
       do {
         const uint32_t j = static_cast<uint32_t>(__builtin_ctzll(mask));
         mask &= mask - 1;
@@ -2634,6 +2676,10 @@ __device__ __forceinline__ void updmask_bytewise_tiles(const UpdateMaskArgs &a) 
         if (store) {
 #pragma unroll
           for (int it = 0; it < IT; ++it) put_nt<false, V>(po + it * kStep, f[it]);
+        }
+        if constexpr (MG) {
+          ml_sub<IT, VW>(ml, d, j);
+          ml_add<IT, VW>(ml, f, j);
         }
 #pragma unroll
         for (int it = 0; it < IT; ++it) d[it] ^= f[it];
@@ -2655,6 +2701,7 @@ __device__ __forceinline__ void updmask_bytewise_tiles(const UpdateMaskArgs &a) 
 #pragma unroll
         for (int it = 0; it < IT; ++it) acc[it][r] = load_ragged<VW>(q, off0 + it * kStep, C);
       }
+      if constexpr (MG) bw_magic_out<R, IT, VW, true>(ml, K, acc);
       do {
         const uint32_t j = static_cast<uint32_t>(__builtin_ctzll(mask));
         mask &= mask - 1;
@@ -2670,6 +2717,10 @@ __device__ __forceinline__ void updmask_bytewise_tiles(const UpdateMaskArgs &a) 
 #pragma unroll
           for (int it = 0; it < IT; ++it) store_ragged<false, VW>(po, off0 + it * kStep, C, f[it]);
         }
+        if constexpr (MG) {
+          ml_sub<IT, VW>(ml, d, j);
+          ml_add<IT, VW>(ml, f, j);
+        }
 #pragma unroll
         for (int it = 0; it < IT; ++it) d[it] ^= f[it];
         bw_acc1<R, IT, VW, BF, false>(acc, d, cells, K, static_cast<int>(j));
@@ -2682,6 +2733,10 @@ __device__ __forceinline__ void updmask_bytewise_tiles(const UpdateMaskArgs &a) 
         for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
       }
     }
+    if constexpr (MG) {
+      bw_magic_out<R, IT, VW>(ml, K, acc);
+      ml_commit_delta(ml, macc, s, K + R, C, off0, kStep, red);
+    }
   }, a.tile_phase);
 }
 
@@ -2690,10 +2745,19 @@ __global__ __launch_bounds__(kBlock) void k_updmask_bytewise(UpdateMaskArgs a) {
   updmask_bytewise_tiles<R, IT, VW, BF>(a);
 }
 
+template <int R, int IT, int VW, bool BF>
+__global__ __launch_bounds__(kBlock) void k_updmagic_bytewise(UpdateMaskMagicArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  updmask_bytewise_tiles<R, IT, VW, BF, true>(a, a.magic_acc, red);
+}
+
 // k_upd_bitsliced's lanes and doubling loop under the stripe's mask.  The mask is looked at first;
-// lanes past the end of a ragged last tile leave the tile body behind that.
-template <int R, int DW>
-__global__ __launch_bounds__(kBlock) void k_updmask_bitsliced(UpdateMaskArgs a) {
+// lanes past the end of a ragged last tile leave the tile body behind that.  MG as in
+// updmask_bytewise_tiles: those lanes then skip the loads and stores, but still join the tile's
+// reduction (as k_gf8_bitsliced's do).
+template <int R, int DW, bool MG = false>
+__device__ __forceinline__ void updmask_bitsliced_tiles(const UpdateMaskArgs &a, unsigned long long *macc = nullptr,
+                                                        uint32_t *red = nullptr) {
   typedef typename VecT<DW>::type V;
   const int K = a.K;
   const uint32_t P = static_cast<uint32_t>(a.packet);
@@ -2710,55 +2774,77 @@ __global__ __launch_bounds__(kBlock) void k_updmask_bitsliced(UpdateMaskArgs a) 
     if (mask == 0) return;  // nothing of this stripe changes: neither read nor written
     const UpdMaskShards sh(a, s);
     const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * (4 * DW);
-    if (colb >= col_bytes) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
+    const bool valid = colb < col_bytes;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
+    if (!MG && !valid) return;
     const uint32_t sp = colb / P;
     const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+    MagicLane ml;  // new minus old of the stripe magic (MG only)
 
-    V acc[R][8];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const ShardRef par = sh.par(r);
-      const uint64_t q = par.base + s * par.stride + off;
-#pragma unroll
-      for (int x = 0; x < 8; ++x) acc[r][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
-    }
-    do {
-      const uint32_t j = static_cast<uint32_t>(__builtin_ctzll(mask));
-      mask &= mask - 1;
-      const ShardRef old = sh.old(j), fresh = a.fresh[j];
-      const uint64_t po = old.base + s * old.stride + off, pf = fresh.base + s * fresh.stride + off;
-      V e[8], f[8];
-#pragma unroll
-      for (int x = 0; x < 8; ++x) {
-        e[x] = __builtin_nontemporal_load(gptr<V>(po + x * P));
-        f[x] = __builtin_nontemporal_load(gptr<V>(pf + x * P));
-      }
-      if (store) {
-#pragma unroll
-        for (int x = 0; x < 8; ++x) put_nt<false, V>(po + x * P, f[x]);
-      }
-#pragma unroll
-      for (int x = 0; x < 8; ++x) e[x] ^= f[x];
-      uint32_t c[R];
-      uint32_t cm = 0;  // bits used by any row: no doublings past the highest one
+    if (!MG || valid) {
+      V acc[R][8];
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        c[r] = cells[r * K + j].coef;
-        cm |= c[r];
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) acc[r][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
+        if constexpr (MG) ml_sub<8, DW>(ml, acc[r], static_cast<uint32_t>(K + r));
       }
-      gf8_sliced_mul_acc<0>(acc, e, c, cm);
-    } while (mask);
-    // the stores go to the addresses the parity loads came from, formed again (k_upd_bitsliced)
-    int64_t off_st = off;
-    asm volatile("" : "+v"(off_st));
+      do {
+        const uint32_t j = static_cast<uint32_t>(__builtin_ctzll(mask));
+        mask &= mask - 1;
+        const ShardRef old = sh.old(j), fresh = a.fresh[j];
+        const uint64_t po = old.base + s * old.stride + off, pf = fresh.base + s * fresh.stride + off;
+        V e[8], f[8];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const ShardRef par = sh.par(r);
-      const uint64_t q = par.base + s * par.stride + off_st;
+        for (int x = 0; x < 8; ++x) {
+          e[x] = __builtin_nontemporal_load(gptr<V>(po + x * P));
+          f[x] = __builtin_nontemporal_load(gptr<V>(pf + x * P));
+        }
+        if (store) {
 #pragma unroll
-      for (int x = 0; x < 8; ++x) put_nt<false, V>(q + x * P, acc[r][x]);
+          for (int x = 0; x < 8; ++x) put_nt<false, V>(po + x * P, f[x]);
+        }
+        if constexpr (MG) {
+          ml_sub<8, DW>(ml, e, j);
+          ml_add<8, DW>(ml, f, j);
+        }
+#pragma unroll
+        for (int x = 0; x < 8; ++x) e[x] ^= f[x];
+        uint32_t c[R];
+        uint32_t cm = 0;  // bits used by any row: no doublings past the highest one
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          c[r] = cells[r * K + j].coef;
+          cm |= c[r];
+        }
+        gf8_sliced_mul_acc<0>(acc, e, c, cm);
+      } while (mask);
+      // the stores go to the addresses the parity loads came from, formed again (k_upd_bitsliced)
+      int64_t off_st = off;
+      asm volatile("" : "+v"(off_st));
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off_st;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) put_nt<false, V>(q + x * P, acc[r][x]);
+        if constexpr (MG) ml_add<8, DW>(ml, acc[r], static_cast<uint32_t>(K + r));
+      }
     }
+    if constexpr (MG) ml_commit_delta(ml, macc, s, K + R, a.size, off, P, red);
   }, a.tile_phase);
+}
+
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_updmask_bitsliced(UpdateMaskArgs a) {
+  updmask_bitsliced_tiles<R, DW>(a);
+}
+
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_updmagic_bitsliced(UpdateMaskMagicArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  updmask_bitsliced_tiles<R, DW, true>(a, a.magic_acc, red);
 }
 
 // The forms (DESIGN.md 3.6 has their registers): the update's, which depend on R alone.
@@ -2794,6 +2880,43 @@ hipError_t dispatch_updmask_bitsliced(const UpdateMaskArgs &a, hipStream_t st, i
 #ifndef LSEC_INSTANTIATING_UPDMASK
 LSEC_DECLARE_UPDMASK_R(1) LSEC_DECLARE_UPDMASK_R(2) LSEC_DECLARE_UPDMASK_R(3) LSEC_DECLARE_UPDMASK_R(4)
 LSEC_DECLARE_UPDMASK_R(5) LSEC_DECLARE_UPDMASK_R(6) LSEC_DECLARE_UPDMASK_R(7) LSEC_DECLARE_UPDMASK_R(8)
+#endif
+
+// The MG forms (lsec_update_magic_dev_masked / _rotated; DESIGN.md 3.6 has their registers): the masked
+// update's own.  None of them uses scratch at those shapes -- the widest, <4, 4>, takes 244 VGPRs -- so
+// they were kept; constants of their own, so that one family can move without the other.
+constexpr BwForm updmagic_bytewise_form(int R) { return updmask_bytewise_form(R); }
+constexpr int kUpdMagicWideRows = kUpdMaskWideRows;
+
+template <int R>
+hipError_t dispatch_updmagic_bytewise(const UpdateMaskMagicArgs &a, hipStream_t st, int grid) {
+  constexpr BwForm f = updmagic_bytewise_form(R);
+  record_launch({kFormUpdMaskMagic, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0});
+  return launch_tiled(&k_updmagic_bytewise<R, f.it, f.vw, f.bf>, grid, st, a);
+}
+
+template <int R, int DW>
+hipError_t updmagic_bitsliced_kernel(const UpdateMaskMagicArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormUpdMaskMagic, 1, R, 0, 0, 0, 0, DW});
+  return launch_tiled(&k_updmagic_bitsliced<R, DW>, grid, st, a);
+}
+
+template <int R>
+hipError_t dispatch_updmagic_bitsliced(const UpdateMaskMagicArgs &a, hipStream_t st, int grid, int dw) {
+  if constexpr (R <= kUpdMagicWideRows) {
+    if (dw == 4) return updmagic_bitsliced_kernel<R, 4>(a, st, grid);
+    if (dw == 2) return updmagic_bitsliced_kernel<R, 2>(a, st, grid);
+  }
+  return dw == 1 ? updmagic_bitsliced_kernel<R, 1>(a, st, grid) : hipErrorInvalidValue;
+}
+
+// instantiated per R in ec_update_magic_inst.hip
+#define LSEC_DECLARE_UPDMAGIC_R(RR)                                                                         \
+  extern template hipError_t dispatch_updmagic_bytewise<RR>(const UpdateMaskMagicArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_updmagic_bitsliced<RR>(const UpdateMaskMagicArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_UPDMAGIC
+LSEC_DECLARE_UPDMAGIC_R(1) LSEC_DECLARE_UPDMAGIC_R(2) LSEC_DECLARE_UPDMAGIC_R(3) LSEC_DECLARE_UPDMAGIC_R(4)
+LSEC_DECLARE_UPDMAGIC_R(5) LSEC_DECLARE_UPDMAGIC_R(6) LSEC_DECLARE_UPDMAGIC_R(7) LSEC_DECLARE_UPDMAGIC_R(8)
 #endif
 
 // ------------------------------------------------------------------ encode over a rotated LUN

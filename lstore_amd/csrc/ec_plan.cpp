@@ -1261,6 +1261,8 @@ struct UpdateCall {
   bool rotated;
   int n_shift;
   long long first_stripe;
+  bool with_magic;  // the masked calls that keep the stripe magics (lsec_update_magic_dev_masked*)
+  uint8_t *magic;   //   their 4 * nstripes bytes of device memory, in and out
 };
 
 // the launches: one per 32-bit range of tiles, in the update's own launch shape for R rows
@@ -1391,6 +1393,12 @@ int update_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
 // rotation 0.  One validation ladder, in the order of the header's refusal list; it touches no
 // device.  Launches as enqueue_update's: per launch the mask pointer advances by s0 words and rot0
 // by (s0 mod n) * rot_step.  Nothing is allocated or uploaded per call.
+//
+// lsec_update_magic_dev_masked / _rotated are the same path with UpdateCall::with_magic: the MG kernels
+// (ec_kernels.h, UpdateMaskMagicArgs) in place of the plain ones, over 16 bytes per stripe of
+// accumulators from the stream-ordered allocator -- zeroed before the first launch, advancing by
+// 2 * s0 words per launch, freed on the stream -- and one finalize launch behind the tile launches
+// that takes the mask pointer and the enabled columns of the whole call.
 namespace {
 
 int update_masked_path(PlanExt *e, const UpdateCall &uc, const lsec_shard_t *sh, int nstripes, long long C,
@@ -1440,6 +1448,7 @@ int update_masked_path(PlanExt *e, const UpdateCall &uc, const lsec_shard_t *sh,
   if (nstripes > 0 && !stripe_cols) return fail("%s: stripe_cols is NULL", uc.name);
   if (nstripes > 0 && reinterpret_cast<uintptr_t>(stripe_cols) % 8 != 0)
     return fail("%s: stripe_cols %p is not a multiple of 8 bytes (64-bit words)", uc.name, static_cast<const void *>(stripe_cols));
+  if (uc.with_magic && nstripes > 0 && !uc.magic) return fail("%s: magic is NULL", uc.name);
   if (check_geometry(p, C)) {
     const std::string why = tl_err;  // the shared rule's message, behind the call's name
     return fail("%s: %s", uc.name, why.c_str());
@@ -1451,7 +1460,7 @@ int update_masked_path(PlanExt *e, const UpdateCall &uc, const lsec_shard_t *sh,
   const int R = encode_rows(e);
   if (R != m) return fail("%s: the plan encodes %d parity rows, m=%d", uc.name, R, m);
   if (C == 0) return 0;
-  lsec::UpdateMaskArgs a;
+  lsec::UpdateMaskMagicArgs a;  // (the plain call's launches take its UpdateMaskArgs part)
   std::memset(static_cast<void *>(&a), 0, sizeof(a));
   a.cells = static_cast<const CoefCell *>(cells);
   a.K = k;
@@ -1466,19 +1475,35 @@ int update_masked_path(PlanExt *e, const UpdateCall &uc, const lsec_shard_t *sh,
   // the encode's dwords per lane for this shape (0: its packet network, which the update has no form of)
   const bool sliced = kind == KBITSLICED;
   const int dw = sliced ? cauchy8_bitsliced_dw(k, m, C) : 0;
-  return for_launches(nstripes, launch_stripes(C, true), [&](long long s0, int ns) {
+  unsigned long long *acc = nullptr;  // with_magic: each stripe's change of the two halves
+  if (uc.with_magic) {
+    hipError_t err = hipMallocAsync(reinterpret_cast<void **>(&acc), 16ull * nstripes, st);
+    if (err == hipSuccess && (err = hipMemsetAsync(acc, 0, 16ull * nstripes, st)) != hipSuccess) (void)hipFreeAsync(acc, st);
+    if (err != hipSuccess) return fail("%s: the magic accumulators (%llu bytes): %s", uc.name, 16ull * nstripes, hipGetErrorString(err));
+  }
+  int rc = for_launches(nstripes, launch_stripes(C, true), [&](long long s0, int ns) {
     a.nstripes = ns;
     a.stripe_cols = stripe_cols + s0;
+    a.magic_acc = acc ? acc + 2 * s0 : nullptr;
     a.rot0 = rot0_from(rot0, a.rot_step, n, s0);
     for (int j = 0; j < k; ++j)
       if (allowed >> j & 1) a.fresh[j] = shard_from(fresh[j], s0);
     // (unrotated: the refs of the columns that are not enabled stay zero, and no kernel addresses them)
     for (int i = 0; i < n; ++i)
       if (uc.rotated || i >= k || (allowed >> i & 1)) a.sh[i] = shard_from(sh[i], s0);
-    const hipError_t err = sliced ? lsec::launch_update_masked_bitsliced(a, st, dw) : lsec::launch_update_masked_bytewise(a, st);
+    const hipError_t err = uc.with_magic ? (sliced ? lsec::launch_update_magic_bitsliced(a, st, dw) : lsec::launch_update_magic_bytewise(a, st))
+                                         : (sliced ? lsec::launch_update_masked_bitsliced(a, st, dw) : lsec::launch_update_masked_bytewise(a, st));
     if (err != hipSuccess) return fail("%s: kernel launch failed: %s", uc.name, hipGetErrorString(err));
     return 0;
   });
+  if (!uc.with_magic) return rc;
+  if (rc == 0) {
+    const hipError_t err = lsec::launch_update_magic_finalize(acc, stripe_cols, allowed, nstripes, uc.magic, st);
+    if (err != hipSuccess) rc = fail("%s: finalize launch failed: %s", uc.name, hipGetErrorString(err));
+  }
+  const hipError_t err = hipFreeAsync(acc, st);
+  if (err != hipSuccess && rc == 0) rc = fail("%s: freeing the magic accumulators: %s", uc.name, hipGetErrorString(err));
+  return rc;
 }
 
 }  // namespace
@@ -1493,6 +1518,19 @@ int update_dev_masked_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes
                               long long first_stripe, const unsigned long long *stripe_cols, const lsec_shard_t *fresh,
                               int flags, hipStream_t st) {
   const UpdateCall uc = {"lsec_update_dev_masked_rotated", true, n_shift, first_stripe};
+  return update_masked_path(e, uc, devs, nstripes, C, stripe_cols, fresh, flags, st);
+}
+
+int update_magic_dev_masked(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const unsigned long long *stripe_cols,
+                            const lsec_shard_t *fresh, int flags, uint8_t *magic, hipStream_t st) {
+  const UpdateCall uc = {"lsec_update_magic_dev_masked", false, 0, 0, true, magic};
+  return update_masked_path(e, uc, sh, nstripes, C, stripe_cols, fresh, flags, st);
+}
+
+int update_magic_dev_masked_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift,
+                                    long long first_stripe, const unsigned long long *stripe_cols, const lsec_shard_t *fresh,
+                                    int flags, uint8_t *magic, hipStream_t st) {
+  const UpdateCall uc = {"lsec_update_magic_dev_masked_rotated", true, n_shift, first_stripe, true, magic};
   return update_masked_path(e, uc, devs, nstripes, C, stripe_cols, fresh, flags, st);
 }
 
@@ -1981,6 +2019,22 @@ int lsec_test_predict_masked_form(int plan_kernel, int K, int R, int packet, lon
   lsec::LaunchForm f;
   if (!lsec::predict_masked_launch(sliced, K, R, packet, sliced ? cauchy8_bitsliced_dw(K, R, block_size) : 0, &f))
     return fail("lsec_test_predict_masked_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
+  const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
+  std::memcpy(form, v, sizeof(v));
+  return 0;
+}
+
+// Test hook, not in include/ (no GPU): lsec_test_predict_masked_form for the masked update that keeps the stripe
+// magics (family 11 of the launch record): the form lsec_update_magic_dev_masked and
+// lsec_update_magic_dev_masked_rotated launch, from the functions the dispatch calls.
+int lsec_test_predict_masked_magic_form(int plan_kernel, int K, int R, int packet, long long block_size, int *form) {
+  if (!form) return fail("lsec_test_predict_masked_magic_form: NULL output");
+  if (plan_kernel != KBYTEWISE && plan_kernel != KBITSLICED)
+    return fail("lsec_test_predict_masked_magic_form: plan kernel %d", plan_kernel);
+  const bool sliced = plan_kernel == KBITSLICED;
+  lsec::LaunchForm f;
+  if (!lsec::predict_masked_magic_launch(sliced, K, R, packet, sliced ? cauchy8_bitsliced_dw(K, R, block_size) : 0, &f))
+    return fail("lsec_test_predict_masked_magic_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
   const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
   std::memcpy(form, v, sizeof(v));
   return 0;

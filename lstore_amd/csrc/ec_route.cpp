@@ -697,6 +697,25 @@ int lsec_update_dev_masked_rotated(lio_erasure_plan_t *plan, const lsec_shard_t 
                                    static_cast<hipStream_t>(stream));
 }
 
+// (the same ladder, and a NULL magic with stripes refused behind the mask array)
+int lsec_update_magic_dev_masked(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
+                                 const unsigned long long *stripe_cols, const lsec_shard_t *fresh, int flags, void *magic,
+                                 void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  return update_magic_dev_masked(e, shards, nstripes, block_size, stripe_cols, fresh, flags, static_cast<uint8_t *>(magic),
+                                 static_cast<hipStream_t>(stream));
+}
+
+int lsec_update_magic_dev_masked_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                                         int n_shift, long long first_stripe, const unsigned long long *stripe_cols,
+                                         const lsec_shard_t *fresh, int flags, void *magic, void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  return update_magic_dev_masked_rotated(e, devs, nstripes, block_size, n_shift, first_stripe, stripe_cols, fresh, flags,
+                                         static_cast<uint8_t *>(magic), static_cast<hipStream_t>(stream));
+}
+
 int et_encode_stripes_magic(lio_erasure_plan_t *plan, char **ptrs, int nstripes, int block_size, char *magic) {
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");

@@ -85,7 +85,7 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev", "lsec_locate_dev",
            "lsec_check_dev_rotated", "lsec_locate_dev_rotated", "lsec_update_dev",
            "lsec_encode_dev_rotated", "lsec_update_dev_rotated", "lsec_update_dev_masked",
-           "lsec_update_dev_masked_rotated")
+           "lsec_update_dev_masked_rotated", "lsec_update_magic_dev_masked", "lsec_update_magic_dev_masked_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -162,7 +162,12 @@ def lib():
                                          C.c_int, C.c_void_p]
     L.lsec_update_dev_masked_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
                                                  C.c_void_p, C.POINTER(ShardRef), C.c_int, C.c_void_p]
+    L.lsec_update_magic_dev_masked.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.POINTER(ShardRef),
+                                               C.c_int, C.c_void_p, C.c_void_p]
+    L.lsec_update_magic_dev_masked_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
+                                                       C.c_void_p, C.POINTER(ShardRef), C.c_int, C.c_void_p, C.c_void_p]
     L.lsec_test_predict_masked_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
+    L.lsec_test_predict_masked_magic_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
     L.lsec_test_locate_ratio.argtypes = [P, C.c_int, C.c_int]
     L.lsec_test_plan_images.argtypes = [P]
     L.lsec_test_set_pattern_split.argtypes = [C.c_int]
@@ -721,6 +726,43 @@ class Plan:
         fresh_refs = [(fresh.data_ptr() + j * fresh.stride(1), fresh.stride(0)) for j in range(self.k)]
         self.update_dev_masked_refs(refs, n, size, stripe_cols.data_ptr(), fresh_refs, store, _stream_handle(stream))
 
+    def update_magic_dev_masked_refs(self, refs, nstripes: int, block_size: int, stripe_cols_ptr: int, fresh_refs,
+                                     magic_ptr: int, store: bool = False, stream: int = 0) -> None:
+        """lsec_update_magic_dev_masked: update_dev_masked_refs, and the 4 bytes at magic_ptr + 4*s (device memory, no
+        alignment; 0: NULL) moved from the adler32 of stripe s as it was to that of stripe s with the chunks replaced."""
+        _check(lib().lsec_update_magic_dev_masked(self._p, None if refs is None else self.shard_refs(refs), nstripes,
+                                                  block_size, stripe_cols_ptr or None,
+                                                  None if fresh_refs is None else self.shard_refs(fresh_refs),
+                                                  UPDATE_STORE if store else 0, magic_ptr or None, stream),
+               "lsec_update_magic_dev_masked")
+
+    def update_magic_dev_masked_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
+                                             stripe_cols_ptr: int, fresh_refs, magic_ptr: int, store: bool = False,
+                                             stream: int = 0) -> None:
+        """lsec_update_magic_dev_masked_rotated: update_dev_masked_rotated_refs with the magics of
+        update_magic_dev_masked_refs; they are over the LOGICAL stripes, whatever the rotation."""
+        _check(lib().lsec_update_magic_dev_masked_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes,
+                                                          block_size, n_shift, first_stripe, stripe_cols_ptr or None,
+                                                          None if fresh_refs is None else self.shard_refs(fresh_refs),
+                                                          UPDATE_STORE if store else 0, magic_ptr or None, stream),
+               "lsec_update_magic_dev_masked_rotated")
+
+    def update_magic_dev_masked(self, data, parity, stripe_cols, fresh, magic, store=False, stream=None) -> None:
+        """torch: update_dev_masked, and magic (uint8 device tensor [N, 4], contiguous: the stripes' adler32 words as
+        stripe_magic_dev writes them) brought from the old stripes' to the new stripes'."""
+        refs, n, size = self.tensor_refs(data, parity)
+        if stripe_cols.dtype.itemsize != 8 or not stripe_cols.is_cuda or not stripe_cols.is_contiguous() \
+                or stripe_cols.numel() != n:
+            raise ValueError("stripe_cols must be a contiguous 64-bit device tensor with one entry per stripe")
+        if fresh.dtype.itemsize != 1 or not fresh.is_cuda or fresh.dim() != 3 or fresh.shape[0] != n \
+                or fresh.shape[1] != self.k or fresh.shape[2] != size or fresh.stride(2) != 1:
+            raise ValueError("fresh must be a uint8 device tensor [N, k, C] with contiguous rows")
+        if magic.dtype.itemsize != 1 or not magic.is_cuda or not magic.is_contiguous() or magic.numel() != 4 * n:
+            raise ValueError("magic must be a contiguous uint8 device tensor of 4 bytes per stripe")
+        fresh_refs = [(fresh.data_ptr() + j * fresh.stride(1), fresh.stride(0)) for j in range(self.k)]
+        self.update_magic_dev_masked_refs(refs, n, size, stripe_cols.data_ptr(), fresh_refs, magic.data_ptr(), store,
+                                          _stream_handle(stream))
+
     def prepare_decode(self, erasures) -> None:
         _check(lib().lsec_prepare_decode(self._p, _erasure_array(erasures)), "lsec_prepare_decode")
 
@@ -808,15 +850,17 @@ per lane, BF branch-free; bit-sliced: DW dwords per lane (the others 0)."""
 
 # the families added behind the nine (FORM_FAMILIES stays as it is): family number 10 onwards
 MASKED_FAMILIES = ("updmask",)
+# and behind those (MASKED_FAMILIES stays as it is too): family number 11, the masked update that keeps the magics
+MAGIC_FAMILIES = ("updmaskmagic",)
 
 
 def _form(v) -> Form:
-    return Form((FORM_FAMILIES + MASKED_FAMILIES)[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
+    return Form((FORM_FAMILIES + MASKED_FAMILIES + MAGIC_FAMILIES)[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
 
 
 def launch_record() -> list:
     """Test hook: the Forms this thread's last check_dev / locate_dev / decode_dev_patterns / decode_dev_rotated
-    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated / update_dev_masked(_rotated) call launched, in order (a locate with repair: its patterned
+    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated / update_dev_masked(_rotated) / update_magic_dev_masked(_rotated) call launched, in order (a locate with repair: its patterned
     decode too; a split call: every launch)."""
     buf = (C.c_int * (8 * 16))()
     n = lib().lsec_test_launch_record(buf, 16)
@@ -841,6 +885,16 @@ def predict_masked_form(plan_kernel: int, k: int, rows: int, packet: int = 0, bl
     out = (C.c_int * 8)()
     _check(lib().lsec_test_predict_masked_form(plan_kernel, k, rows, packet, block_size, out),
            "lsec_test_predict_masked_form")
+    return _form(out)
+
+
+def predict_masked_magic_form(plan_kernel: int, k: int, rows: int, packet: int = 0, block_size: int = 0) -> Form:
+    """Test hook (no GPU): the Form ("updmaskmagic") update_magic_dev_masked_refs and
+    update_magic_dev_masked_rotated_refs launch for a plan of kernel 1 or 2 with k columns and `rows` rows, asked of
+    the functions the dispatch itself calls."""
+    out = (C.c_int * 8)()
+    _check(lib().lsec_test_predict_masked_magic_form(plan_kernel, k, rows, packet, block_size, out),
+           "lsec_test_predict_masked_magic_form")
     return _form(out)
 
 

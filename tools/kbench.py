@@ -20,6 +20,10 @@ lsec_update_dev against a device copy of the fresh chunk followed by lsec_encode
 python tools/kbench.py --update-masked [--rounds R] [--reps N] [--pattern-codes rs63,rs164,cg63]
 lsec_update_dev_masked against lsec_update_dev and the per-class calls it replaces: see update_masked_bench.
 
+python tools/kbench.py --update-magic [--rounds R] [--reps N] [--pattern-codes rs63,cg63]
+lsec_update_magic_dev_masked against lsec_update_dev_masked alone and followed by lsec_stripe_magic_dev, which is
+what keeping the magics current costs without it: see update_magic_bench.
+
 python tools/kbench.py --rotated-scrub [--rounds R] [--reps N]
 lsec_check_dev_rotated / lsec_locate_dev_rotated over the devices of a rotated LUN against the unrotated
 calls over the same bytes: see rotated_scrub_bench.
@@ -645,6 +649,87 @@ def update_masked_bench(a):
         torch.cuda.empty_cache()
 
 
+def update_magic_bench(a):
+    """The masked update that keeps the stripe magics beside what a caller does without it, interleaved round by
+    round in one process on the same k+m buffers (one per chunk, C = 1 MiB), one changed chunk per stripe (masks
+    1 << (s mod k)), LSEC_UPDATE_STORE:
+      (a) lsec_update_dev_masked                                        the update alone; its min-max is the band
+      (b) (a), then lsec_stripe_magic_dev over the k+m chunks           what a caller does today for the new magics
+      (c) lsec_update_magic_dev_masked                                  the new call
+    Chunk-sized units moved per stripe with c changed chunks: (a) (2c+m)+(m+c), (b) that + (k+m), (c) as (a).
+    Every case is checked before timing: the parity is lsec_encode_dev's for the data as it then stands, and the
+    magics (c) leaves, entered as lsec_stripe_magic_dev's of the old stripes, are lsec_stripe_magic_dev's of the new."""
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream()
+    sh = stream.cuda_stream
+    C, N = 1 << 20, a.pattern_stripes
+    for name in a.pattern_codes.split(","):
+        meth, k, m = CONFIGS[name][:3]
+        n = k + m
+        plan = L.Plan.for_chunk(meth, k, m, C)
+        bufs = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(n)]
+        fresh = [torch.randint(0, 256, (N, C), dtype=torch.uint8, device=dev) for _ in range(2)]
+        refs = [(b.data_ptr(), C) for b in bufs]
+        fresh_refs = [(fresh[j % 2].data_ptr(), C) for j in range(k)]
+        s_idx = torch.arange(N, dtype=torch.int64, device=dev)
+        mask = torch.ones(N, dtype=torch.int64, device=dev) << (s_idx % k)
+        magic = torch.zeros((N, 4), dtype=torch.uint8, device=dev)
+        magic_b = torch.zeros((N, 4), dtype=torch.uint8, device=dev)
+
+        def today():
+            plan.update_dev_masked_refs(refs, N, C, mask.data_ptr(), fresh_refs, True, sh)
+            plan.stripe_magic_dev_refs(refs, N, C, magic_b.data_ptr(), sh)
+
+        runs = {"a": lambda: plan.update_dev_masked_refs(refs, N, C, mask.data_ptr(), fresh_refs, True, sh),
+                "b": today,
+                "c": lambda: plan.update_magic_dev_masked_refs(refs, N, C, mask.data_ptr(), fresh_refs, magic.data_ptr(), True, sh)}
+        want = [torch.empty((N, C), dtype=torch.uint8, device=dev) for _ in range(m)]
+        for key in runs:
+            for b in bufs[:k]:
+                b.add_(1)  # old bytes that differ from the fresh ones again
+            plan.encode_dev_refs(refs, N, C, sh)  # consistent stripes
+            plan.stripe_magic_dev_refs(refs, N, C, magic.data_ptr(), sh)  # and their magics
+            runs[key]()
+            torch.cuda.synchronize()
+            for j in range(k):
+                hit = (mask >> j & 1).bool()
+                assert torch.equal(bufs[j][hit], fresh[j % 2][hit]), f"({key}) data chunk {j}"
+            plan.encode_dev_refs(refs[:k] + [(w.data_ptr(), C) for w in want], N, C, sh)
+            torch.cuda.synchronize()
+            for r in range(m):
+                assert torch.equal(bufs[k + r], want[r]), f"({key}) parity row {r} differs from the re-encode"
+            if key == "c":
+                plan.stripe_magic_dev_refs(refs, N, C, magic_b.data_ptr(), sh)
+                torch.cuda.synchronize()
+                assert torch.equal(magic, magic_b), "(c) the magics differ from lsec_stripe_magic_dev's over the new stripes"
+        del want
+        torch.cuda.empty_cache()
+        times = {key: [] for key in runs}
+        for _ in range(a.rounds):
+            for key, fn in runs.items():
+                fn()  # warm
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.reps):
+                    fn()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                times[key].append(e0.elapsed_time(e1) / a.reps)
+        what = {"a": "lsec_update_dev_masked", "b": "(a) + lsec_stripe_magic_dev", "c": "lsec_update_magic_dev_masked"}
+        units = {"a": 2 + m + m + 1, "b": 2 + m + m + 1 + n, "c": 2 + m + m + 1}
+        med = {key: sorted(ts)[len(ts) // 2] for key, ts in times.items()}
+        for key, ts in times.items():
+            db = units[key] * C * N
+            print(f"{name} N={N} C={C} ({key}) {what[key]:30s} median {med[key]:7.3f} ms  min {min(ts):7.3f}  max {max(ts):7.3f}  "
+                  f"{units[key]:2d} chunks per stripe {db / med[key] / 1e6:7.1f} GB/s ({db / med[key] / 8e9:5.1%} of 8 TB/s)", flush=True)
+        print(f"{name} over {a.rounds} rounds of {a.reps} launches: (c)/(b) = {med['c'] / med['b']:.3f} "
+              f"({'below' if med['c'] < med['b'] else 'NOT below'} today's two calls), (c)/(a) = {med['c'] / med['a']:.3f} "
+              f"(the price of the fused sums)", flush=True)
+        del bufs, fresh, mask, magic, magic_b
+        plan.close()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data-gib", type=float, default=24.0)
@@ -679,7 +764,13 @@ def main():
     ap.add_argument("--update-masked", action="store_true",
                     help="time lsec_update_dev_masked against lsec_update_dev and the per-class calls it replaces "
                          "(update_masked_bench; --pattern-stripes, --pattern-codes) and exit")
+    ap.add_argument("--update-magic", action="store_true",
+                    help="time lsec_update_magic_dev_masked against lsec_update_dev_masked alone and followed by "
+                         "lsec_stripe_magic_dev (update_magic_bench; --pattern-stripes, --pattern-codes) and exit")
     a = ap.parse_args()
+    if a.update_magic:
+        update_magic_bench(a)
+        return
     if a.update_masked:
         update_masked_bench(a)
         return
