@@ -166,6 +166,62 @@ int lsec_decode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
                             long long block_size, const int *lost, int n_shift,
                             long long first_stripe, void *stream);
 
+/* The patterned decode that also leaves every stripe's magic, one pass: lsec_decode_dev_patterns /
+ * lsec_decode_dev_rotated, and magic[s] -- the adler32 over all k+m chunks of stripe s (the stripe
+ * "magic", below) -- as lsec_stripe_magic_dev would write it behind the decode.  A degraded or
+ * paranoid read is "rebuild the bad chunks, then the checksum over all k+m chunks must equal the
+ * quorum magic" (jerase_control_check, segment/jerasure.c:244-249; je_cksum_compare, :188-194);
+ * as two calls that is k reads + e writes and then k+m reads per stripe with e erasures.  Here the k
+ * survivors the decode loads and the e chunks it forms are summed from registers, and only the
+ * m - e survivors it does not use are loaded for the checksum alone: k+m-e reads and e writes.
+ * Purely additive too: the version stays 3, a caller detects the calls by their symbols.
+ *
+ * - Bytes left in the shards: exactly those lsec_decode_dev_patterns / lsec_decode_dev_rotated
+ *   leave for the same arguments.  Only erased slots are written; survivors are only read; a
+ *   RAID4 pattern that loses only the parity writes nothing.
+ * - `magic` is device memory, 4*nstripes bytes, no alignment requirement, pure output.  Word s is
+ *   the 4 little-endian bytes of zlib's adler32 over the k+m chunks of stripe s in LOGICAL order
+ *   (for the rotated call: after un-rotating), as they lie in memory after the decode.  A stripe
+ *   whose stored bytes are inconsistent, or whose RAID4 parity is stale, gets the adler32 of
+ *   exactly those bytes: the call judges nothing but `expect`.
+ * - A stripe whose pattern is empty (just -1, or RAID4 parity-only) is checksummed without being
+ *   written, k+m reads: the paranoid read's "verify every stripe".
+ * - Patterned call: a stripe_pattern value >= npatterns skips the stripe entirely.  None of its
+ *   chunks is read or written, its magic word is neither read nor written, and bad[s] is 0: the
+ *   non-paranoid read, which verifies only stripes with bad chunks.  In the rotated call every
+ *   stripe has a pattern (its rotation), so none is skipped.
+ * - `expect`, `bad` and `bad_count` are optional (NULL).  expect: device memory, 4*nstripes bytes,
+ *   no alignment requirement, only read: the quorum magics.  With it, bad (nstripes bytes, no
+ *   alignment) receives 1 where magic[s] != expect[s] for a stripe that was not skipped, else 0,
+ *   and bad_count (one 32-bit word, 4-byte aligned) the number of those.  The call sets both; it
+ *   does not add to them.  Without expect a non-NULL bad or bad_count is refused.
+ * - Scratch: the per-stripe accumulators, 16 bytes per stripe, come from the stream-ordered
+ *   allocator (hipMallocAsync on `stream`), are zeroed there and go back to it on the stream,
+ *   exactly as lsec_encode_magic_dev's do.
+ * - Tables: the plain calls' own, cached on the plan per device under the same keys, together with
+ *   what the magic form adds to a pattern's record (the survivors its decode does not read).  A
+ *   repeated call does no matrix work and no upload.  nstripes == 0 validates the arguments and
+ *   prepares the tables, as for the plain calls; magic and the other outputs may then be NULL.
+ * - Plans: lsec_plan_kernel 1 and 2.  Limits: k <= 64, 1 <= m <= 8 (so a pattern has at most 8
+ *   unused survivors), at most 8 erasures per pattern, 1 <= npatterns <= 256.  Layout, alignment
+ *   and block_size rules are those of lsec_decode_dev.  magic, expect, bad and bad_count must not
+ *   overlap one another or the shards.
+ * - Every refusal -- plan kernels 3-5, k or m out of range, then anything the plain call refuses,
+ *   in its order, then a NULL magic with nstripes > 0, bad or bad_count without expect, a
+ *   misaligned bad_count -- returns -1 with a message for lsec_last_error that names this call and
+ *   the limit, and nothing is enqueued: every argument check comes before the first HIP call.
+ *   There is no fallback.
+ * Enqueued on `stream`; return without synchronising.  0 / -1. */
+int lsec_decode_magic_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
+                                   long long block_size, const int *patterns, int npatterns,
+                                   const unsigned char *stripe_pattern, void *magic,
+                                   const void *expect, unsigned char *bad, unsigned int *bad_count,
+                                   void *stream);
+int lsec_decode_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                                  long long block_size, const int *lost, int n_shift, long long first_stripe,
+                                  void *magic, const void *expect, unsigned char *bad,
+                                  unsigned int *bad_count, void *stream);
+
 /* Parity check of device-resident stripes, one pass: are these stripes consistent, and if not,
  * which parity rows disagree?  `shards` are the k+m logical chunks as for lsec_encode_dev; all
  * of them are only read.  `syndrome` is device memory holding nstripes 32-bit words.

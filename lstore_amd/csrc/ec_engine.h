@@ -109,6 +109,11 @@ struct PatternTable {
   std::vector<CoefCell> cells;
   std::vector<char> reachable;  // rotated: 0 for a rotation (first_stripe + s) * n_shift mod n never takes
   DevImage dev_recs, dev_cells;  // both uploaded, per device: a device has both or neither
+  // what the magic form adds to the records (ec_kernels.h, PatUnused): each pattern's survivors that its decode
+  // does not read, built with the table (m <= 8, else left empty) and uploaded at the first
+  // lsec_decode_magic_dev_* call on a device
+  std::vector<lsec::PatUnused> unused;
+  DevImage dev_unused;
   struct Dev {                   // the pair on one device, as enqueue_patterns takes it
     const lsec::PatRecord *recs = nullptr;
     const CoefCell *cells = nullptr;
@@ -150,6 +155,7 @@ struct PlanImpl {
     for (auto &tab : pattern_cache) {
       f(tab.second.dev_recs);
       f(tab.second.dev_cells);
+      f(tab.second.dev_unused);
     }
   }
 };
@@ -251,6 +257,20 @@ int decode_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long l
                         const unsigned char *stripe_pattern, hipStream_t st);
 int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
                        long long first_stripe, hipStream_t st);
+// the same decodes, and magic[s] = adler32 of stripe s's k+m logical chunks as the decode leaves them (a stripe whose
+// pattern id is >= npatterns is skipped); expect / bad / bad_count: the comparison with the quorum magics, all optional
+int named(const char *name, int rc);  // rc != 0: lsec_last_error's message gets "<name>: " in front; returns rc
+int decode_magic_limits(const lio_erasure_plan_t *p, const char *name);  // plan kernels 1 and 2, k <= 64, 1 <= m <= 8
+struct MagicCheck {
+  uint8_t *magic;
+  const uint8_t *expect;
+  uint8_t *bad;
+  unsigned *bad_count;
+};
+int decode_magic_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
+                              const unsigned char *stripe_pattern, const MagicCheck &mc, hipStream_t st);
+int decode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
+                             long long first_stripe, const MagicCheck &mc, hipStream_t st);
 void fp_encode_block(lio_erasure_plan_t *p, char **ptr, int block_size);         // ec_route.cpp
 int fp_dummy(lio_erasure_plan_t *);                                            // ec_route.cpp
 int encode_stripes_impl(PlanExt *e, char **ptrs, int nstripes, long long C);  // ec_route.cpp

@@ -130,7 +130,8 @@ struct alignas(64) PatRecord {
   uint32_t nout;               // erasure count; 0: the stripe is neither read nor written
   uint32_t cells_off;          // first cell of the pattern's CoefCell[Rmax][K] image in PatternArgs::cells
   uint32_t pad[2];
-  uint32_t in_sel[kMaxK];      // PatternArgs::sh index of input j (the pattern's j-th survivor)
+  uint32_t in_sel[kMaxK];      // PatternArgs::sh index of input j (the pattern's j-th survivor; nout 0: data chunk j,
+                               // which only the MG kernels look at)
   uint32_t out_sel[kPatMaxOut];  // PatternArgs::sh index of output r (its r-th erased chunk)
 };
 static_assert(sizeof(PatRecord) == 320, "PatRecord layout");
@@ -156,6 +157,49 @@ struct PatternArgs {
 // rmax = the table's largest erasure count (1..kPatMaxOut): the kernel's output rows
 hipError_t launch_pattern_bytewise(const PatternArgs &a, int rmax, hipStream_t stream);
 hipError_t launch_pattern_bitsliced(const PatternArgs &a, int rmax, hipStream_t stream);
+
+// The patterned decode that also leaves each stripe's adler32 magic (lsec_decode_magic_dev_patterns /
+// _rotated): the paranoid read's "rebuild, then the checksum over all k+m chunks" in one pass.  A
+// tile holds the K survivors it loads and the rows it forms in registers; the MG kernels
+// (k_patmagic_*: the patterned tile bodies under `if constexpr (MG)`) sum those into one MagicLane at
+// their LOGICAL chunk ids, load the survivors the decode does not read -- the pattern's PatUnused
+// list, a device array parallel to recs and in in_sel's index space -- for the checksum alone, and
+// commit once per tile into magic_acc[2s], [2s + 1] (zeroed before the first launch).  A record whose
+// nout is 0 names the K data chunks in in_sel and the parity in its PatUnused: the checksum-only
+// path, K + m reads and no write.  Logical ids: the selection itself with a stripe_pattern (the
+// shards are logical chunks), (sel + p) mod nshards without one (the records of rotation p hold
+// physical devices).  launch_pattern_magic_finalize folds the sums into the magic words.  The struct
+// derives from PatternArgs, whose layout -- and PatRecord's, and with them every k_pat_* and
+// k_patrot_* kernel -- stays as it is.
+constexpr int kPatMaxUnused = 8;     // survivors a pattern's decode does not read: m - nout <= m <= 8
+struct alignas(16) PatUnused {
+  uint32_t n;                        // entries of sel in use
+  uint32_t pad[3];
+  uint32_t sel[kPatMaxUnused];       // PatternArgs::sh indices, ascending by logical id
+};
+static_assert(sizeof(PatUnused) == 48, "PatUnused layout");
+
+struct PatternMagicArgs : PatternArgs {
+  const PatUnused *unused;        // npat records (device memory)
+  unsigned long long *magic_acc;  // 2 per stripe of this launch (8-byte aligned device memory)
+};
+static_assert(sizeof(PatternMagicArgs) == sizeof(PatternArgs) + 16, "PatternMagicArgs layout");
+static_assert(sizeof(PatternMagicArgs) < 4096, "PatternMagicArgs: under the 4 KiB of kernel arguments");
+
+// As launch_pattern_*, with unused and magic_acc != NULL and nshards - K <= kPatMaxUnused; rmax >= 1
+// also for a table whose patterns are all empty (its tiles only checksum).  The launch shapes are the
+// patterned kernels' own (patmagic_bytewise_form).
+hipError_t launch_pattern_magic_bytewise(const PatternMagicArgs &a, int rmax, hipStream_t stream);
+hipError_t launch_pattern_magic_bitsliced(const PatternMagicArgs &a, int rmax, hipStream_t stream);
+// One launch per call, behind the tile launches, one thread per stripe of the whole call.  A stripe
+// whose stripe_pattern id (stripe_pattern may be null: none is skipped) is >= npat: its magic word is
+// neither read nor written and bad[s] = 0.  Every other: the 4 little-endian bytes at magic + 4s (no
+// alignment) become A = (1 + acc[2s]) mod 65521, B = (total_len + acc[2s + 1]) mod 65521; with expect
+// (may be null; 4 bytes per stripe, no alignment) bad[s] (may be null) = the words differ, and
+// bad_count (may be null; zeroed by the caller) counts them.
+hipError_t launch_pattern_magic_finalize(const unsigned long long *acc, const uint8_t *stripe_pattern, uint32_t npat,
+                                         int nstripes, int64_t total_len, uint8_t *magic, const uint8_t *expect,
+                                         uint8_t *bad, unsigned *bad_count, hipStream_t stream);
 
 // Parity check of device-resident stripes (lsec_check_dev): one streaming pass forms the R parity
 // rows of every stripe in registers, as the encode kernels do, and compares them with the stored
@@ -423,7 +467,7 @@ hipError_t launch_update_magic_finalize(const unsigned long long *acc, const uns
 // functions record the form at the one place where the template arguments are known; the record
 // is the calling thread's, holds the launches since launch_record_reset() in order (the engine
 // resets it on entry to each of those calls) and costs a few host stores per launch.
-enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic };
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic, kFormPatMagic };
 struct LaunchForm {
   int family, sliced, R, KC, IT, VW, BF, DW;
 };
@@ -439,6 +483,8 @@ bool predict_launch(int family, bool sliced, int K, int R, int packet, int dw_pr
 bool predict_masked_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // and for the masked update with the magic (kFormUpdMaskMagic)
 bool predict_masked_magic_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
+// and for the patterned decode with the magic (kFormPatMagic; R: the table's rmax, at least 1)
+bool predict_pattern_magic_launch(bool sliced, int K, int R, int packet, LaunchForm *out);
 // the K with fixed-K forms (LSEC_FIXED_K), ascending -> how many there are; out[0 .. min(that, max))
 int fixed_k_list(int *out, int max);
 

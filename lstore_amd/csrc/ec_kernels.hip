@@ -390,6 +390,32 @@ hipError_t launch_pattern_bitsliced(const PatternArgs &a, int rmax, hipStream_t 
   return by_r(rmax, [&](auto r) { return dispatch_pat_bitsliced<decltype(r)::value>(a, st, grid); });
 }
 
+// ------------------------------------------------------------------ the patterned decode that leaves the stripe magics
+namespace {
+bool pattern_magic_args_ok(const PatternMagicArgs &a, int rmax) {
+  return pattern_args_ok(a, rmax) && a.unused && a.magic_acc && reinterpret_cast<uintptr_t>(a.magic_acc) % 8 == 0 &&
+         a.nshards > a.K && a.nshards - a.K <= kPatMaxUnused;
+}
+}  // namespace
+
+hipError_t launch_pattern_magic_bytewise(const PatternMagicArgs &a, int rmax, hipStream_t st) {
+  if (!pattern_magic_args_ok(a, rmax)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const BwForm f = patmagic_bytewise_form(a.K, rmax);
+  const int grid = tile_grid(BwShape{f.it, f.vw, f.bf}.tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(rmax, [&](auto r) { return dispatch_patmagic_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_pattern_magic_bitsliced(const PatternMagicArgs &a, int rmax, hipStream_t st) {
+  if (!pattern_magic_args_ok(a, rmax) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int grid = tile_grid(kBlock * 4, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(rmax, [&](auto r) { return dispatch_patmagic_bitsliced<decltype(r)::value>(a, st, grid); });
+}
+
 // ------------------------------------------------------------------ check / locate, rotated or not
 namespace {
 bool rot_fields_ok(uint32_t rot0, uint32_t rot_step, uint32_t rot_n, int nshards) {
@@ -739,6 +765,18 @@ bool predict_masked_magic_launch(bool sliced, int K, int R, int packet, int dw_p
   return true;
 }
 
+bool predict_pattern_magic_launch(bool sliced, int K, int R, int packet, LaunchForm *out) {
+  if (K < 1 || K > kMaxK || R < 1 || R > kPatMaxOut) return false;
+  if (sliced) {
+    if (packet <= 0 || packet % 4 != 0) return false;
+    *out = LaunchForm{kFormPatMagic, 1, R, 0, 0, 0, 0, 1};
+    return true;
+  }
+  const BwForm f = patmagic_bytewise_form(K, R);
+  *out = LaunchForm{kFormPatMagic, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
+  return true;
+}
+
 int fixed_k_list(int *out, int max) {
   int n = 0;
 #define LSEC_LIST_K(KK)     \
@@ -822,6 +860,34 @@ __global__ void k_update_magic_finalize(const unsigned long long *acc, const uns
   w[1] = (m >> 8) & 255;
   w[2] = (m >> 16) & 255;
   w[3] = m >> 24;
+}
+
+// The patterned decode's magics (launch_pattern_magic_finalize, ec_kernels.h): acc holds each stripe's
+// sums, per-tile values in [0, M) added up.  The words are written and compared bytewise: magic and
+// expect have no alignment.
+__global__ void k_pattern_magic_finalize(const unsigned long long *acc, const uint8_t *stripe_pattern, uint32_t npat,
+                                         int nstripes, uint64_t total_len, uint8_t *magic, const uint8_t *expect,
+                                         uint8_t *bad, unsigned *bad_count) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nstripes) return;
+  if (stripe_pattern && stripe_pattern[s] >= npat) {  // a skipped stripe: its word is neither read nor written
+    if (bad) bad[s] = 0;
+    return;
+  }
+  const uint32_t A = static_cast<uint32_t>((1 + acc[2 * s]) % kAdlerMod);
+  const uint32_t B = static_cast<uint32_t>((total_len % kAdlerMod + acc[2 * s + 1]) % kAdlerMod);
+  const uint32_t m = (B << 16) | A;
+  uint8_t *w = magic + 4ll * s;
+  w[0] = m & 255;
+  w[1] = (m >> 8) & 255;
+  w[2] = (m >> 16) & 255;
+  w[3] = m >> 24;
+  if (!expect) return;
+  const uint8_t *x = expect + 4ll * s;
+  const uint32_t want = x[0] | (x[1] << 8) | (x[2] << 16) | (static_cast<uint32_t>(x[3]) << 24);
+  const bool differs = want != m;
+  if (bad) bad[s] = differs ? 1 : 0;
+  if (bad_count && differs) atomicAdd(bad_count, 1u);
 }
 
 // one block per (stripe, 8 KiB column tile): OR of a^b over every pair, one flag store per
@@ -1127,6 +1193,15 @@ hipError_t launch_magic_finalize(const unsigned long long *acc, int nstripes, in
   if (nstripes <= 0) return hipSuccess;
   return launch_kernel(&k_magic_finalize, dim3((nstripes + 255) / 256), dim3(256), st, acc, nstripes,
                      static_cast<uint64_t>(total_len), magic);
+}
+
+hipError_t launch_pattern_magic_finalize(const unsigned long long *acc, const uint8_t *stripe_pattern, uint32_t npat,
+                                         int nstripes, int64_t total_len, uint8_t *magic, const uint8_t *expect,
+                                         uint8_t *bad, unsigned *bad_count, hipStream_t st) {
+  if (nstripes <= 0) return hipSuccess;
+  if (!acc || !magic || total_len < 0 || reinterpret_cast<uintptr_t>(bad_count) % 4 != 0) return hipErrorInvalidValue;
+  return launch_kernel(&k_pattern_magic_finalize, dim3((nstripes + 255) / 256), dim3(256), st, acc, stripe_pattern, npat,
+                       nstripes, static_cast<uint64_t>(total_len), magic, expect, bad, bad_count);
 }
 
 hipError_t launch_update_magic_finalize(const unsigned long long *acc, const unsigned long long *stripe_cols,

@@ -1416,8 +1416,86 @@ struct PatShards {
 // kernel ran at 0.56 of 8 TB/s against their 0.75: profiles/patterns_kbench_runtime_k.txt).
 // Instantiated for the one-row kernel only (dispatch_pat_bytewise).  Args: PatternArgs, or
 // PatternRotArgs for the rotated single-erasure repair (the same tile body up to PatShards).
-template <int R, int KC, int IT, int VW, bool BF, typename Args>
-__device__ __forceinline__ void pat_bytewise_tiles(const Args &a) {
+//
+// MG (lsec_decode_magic_dev_patterns / _rotated; Args: PatternMagicArgs): the tile also sums the
+// stripe's adler32 magic over all of its chunks as the decode leaves them.  One MagicLane takes every
+// survivor the tile loads, every row it rebuilds (r < nout) and the pattern's unused survivors
+// (PatUnused, loaded here for the checksum alone), each at its LOGICAL chunk id (pat_logical), and the
+// tile commits once through block_sum into macc[2s], macc[2s + 1].  block_sum has barriers: every lane
+// of the workgroup reaches it.  The one exit ahead of it, id >= npat, is uniform over the workgroup;
+// nout == 0 no longer leaves but takes the checksum-only path (no image is read, nothing is
+// stored), and units past the end of a ragged tile read as zero and add nothing.  red: kBlock / 64
+// words of LDS.  Without MG un, macc and red are not looked at and the code is the plain decode's.
+typedef const __attribute__((address_space(4))) PatUnused ConstUnused;
+
+// the logical chunk id of selection sel in a stripe of pattern p: the records of a call without a
+// stripe_pattern hold the physical devices of rotation p (wave-uniform scalar arithmetic)
+__device__ __forceinline__ uint32_t pat_logical(const PatternArgs &a, uint32_t p, uint32_t sel) {
+  if (a.stripe_pattern) return sel;
+  const uint32_t c = sel + p;
+  return c >= static_cast<uint32_t>(a.nshards) ? c - static_cast<uint32_t>(a.nshards) : c;
+}
+
+// bw_inputs for the MG tiles of a full tile: the same loads and arithmetic (`work`: the pattern has
+// rows to form, wave-uniform), and every input's units handed to seen(j, units) once they are loaded.
+template <int R, int KC, int IT, int VW, bool BF, typename Addr, typename Seen>
+__device__ __forceinline__ void bw_inputs_seen(typename VecT<VW>::type (&acc)[IT][R], ConstCell *cells, int K, bool work,
+                                               Addr &&addr, Seen &&seen) {
+  typedef typename VecT<VW>::type V;
+  constexpr int kStep = BwTile<IT, VW>::kStep;
+  if constexpr (KC > 0) {
+    V v[KC][IT];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+      const uint64_t p = addr(j);
+#pragma unroll
+      for (int it = 0; it < IT; ++it) v[j][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
+    }
+    if (work) {
+      if constexpr (BF) {
+#pragma unroll
+        for (int j = 0; j + 1 < KC; j += 2) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[j], v[j + 1], cells, K, j);
+        if constexpr (KC % 2) bw_accumulate_bf<R, IT, VW, false, false>(acc, v[KC - 1], v[KC - 1], cells, K, KC - 1);
+      } else {
+#pragma unroll
+        for (int j = 0; j < KC; ++j) bw_accumulate<R, IT, VW>(acc, v[j], cells, K, j);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < KC; ++j) seen(j, v[j]);
+  } else {
+    for (int j0 = 0; j0 < K; j0 += 4) {
+      V v[4][IT];
+      const int nj = min(4, K - j0);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        if (jj < nj) {
+          const uint64_t p = addr(j0 + jj);
+#pragma unroll
+          for (int it = 0; it < IT; ++it) v[jj][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
+        }
+      }
+      if (work) {
+        if constexpr (BF) {
+          if (nj >= 2) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[0], v[1], cells, K, j0);
+          if (nj == 4) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[2], v[3], cells, K, j0 + 2);
+          if (nj == 1 || nj == 3) bw_accumulate_bf<R, IT, VW, false, false>(acc, v[nj - 1], v[nj - 1], cells, K, j0 + nj - 1);
+        } else {
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj)
+            if (jj < nj) bw_accumulate<R, IT, VW>(acc, v[jj], cells, K, j0 + jj);
+        }
+      }
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj)
+        if (jj < nj) seen(j0 + jj, v[jj]);
+    }
+  }
+}
+
+template <int R, int KC, int IT, int VW, bool BF, bool MG = false, typename Args>
+__device__ __forceinline__ void pat_bytewise_tiles(const Args &a, ConstUnused *un = nullptr, unsigned long long *macc = nullptr,
+                                                   uint32_t *red = nullptr) {
   typedef typename VecT<VW>::type V;
   constexpr int kStep = BwTile<IT, VW>::kStep;
   constexpr int kTile = BwTile<IT, VW>::kBytes;
@@ -1435,11 +1513,12 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a) {
     if (p >= a.npat) return;  // no such pattern: the stripe is left alone
     ConstRec *rec = recs + p;
     const uint32_t nout = rec->nout;
-    if (nout == 0) return;  // nothing to rebuild
+    if (!MG && nout == 0) return;  // nothing to rebuild
     ConstCell *cells = images + rec->cells_off;
     const PatShards<Args> sh(a, s);
     const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
     const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
+    MagicLane ml;  // the stripe magic's partial sums (MG only)
 
     V acc[IT][R];
 #pragma unroll
@@ -1448,13 +1527,23 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a) {
       for (int r = 0; r < R; ++r) acc[it][r] = 0u;
 
     if (full) {
-      bw_inputs<R, KC, IT, VW, BF, false>(
-          acc, cells, K,
-          [&](int j) LSEC_INLINE {
-            const ShardRef in = sh.at(rec->in_sel[j]);
-            return in.base + s * in.stride + off0;
-          },
-          NoLoads());
+      if constexpr (MG) {
+        bw_inputs_seen<R, KC, IT, VW, BF>(
+            acc, cells, K, nout != 0,
+            [&](int j) LSEC_INLINE {
+              const ShardRef in = sh.at(rec->in_sel[j]);
+              return in.base + s * in.stride + off0;
+            },
+            [&](int j, const V(&v)[IT]) LSEC_INLINE { ml_add<IT, VW>(ml, v, pat_logical(a, p, rec->in_sel[j])); });
+      } else {
+        bw_inputs<R, KC, IT, VW, BF, false>(
+            acc, cells, K,
+            [&](int j) LSEC_INLINE {
+              const ShardRef in = sh.at(rec->in_sel[j]);
+              return in.base + s * in.stride + off0;
+            },
+            NoLoads());
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
@@ -1471,6 +1560,10 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a) {
         V v[IT];
 #pragma unroll
         for (int it = 0; it < IT; ++it) v[it] = load_ragged<VW>(q, off0 + it * kStep, C);
+        if constexpr (MG) {
+          ml_add<IT, VW>(ml, v, pat_logical(a, p, rec->in_sel[j]));
+          if (nout == 0) continue;  // checksum only: the record has no image
+        }
         bw_acc1<R, IT, VW, BF, false>(acc, v, cells, K, j);
       }
 #pragma unroll
@@ -1482,6 +1575,40 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a) {
           for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
         }
       }
+    }
+    if constexpr (MG) {
+      // the rebuilt rows as stored (a ragged tile's units past C were formed from zeros and are zero)
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (static_cast<uint32_t>(r) < nout) {
+          V o[IT];
+#pragma unroll
+          for (int it = 0; it < IT; ++it) o[it] = acc[it][r];
+          ml_add<IT, VW>(ml, o, pat_logical(a, p, rec->out_sel[r]));
+        }
+      }
+      // the survivors the decode did not read, up to four in flight as the inputs are
+      ConstUnused *ur = un + p;
+      const uint32_t nu = min(ur->n, static_cast<uint32_t>(kPatMaxUnused));
+      for (uint32_t u0 = 0; u0 < nu; u0 += 4) {
+        V v[4][IT];
+#pragma unroll
+        for (uint32_t uu = 0; uu < 4; ++uu) {
+          if (u0 + uu < nu) {
+            const ShardRef in = sh.at(ur->sel[u0 + uu]);
+            const uint64_t q = in.base + s * in.stride;
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+              if (full) v[uu][it] = __builtin_nontemporal_load(gptr<V>(q + off0 + it * kStep));
+              else v[uu][it] = load_ragged<VW>(q, off0 + it * kStep, C);
+            }
+          }
+        }
+#pragma unroll
+        for (uint32_t uu = 0; uu < 4; ++uu)
+          if (u0 + uu < nu) ml_add<IT, VW>(ml, v[uu], pat_logical(a, p, ur->sel[u0 + uu]));
+      }
+      ml_commit(ml, macc, s, a.nshards, static_cast<uint64_t>(C), static_cast<uint64_t>(off0), kStep, red);
     }
   }, a.tile_phase);
 }
@@ -1496,9 +1623,19 @@ __global__ __launch_bounds__(kBlock) void k_patrot_bytewise(PatternRotArgs a) {
   pat_bytewise_tiles<R, KC, IT, VW, BF>(a);
 }
 
-// k_gf8_bitsliced's lanes (one dword of packet-column space per lane) under a pattern record
-template <int R, typename Args>
-__device__ __forceinline__ void pat_bitsliced_tiles(const Args &a) {
+template <int R, int KC, int IT, int VW, bool BF>
+__global__ __launch_bounds__(kBlock) void k_patmagic_bytewise(PatternMagicArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  pat_bytewise_tiles<R, KC, IT, VW, BF, true>(
+      a, reinterpret_cast<ConstUnused *>(reinterpret_cast<uintptr_t>(a.unused)), a.magic_acc, red);
+}
+
+// k_gf8_bitsliced's lanes (one dword of packet-column space per lane) under a pattern record.
+// MG as in pat_bytewise_tiles: the lanes past the end of a ragged last tile then skip the loads and
+// the stores, but still join the tile's reduction (as k_gf8_bitsliced's do).
+template <int R, bool MG = false, typename Args>
+__device__ __forceinline__ void pat_bitsliced_tiles(const Args &a, ConstUnused *un = nullptr, unsigned long long *macc = nullptr,
+                                                    uint32_t *red = nullptr) {
   const int K = a.K;
   const uint32_t P = static_cast<uint32_t>(a.packet);
   const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
@@ -1514,44 +1651,67 @@ __device__ __forceinline__ void pat_bitsliced_tiles(const Args &a) {
     if (p >= a.npat) return;
     ConstRec *rec = recs + p;
     const uint32_t nout = rec->nout;
-    if (nout == 0) return;
+    if (!MG && nout == 0) return;
     ConstCell *cells = images + rec->cells_off;
     const PatShards<Args> sh(a, s);
     const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * 4;
-    if (colb >= col_bytes) return;  // lanes past the end of a ragged last tile
+    const bool valid = colb < col_bytes;
+    if (!MG && !valid) return;  // lanes past the end of a ragged last tile
     const uint32_t sp = colb / P;
     const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+    MagicLane ml;  // the stripe magic's partial sums (MG only)
 
-    uint32_t acc[R][8];
+    if (!MG || valid) {
+      uint32_t acc[R][8];
 #pragma unroll
-    for (int r = 0; r < R; ++r)
+      for (int r = 0; r < R; ++r)
 #pragma unroll
-      for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
+        for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
 
-    for (int j = 0; j < K; ++j) {
-      const ShardRef in = sh.at(rec->in_sel[j]);
-      const uint64_t q = in.base + s * in.stride + off;
-      uint32_t e[8];
+      for (int j = 0; j < K; ++j) {
+        const ShardRef in = sh.at(rec->in_sel[j]);
+        const uint64_t q = in.base + s * in.stride + off;
+        uint32_t e[8];
 #pragma unroll
-      for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<uint32_t>(q + x * P));
-      uint32_t c[R];
-      uint32_t cm = 0;  // bits used by any output: no doublings past the highest one
+        for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<uint32_t>(q + x * P));
+        if constexpr (MG) {
+          ml_add<8, 1>(ml, e, pat_logical(a, p, rec->in_sel[j]));
+          if (nout == 0) continue;  // checksum only: the record has no image
+        }
+        uint32_t c[R];
+        uint32_t cm = 0;  // bits used by any output: no doublings past the highest one
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          c[r] = cells[r * K + j].coef;
+          cm |= c[r];
+        }
+        gf8_sliced_mul_acc<0>(acc, e, c, cm);
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        c[r] = cells[r * K + j].coef;
-        cm |= c[r];
-      }
-      gf8_sliced_mul_acc<0>(acc, e, c, cm);
-    }
+        if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
+          const ShardRef out = sh.at(rec->out_sel[r]);
+          const uint64_t q = out.base + s * out.stride + off;
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
-        const ShardRef out = sh.at(rec->out_sel[r]);
-        const uint64_t q = out.base + s * out.stride + off;
+          for (int x = 0; x < 8; ++x) put_nt<false, uint32_t>(q + x * P, acc[r][x]);
+          if constexpr (MG) ml_add<8, 1>(ml, acc[r], pat_logical(a, p, rec->out_sel[r]));
+        }
+      }
+      if constexpr (MG) {
+        // the survivors the decode did not read
+        ConstUnused *ur = un + p;
+        const uint32_t nu = min(ur->n, static_cast<uint32_t>(kPatMaxUnused));
+        for (uint32_t u = 0; u < nu; ++u) {
+          const ShardRef in = sh.at(ur->sel[u]);
+          const uint64_t q = in.base + s * in.stride + off;
+          uint32_t e[8];
 #pragma unroll
-        for (int x = 0; x < 8; ++x) put_nt<false, uint32_t>(q + x * P, acc[r][x]);
+          for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<uint32_t>(q + x * P));
+          ml_add<8, 1>(ml, e, pat_logical(a, p, ur->sel[u]));
+        }
       }
     }
+    if constexpr (MG) ml_commit(ml, macc, s, a.nshards, static_cast<uint64_t>(a.size), static_cast<uint64_t>(off), P, red);
   }, a.tile_phase);
 }
 
@@ -1563,6 +1723,12 @@ __global__ __launch_bounds__(kBlock) void k_pat_bitsliced(PatternArgs a) {
 template <int R>
 __global__ __launch_bounds__(kBlock) void k_patrot_bitsliced(PatternRotArgs a) {
   pat_bitsliced_tiles<R>(a);
+}
+
+template <int R>
+__global__ __launch_bounds__(kBlock) void k_patmagic_bitsliced(PatternMagicArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  pat_bitsliced_tiles<R, true>(a, reinterpret_cast<ConstUnused *>(reinterpret_cast<uintptr_t>(a.unused)), a.magic_acc, red);
 }
 
 // The patterned bytewise kernel takes the automatic shape (bw_auto) of the table's row count and
@@ -1633,6 +1799,47 @@ hipError_t dispatch_patrot_bitsliced(const PatternRotArgs &a, hipStream_t st, in
   record_launch({kFormPatRot, 1, 1, 0, 0, 0, 0, 1});
   return launch_tiled(&k_patrot_bitsliced<1>, grid, st, a);
 }
+#endif
+
+// The MG forms (lsec_decode_magic_dev_patterns / _rotated; DESIGN.md 3.7 has their registers): the
+// patterned kernels' own, through a constant of their own, so that one family can move without the other.
+constexpr BwForm patmagic_bytewise_form(int K, int R) { return pat_bytewise_form(K, R); }
+
+template <int R, int KC, int IT, int VW, bool BF>
+hipError_t patmagic_kernel(const PatternMagicArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormPatMagic, 0, R, KC, IT, VW, BF ? 1 : 0, 0});
+  return launch_tiled(&k_patmagic_bytewise<R, KC, IT, VW, BF>, grid, st, a);
+}
+
+template <int R>
+hipError_t dispatch_patmagic_bytewise(const PatternMagicArgs &a, hipStream_t st, int grid) {
+  const BwForm f = patmagic_bytewise_form(a.K, R);
+  if constexpr (R == 1) {
+    constexpr BwShape sh = bw_auto(0, 1);
+    switch (f.kc) {
+      case 6: return patmagic_kernel<1, 6, sh.it, sh.vw, sh.bf>(a, st, grid);
+      case 10: return patmagic_kernel<1, 10, sh.it, sh.vw, sh.bf>(a, st, grid);
+      default: return patmagic_kernel<1, 0, sh.it, sh.vw, sh.bf>(a, st, grid);
+    }
+  } else {
+    if (f.it == 1) return patmagic_kernel<R, 0, 1, 4, true>(a, st, grid);
+    return patmagic_kernel<R, 0, 2, 4, true>(a, st, grid);
+  }
+}
+
+template <int R>
+hipError_t dispatch_patmagic_bitsliced(const PatternMagicArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormPatMagic, 1, R, 0, 0, 0, 0, 1});
+  return launch_tiled(&k_patmagic_bitsliced<R>, grid, st, a);
+}
+
+// instantiated per R in ec_patterns_magic_inst.hip
+#define LSEC_DECLARE_PATMAGIC_R(RR)                                                                     \
+  extern template hipError_t dispatch_patmagic_bytewise<RR>(const PatternMagicArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_patmagic_bitsliced<RR>(const PatternMagicArgs &, hipStream_t, int);
+#ifndef LSEC_INSTANTIATING_PATMAGIC
+LSEC_DECLARE_PATMAGIC_R(1) LSEC_DECLARE_PATMAGIC_R(2) LSEC_DECLARE_PATMAGIC_R(3) LSEC_DECLARE_PATMAGIC_R(4)
+LSEC_DECLARE_PATMAGIC_R(5) LSEC_DECLARE_PATMAGIC_R(6) LSEC_DECLARE_PATMAGIC_R(7) LSEC_DECLARE_PATMAGIC_R(8)
 #endif
 
 // instantiated per R in ec_patterns_inst.hip

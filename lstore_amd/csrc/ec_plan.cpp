@@ -768,13 +768,31 @@ int pattern_limits(const lio_erasure_plan_t *p) {
 // Appends one pattern's record and image rows to the host table.  `ids`: its erased logical ids
 // (sorted, distinct; empty: nothing to rebuild); rot: shard index = (logical id - rot) mod n
 // (0 for the patterned call, whose shards are logical chunks).  Takes the plan's mutex.
-int pattern_record(PlanExt *e, const std::vector<int> &ids, int rot, lsec::PatRecord &rec, lsec::gf8::Mat &rows) {
+int pattern_record(PlanExt *e, const std::vector<int> &ids, int rot, lsec::PatRecord &rec, lsec::PatUnused &unused,
+                   lsec::gf8::Mat &rows) {
   const lio_erasure_plan_t *p = &e->pub;
   const int k = p->data_strips, n = k + p->parity_strips;
+  const auto shard_of = [&](int logical) { return static_cast<uint32_t>(((logical - rot) % n + n) % n); };
   std::memset(&rec, 0, sizeof(rec));
+  std::memset(&unused, 0, sizeof(unused));
   rows.clear();
-  if (ids.empty()) return 0;
-  if (p->method == RAID4 && ids[0] >= k) return 0;  // raid4.c:48 leaves lost parity alone
+  // What the magic form sums beside the record's inputs and outputs: the logical ids in neither list, ascending.
+  // Only tables of m <= 8 have room for them, and only those are ever asked for them (decode_magic_limits).
+  const auto note_unused = [&](const std::vector<int> &survivors, const std::vector<int> &erased) {
+    if (n - k > lsec::kPatMaxUnused) return;
+    for (int c = 0; c < n; ++c)
+      if (std::find(survivors.begin(), survivors.end(), c) == survivors.end() &&
+          std::find(erased.begin(), erased.end(), c) == erased.end())
+        unused.sel[unused.n++] = shard_of(c);
+  };
+  // nothing to rebuild (raid4.c:48 leaves lost parity alone): the plain kernels leave at nout == 0; the magic
+  // form's checksum-only path reads the data chunks as its inputs and the parity as its unused survivors
+  if (ids.empty() || (p->method == RAID4 && ids[0] >= k)) {
+    std::vector<int> data(k);
+    for (int j = 0; j < k; ++j) rec.in_sel[j] = shard_of(data[j] = j);
+    note_unused(data, {});
+    return 0;
+  }
   if (static_cast<int>(ids.size()) > lsec::kPatMaxOut)
     return fail("per-stripe patterns: %zu erasures in one pattern exceed %d", ids.size(), lsec::kPatMaxOut);
   DecodeEntry *ent = nullptr;
@@ -784,8 +802,9 @@ int pattern_record(PlanExt *e, const std::vector<int> &ids, int rot, lsec::PatRe
   }
   // (entries are never moved or freed before the plan is destroyed: decode_entry)
   rec.nout = static_cast<uint32_t>(ent->dp.erased.size());
-  for (int j = 0; j < k; ++j) rec.in_sel[j] = static_cast<uint32_t>(((ent->dp.survivors[j] - rot) % n + n) % n);
-  for (uint32_t r = 0; r < rec.nout; ++r) rec.out_sel[r] = static_cast<uint32_t>(((ent->dp.erased[r] - rot) % n + n) % n);
+  for (int j = 0; j < k; ++j) rec.in_sel[j] = shard_of(ent->dp.survivors[j]);
+  for (uint32_t r = 0; r < rec.nout; ++r) rec.out_sel[r] = shard_of(ent->dp.erased[r]);
+  note_unused(std::vector<int>(ent->dp.survivors.begin(), ent->dp.survivors.begin() + k), ent->dp.erased);
   rows = ent->dp.rows;
   return 0;
 }
@@ -868,9 +887,10 @@ int fill_pattern_table(PlanExt *e, PatternLists &pl, PatternTable &tab) {
   const size_t np = lists.size();
   std::vector<lsec::gf8::Mat> rows(np);
   tab.recs.assign(np, lsec::PatRecord());
+  tab.unused.assign(np, lsec::PatUnused());
   tab.rmax = 0;
   for (size_t i = 0; i < np; ++i) {
-    if (pattern_record(e, lists[i], rots[i], tab.recs[i], rows[i])) return -1;
+    if (pattern_record(e, lists[i], rots[i], tab.recs[i], tab.unused[i], rows[i])) return -1;
     tab.rmax = std::max(tab.rmax, static_cast<int>(tab.recs[i].nout));
   }
   // one CoefCell[rmax][k] image per entry with something to rebuild; rows past its count are zero cells
@@ -1007,6 +1027,161 @@ int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
   const int n = p->data_strips + p->parity_strips;
   return enqueue_patterns(e, *tab, dv, devs, nstripes, C, nullptr, pattern_rot0(n, n_shift, first_stripe),
                           static_cast<uint32_t>(n_shift % n), false, st);
+}
+
+// ---------------------------------------------------------------- patterned decode with the stripe magics
+// lsec_decode_magic_dev_patterns / _rotated: the plain calls' table, launches and split, with the MG
+// kernels (ec_kernels.h, PatternMagicArgs) over 16 bytes per stripe of accumulators from the
+// stream-ordered allocator -- zeroed before the first launch, advancing by 2 * s0 words per launch,
+// freed on the stream -- and one finalize launch behind the tile launches.  The table is the plain
+// calls' own cache entry; the unused-survivor records it carries are uploaded at the first magic call
+// on a device and cached with it.  Every refusal names the call; all of them come before the first
+// HIP call.
+int named(const char *name, int rc) {
+  if (rc) {
+    const std::string why = tl_err;  // the shared rule's message, behind the call's name
+    fail("%s: %s", name, why.c_str());
+  }
+  return rc;
+}
+
+int decode_magic_limits(const lio_erasure_plan_t *p, const char *name) {
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("%s needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d", name,
+                JE_method[p->method], p->w, kind);
+  if (p->data_strips < 1 || p->data_strips > lsec::kMaxK)
+    return fail("%s: k=%d outside 1..%d", name, p->data_strips, lsec::kMaxK);
+  if (p->parity_strips < 1 || p->parity_strips > lsec::kPatMaxUnused)
+    return fail("%s: m=%d outside 1..%d (the survivors a pattern's decode does not read, and the 32-bit lane sums)", name,
+                p->parity_strips, lsec::kPatMaxUnused);
+  return 0;
+}
+
+namespace {
+
+int magic_check_args(const char *name, const MagicCheck &mc, int nstripes) {
+  if (nstripes > 0 && !mc.magic) return fail("%s: magic is NULL", name);
+  if (mc.bad && !mc.expect) return fail("%s: bad is given without expect (there is nothing to compare with)", name);
+  if (mc.bad_count && !mc.expect) return fail("%s: bad_count is given without expect (there is nothing to compare with)", name);
+  if (reinterpret_cast<uintptr_t>(mc.bad_count) % 4 != 0)
+    return fail("%s: bad_count %p is not a multiple of 4 bytes (one 32-bit word)", name, static_cast<const void *>(mc.bad_count));
+  return 0;
+}
+
+// the table's unused-survivor records on the current device: uploaded once, cached with the table
+int pattern_unused_dev(PlanExt *e, const PatternTable *ctab, const lsec::PatUnused **out) {
+  int dev = 0;
+  HIP_OK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  PatternTable &tab = *const_cast<PatternTable *>(ctab);  // (a node of the plan's own map, guarded by its mutex)
+  const void *p = tab.dev_unused.find(dev);
+  if (!p && tab.dev_unused.get(dev, tab.unused.data(), sizeof(lsec::PatUnused) * tab.unused.size(),
+                               "hipMemcpy(unused survivors)", nullptr, &p))
+    return -1;
+  *out = static_cast<const lsec::PatUnused *>(p);
+  return 0;
+}
+
+// enqueue_patterns for the MG kernels.  A table whose patterns are all empty still launches (one row:
+// its tiles only checksum).
+int enqueue_patterns_magic(PlanExt *e, const char *name, const PatternTable &tab, const PatternTable::Dev &dv,
+                           const lsec::PatUnused *unused, const lsec_shard_t *sh, int nstripes, long long C,
+                           const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, const MagicCheck &mc,
+                           hipStream_t st) {
+  const lio_erasure_plan_t *p = &e->pub;
+  const int n = p->data_strips + p->parity_strips;
+  if (nstripes <= 0) return 0;
+  const bool rotates = !stripe_pattern;
+  const int rmax = std::max(1, tab.rmax);
+  lsec::PatternMagicArgs a;
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  a.recs = dv.recs;
+  a.cells = dv.cells;
+  a.unused = unused;
+  a.npat = static_cast<uint32_t>(tab.recs.size());
+  a.K = p->data_strips;
+  a.packet = p->packet_size;
+  a.nshards = n;
+  a.size = C;
+  a.rot_step = rot_step;
+  a.rot_n = rotates ? static_cast<uint32_t>(n) : 0;
+  const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
+  unsigned long long *acc = nullptr;
+  hipError_t err = hipMallocAsync(reinterpret_cast<void **>(&acc), 16ull * nstripes, st);
+  if (err == hipSuccess && (err = hipMemsetAsync(acc, 0, 16ull * nstripes, st)) != hipSuccess) (void)hipFreeAsync(acc, st);
+  if (err != hipSuccess) return fail("%s: the magic accumulators (%llu bytes): %s", name, 16ull * nstripes, hipGetErrorString(err));
+  int rc = 0;
+  if (mc.bad_count && (err = hipMemsetAsync(mc.bad_count, 0, sizeof(unsigned), st)) != hipSuccess)
+    rc = fail("%s: zeroing bad_count: %s", name, hipGetErrorString(err));
+  if (rc == 0)
+    rc = for_launches(nstripes, launch_stripes(C, true), [&](long long s0, int ns) {
+      a.nstripes = ns;
+      for (int i = 0; i < n; ++i) a.sh[i] = shard_from(sh[i], s0);
+      a.stripe_pattern = stripe_pattern ? stripe_pattern + s0 : nullptr;
+      a.rot0 = rotates ? rot0_from(rot0, rot_step, n, s0) : 0;
+      a.magic_acc = acc + 2 * s0;
+      const hipError_t le = sliced ? lsec::launch_pattern_magic_bitsliced(a, rmax, st) : lsec::launch_pattern_magic_bytewise(a, rmax, st);
+      if (le != hipSuccess) return fail("%s: kernel launch failed: %s", name, hipGetErrorString(le));
+      return 0;
+    });
+  if (rc == 0) {
+    err = lsec::launch_pattern_magic_finalize(acc, stripe_pattern, a.npat, nstripes, static_cast<int64_t>(n) * C, mc.magic,
+                                              mc.expect, mc.bad, mc.bad_count, st);
+    if (err != hipSuccess) rc = fail("%s: finalize launch failed: %s", name, hipGetErrorString(err));
+  }
+  err = hipFreeAsync(acc, st);
+  if (err != hipSuccess && rc == 0) rc = fail("%s: freeing the magic accumulators: %s", name, hipGetErrorString(err));
+  return rc;
+}
+
+}  // namespace
+
+int decode_magic_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
+                              const unsigned char *stripe_pattern, const MagicCheck &mc, hipStream_t st) {
+  static const char name[] = "lsec_decode_magic_dev_patterns";
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  if (!patterns) return fail("%s: patterns is NULL", name);
+  if (nstripes < 0) return fail("%s: nstripes %d is negative", name, nstripes);
+  if (nstripes > 0 && !stripe_pattern) return fail("%s: stripe_pattern is NULL", name);
+  if (named(name, pattern_limits(p) || check_geometry(p, C) ? -1 : 0)) return -1;
+  {
+    PatternLists pl;  // the lists' own refusals, ahead of the magic's (pattern_table_dev parses them again)
+    if (named(name, parse_pattern_lists(p, patterns, npatterns, nullptr, 0, pl))) return -1;
+  }
+  if (magic_check_args(name, mc, nstripes)) return -1;
+  const PatternTable *tab = nullptr;
+  PatternTable::Dev dv;
+  const lsec::PatUnused *unused = nullptr;
+  if (named(name, pattern_table_dev(e, patterns, npatterns, nullptr, 0, &tab, &dv)) || named(name, pattern_unused_dev(e, tab, &unused)))
+    return -1;
+  return enqueue_patterns_magic(e, name, *tab, dv, unused, sh, nstripes, C, stripe_pattern, 0, 0, mc, st);
+}
+
+int decode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
+                             long long first_stripe, const MagicCheck &mc, hipStream_t st) {
+  static const char name[] = "lsec_decode_magic_dev_rotated";
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  if (!lost) return fail("%s: lost is NULL", name);
+  if (nstripes < 0) return fail("%s: nstripes %d is negative", name, nstripes);
+  if (n_shift < 0) return fail("%s: n_shift %d is negative", name, n_shift);
+  if (first_stripe < 0) return fail("%s: first_stripe %lld is negative", name, first_stripe);
+  if (named(name, pattern_limits(p) || check_geometry(p, C) ? -1 : 0)) return -1;
+  {
+    PatternLists pl;
+    if (named(name, parse_pattern_lists(p, nullptr, 0, lost, n_shift, pl))) return -1;
+  }
+  if (magic_check_args(name, mc, nstripes)) return -1;
+  const PatternTable *tab = nullptr;
+  PatternTable::Dev dv;
+  const lsec::PatUnused *unused = nullptr;
+  if (named(name, pattern_table_dev(e, nullptr, 0, lost, n_shift, &tab, &dv)) || named(name, pattern_unused_dev(e, tab, &unused)))
+    return -1;
+  const int n = p->data_strips + p->parity_strips;
+  return enqueue_patterns_magic(e, name, *tab, dv, unused, devs, nstripes, C, nullptr, pattern_rot0(n, n_shift, first_stripe),
+                                static_cast<uint32_t>(n_shift % n), mc, st);
 }
 
 // ---------------------------------------------------------------- check / locate, rotated or not
@@ -1975,7 +2150,7 @@ int lsec_test_apply_path(void) { return tl_apply_path; }
 // Test hook, not in include/: the kernel forms (ec_kernels.h, LaunchForm) that the calling thread's last
 // lsec_check_dev, lsec_locate_dev, lsec_decode_dev_patterns, lsec_decode_dev_rotated,
 // lsec_check_dev_rotated, lsec_locate_dev_rotated, lsec_update_dev, lsec_encode_dev_rotated,
-// lsec_update_dev_rotated or lsec_update_dev_masked(_rotated) launched, in order: a locate with repair its
+// lsec_update_dev_rotated, lsec_update_dev_masked(_rotated) or lsec_decode_magic_dev_patterns / _rotated launched, in order: a locate with repair its
 // patterned decode too, a split call every launch; the finalize launch, which has one form, is not
 // among them.  forms: 8 ints each (family, bit-sliced, R, KC, IT, VW, BF, DW).  Returns the number
 // of launches; at most min(that, max_forms, 16) are written.
@@ -2040,6 +2215,45 @@ int lsec_test_predict_masked_magic_form(int plan_kernel, int K, int R, int packe
   return 0;
 }
 
+// Test hook, not in include/ (no GPU): the form (family 12 of the launch record) lsec_decode_magic_dev_patterns and
+// lsec_decode_magic_dev_rotated launch for a plan of kernel 1 or 2 with K inputs and a table of at most R erasures
+// per pattern (a table of empty patterns launches the one-row form), from the function the dispatch calls.
+int lsec_test_predict_pattern_magic_form(int plan_kernel, int K, int R, int packet, int *form) {
+  if (!form) return fail("lsec_test_predict_pattern_magic_form: NULL output");
+  if (plan_kernel != KBYTEWISE && plan_kernel != KBITSLICED)
+    return fail("lsec_test_predict_pattern_magic_form: plan kernel %d", plan_kernel);
+  lsec::LaunchForm f;
+  if (!lsec::predict_pattern_magic_launch(plan_kernel == KBITSLICED, K, R, packet, &f))
+    return fail("lsec_test_predict_pattern_magic_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
+  const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
+  std::memcpy(form, v, sizeof(v));
+  return 0;
+}
+
+// Test hook, not in include/ (no GPU): what the magic form adds to entry pattern_id of the table of
+// lsec_test_pattern_table (same arguments): *nout its erasure count (0: the checksum-only path; -1: a rotation that
+// cannot occur), in_sel[0..k) the shard indices it loads as inputs (for nout 0 too: the data chunks),
+// out_sel[0..nout), and unused[0..return value) the survivors it loads for the checksum alone.  Returns their
+// count, or -1 with a message.
+int lsec_test_pattern_unused(lio_erasure_plan_t *plan, const int *patterns, int npatterns, const int *lost, int n_shift,
+                             int pattern_id, int *nout, int *in_sel, int *out_sel, int *unused) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!nout || !in_sel || !out_sel || !unused) return fail("lsec_test_pattern_unused: NULL output");
+  if (decode_magic_limits(plan, "lsec_test_pattern_unused")) return -1;
+  PatternTable tab;
+  if (build_pattern_table(e, patterns, npatterns, lost, n_shift, tab)) return -1;
+  if (pattern_id < 0 || pattern_id >= static_cast<int>(tab.recs.size()))
+    return fail("lsec_test_pattern_unused: entry %d outside 0..%zu", pattern_id, tab.recs.size() - 1);
+  const lsec::PatRecord &rec = tab.recs[pattern_id];
+  const lsec::PatUnused &un = tab.unused[pattern_id];
+  *nout = tab.reachable[pattern_id] ? static_cast<int>(rec.nout) : -1;
+  for (int j = 0; j < plan->data_strips; ++j) in_sel[j] = static_cast<int>(rec.in_sel[j]);
+  for (uint32_t r = 0; r < rec.nout; ++r) out_sel[r] = static_cast<int>(rec.out_sel[r]);
+  for (uint32_t u = 0; u < un.n; ++u) unused[u] = static_cast<int>(un.sel[u]);
+  return static_cast<int>(un.n);
+}
+
 // Test hook, not in include/ (no GPU): the K that have fixed-K forms (LSEC_FIXED_K), ascending
 int lsec_test_fixed_k(int *out, int max) { return lsec::fixed_k_list(out, max); }
 
@@ -2053,8 +2267,9 @@ void lsec_test_set_cauchy8_policy(int mode) { g_c8_policy.store(mode == 1 ? 1 : 
 void lsec_test_set_tile_phase(int mode) { lsec::set_tile_phase(mode); }
 
 // Test hook, not in include/: a patterned call (and lsec_update_dev, lsec_encode_dev_rotated,
-// lsec_update_dev_rotated and lsec_update_dev_masked(_rotated)) launches at most `stripes` stripes at a time
-// (0, the default: only the 32-bit tile limit splits), so a small batch exercises the split.
+// lsec_update_dev_rotated, lsec_update_dev_masked(_rotated) and lsec_decode_magic_dev_patterns / _rotated) launches at
+// most `stripes` stripes at a time (0, the default: only the 32-bit tile limit splits), so a small batch exercises
+// the split.
 void lsec_test_set_pattern_split(int stripes) { g_pattern_split.store(std::max(0, stripes), std::memory_order_relaxed); }
 
 // Test hook, not in include/ (no GPU): entry pattern_id of the table the host builds for

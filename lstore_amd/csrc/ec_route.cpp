@@ -638,6 +638,35 @@ int lsec_decode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
   return decode_dev_rotated(e, devs, nstripes, block_size, lost, n_shift, first_stripe, static_cast<hipStream_t>(stream));
 }
 
+// (the call's own limits first -- plan kernel, k, m -- then the plain call's ladder, every message behind the call's name)
+int lsec_decode_magic_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
+                                   const int *patterns, int npatterns, const unsigned char *stripe_pattern, void *magic,
+                                   const void *expect, unsigned char *bad, unsigned int *bad_count, void *stream) {
+  static const char name[] = "lsec_decode_magic_dev_patterns";
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (decode_magic_limits(plan, name)) return -1;
+  if (!shards) return fail("%s: shards is NULL", name);
+  if (named(name, check_shards(plan, shards, nstripes))) return -1;
+  const MagicCheck mc = {static_cast<uint8_t *>(magic), static_cast<const uint8_t *>(expect), bad, bad_count};
+  return decode_magic_dev_patterns(e, shards, nstripes, block_size, patterns, npatterns, stripe_pattern, mc,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int lsec_decode_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                                  const int *lost, int n_shift, long long first_stripe, void *magic, const void *expect,
+                                  unsigned char *bad, unsigned int *bad_count, void *stream) {
+  static const char name[] = "lsec_decode_magic_dev_rotated";
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (decode_magic_limits(plan, name)) return -1;
+  if (!devs) return fail("%s: devs is NULL", name);
+  if (named(name, check_shards(plan, devs, nstripes))) return -1;
+  const MagicCheck mc = {static_cast<uint8_t *>(magic), static_cast<const uint8_t *>(expect), bad, bad_count};
+  return decode_magic_dev_rotated(e, devs, nstripes, block_size, lost, n_shift, first_stripe, mc,
+                                  static_cast<hipStream_t>(stream));
+}
+
 int lsec_check_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
                            int n_shift, long long first_stripe, unsigned int *syndrome, unsigned int *bad_count,
                            void *stream) {

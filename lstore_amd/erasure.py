@@ -85,7 +85,8 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_decode_dev_patterns", "lsec_decode_dev_rotated", "lsec_check_dev", "lsec_locate_dev",
            "lsec_check_dev_rotated", "lsec_locate_dev_rotated", "lsec_update_dev",
            "lsec_encode_dev_rotated", "lsec_update_dev_rotated", "lsec_update_dev_masked",
-           "lsec_update_dev_masked_rotated", "lsec_update_magic_dev_masked", "lsec_update_magic_dev_masked_rotated")
+           "lsec_update_dev_masked_rotated", "lsec_update_magic_dev_masked", "lsec_update_magic_dev_masked_rotated",
+           "lsec_decode_magic_dev_patterns", "lsec_decode_magic_dev_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -166,6 +167,13 @@ def lib():
                                                C.c_int, C.c_void_p, C.c_void_p]
     L.lsec_update_magic_dev_masked_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
                                                        C.c_void_p, C.POINTER(ShardRef), C.c_int, C.c_void_p, C.c_void_p]
+    L.lsec_decode_magic_dev_patterns.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lsec_decode_magic_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
+                                                C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lsec_test_predict_pattern_magic_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.lsec_test_pattern_unused.argtypes = [P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lsec_test_predict_masked_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
     L.lsec_test_predict_masked_magic_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
     L.lsec_test_locate_ratio.argtypes = [P, C.c_int, C.c_int]
@@ -590,6 +598,50 @@ class Plan:
         _check(lib().lsec_decode_dev_rotated(self._p, self.shard_refs(refs), nstripes, block_size, _erasure_array(lost),
                                              n_shift, first_stripe, stream), "lsec_decode_dev_rotated")
 
+    def decode_magic_dev_patterns_refs(self, refs, nstripes: int, block_size: int, patterns, stripe_pattern_ptr: int,
+                                       magic_ptr: int, expect_ptr: int = 0, bad_ptr: int = 0, bad_count_ptr: int = 0,
+                                       stream: int = 0) -> None:
+        """lsec_decode_magic_dev_patterns: decode_dev_patterns_refs, and the 4 bytes at magic_ptr + 4*s (device memory,
+        no alignment; 0: NULL) set to the adler32 of stripe s's k+m chunks as the decode leaves them; a stripe whose
+        pattern id is >= len(patterns) is skipped.  expect_ptr (4 bytes per stripe), bad_ptr (1 byte per stripe) and
+        bad_count_ptr (one aligned uint32): the comparison with the quorum magics, each optional (0)."""
+        patterns = list(patterns)
+        _check(lib().lsec_decode_magic_dev_patterns(self._p, None if refs is None else self.shard_refs(refs), nstripes,
+                                                    block_size, _pattern_array(patterns), len(patterns),
+                                                    stripe_pattern_ptr or None, magic_ptr or None, expect_ptr or None,
+                                                    bad_ptr or None, bad_count_ptr or None, stream),
+               "lsec_decode_magic_dev_patterns")
+
+    def decode_magic_dev_rotated_refs(self, refs, nstripes: int, block_size: int, lost, n_shift: int, first_stripe: int,
+                                      magic_ptr: int, expect_ptr: int = 0, bad_ptr: int = 0, bad_count_ptr: int = 0,
+                                      stream: int = 0) -> None:
+        """lsec_decode_magic_dev_rotated: decode_dev_rotated_refs with the magics of decode_magic_dev_patterns_refs;
+        they are over the LOGICAL stripes, whatever the rotation."""
+        _check(lib().lsec_decode_magic_dev_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes,
+                                                   block_size, _erasure_array(lost), n_shift, first_stripe,
+                                                   magic_ptr or None, expect_ptr or None, bad_ptr or None,
+                                                   bad_count_ptr or None, stream), "lsec_decode_magic_dev_rotated")
+
+    def decode_magic_dev_patterns(self, data, parity, patterns, stripe_pattern, magic, expect=None, bad=None,
+                                  bad_count=None, stream=None) -> None:
+        """torch: decode_dev_patterns, and magic (uint8 device tensor of 4 bytes per stripe, contiguous) set to the
+        stripes' adler32 words as stripe_magic_dev writes them; expect (as magic), bad (uint8 [N]) and bad_count (one
+        32-bit element) compare them with the quorum magics."""
+        refs, n, size = self.tensor_refs(data, parity)
+        if stripe_pattern.dtype.itemsize != 1 or not stripe_pattern.is_cuda or not stripe_pattern.is_contiguous() \
+                or stripe_pattern.numel() != n:
+            raise ValueError("stripe_pattern must be a contiguous uint8 device tensor with one entry per stripe")
+        for what, t in (("magic", magic), ("expect", expect)):
+            if t is not None and (t.dtype.itemsize != 1 or not t.is_cuda or not t.is_contiguous() or t.numel() != 4 * n):
+                raise ValueError(f"{what} must be a contiguous uint8 device tensor of 4 bytes per stripe")
+        if bad is not None and (bad.dtype.itemsize != 1 or not bad.is_cuda or not bad.is_contiguous() or bad.numel() != n):
+            raise ValueError("bad must be a contiguous uint8 device tensor with one entry per stripe")
+        if bad_count is not None and (bad_count.dtype.itemsize != 4 or not bad_count.is_cuda or bad_count.numel() != 1):
+            raise ValueError("bad_count must be a 32-bit device tensor of one element")
+        self.decode_magic_dev_patterns_refs(refs, n, size, patterns, stripe_pattern.data_ptr(), magic.data_ptr(),
+                                            0 if expect is None else expect.data_ptr(), 0 if bad is None else bad.data_ptr(),
+                                            0 if bad_count is None else bad_count.data_ptr(), _stream_handle(stream))
+
     def check_dev_refs(self, refs, nstripes: int, block_size: int, syndrome_ptr: int, bad_count_ptr: int = 0,
                        stream: int = 0) -> None:
         """lsec_check_dev: one-pass parity check.  syndrome_ptr: device address of nstripes uint32 words,
@@ -854,13 +906,18 @@ MASKED_FAMILIES = ("updmask",)
 MAGIC_FAMILIES = ("updmaskmagic",)
 
 
+# and behind those (MAGIC_FAMILIES stays as it is too): family number 12, the patterned decode that leaves the magics
+PATMAGIC_FAMILIES = ("patmagic",)
+
+
 def _form(v) -> Form:
-    return Form((FORM_FAMILIES + MASKED_FAMILIES + MAGIC_FAMILIES)[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
+    return Form((FORM_FAMILIES + MASKED_FAMILIES + MAGIC_FAMILIES + PATMAGIC_FAMILIES)[v[0] - 1], bool(v[1]),
+                *(int(x) for x in v[2:8]))
 
 
 def launch_record() -> list:
     """Test hook: the Forms this thread's last check_dev / locate_dev / decode_dev_patterns / decode_dev_rotated
-    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated / update_dev_masked(_rotated) / update_magic_dev_masked(_rotated) call launched, in order (a locate with repair: its patterned
+    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated / update_dev_masked(_rotated) / update_magic_dev_masked(_rotated) / decode_magic_dev_patterns / decode_magic_dev_rotated call launched, in order (a locate with repair: its patterned
     decode too; a split call: every launch)."""
     buf = (C.c_int * (8 * 16))()
     n = lib().lsec_test_launch_record(buf, 16)
@@ -895,6 +952,16 @@ def predict_masked_magic_form(plan_kernel: int, k: int, rows: int, packet: int =
     out = (C.c_int * 8)()
     _check(lib().lsec_test_predict_masked_magic_form(plan_kernel, k, rows, packet, block_size, out),
            "lsec_test_predict_masked_magic_form")
+    return _form(out)
+
+
+def predict_pattern_magic_form(plan_kernel: int, k: int, rows: int, packet: int = 0) -> Form:
+    """Test hook (no GPU): the Form ("patmagic") decode_magic_dev_patterns_refs and decode_magic_dev_rotated_refs launch
+    for a plan of kernel 1 or 2 with k inputs and a table of at most `rows` erasures per pattern (a table of empty
+    patterns: 1), asked of the function the dispatch itself calls."""
+    out = (C.c_int * 8)()
+    _check(lib().lsec_test_predict_pattern_magic_form(plan_kernel, k, rows, packet, out),
+           "lsec_test_predict_pattern_magic_form")
     return _form(out)
 
 
@@ -944,6 +1011,21 @@ def pattern_table_entry(plan: "Plan", pattern_id: int, patterns=None, lost=None,
                                          C.byref(nout), in_sel, out_sel, coef), "lsec_test_pattern_table")
     e = max(0, nout.value)
     return nout.value, list(in_sel[:k]), list(out_sel[:e]), np.array(coef[:e * k], dtype=np.int32).reshape(e, k)
+
+
+def pattern_unused_entry(plan: "Plan", pattern_id: int, patterns=None, lost=None, n_shift: int = 0):
+    """Test hook (no GPU): what the magic form sums for entry pattern_id of pattern_table_entry's table ->
+    (nout, in_sel [k], out_sel [nout], unused): the shard indices it loads as inputs (nout 0, the checksum-only
+    path: the data chunks), those it rebuilds, and the survivors it loads for the checksum alone."""
+    k, n = plan.k, plan.k + plan.m
+    nout = C.c_int(0)
+    in_sel, out_sel, unused = (C.c_int * k)(), (C.c_int * n)(), (C.c_int * n)()
+    pats = None if patterns is None else list(patterns)
+    nu = _check_nonneg(lib().lsec_test_pattern_unused(plan.ptr, None if pats is None else _pattern_array(pats),
+                                                      0 if pats is None else len(pats),
+                                                      None if lost is None else _erasure_array(lost), n_shift, pattern_id,
+                                                      C.byref(nout), in_sel, out_sel, unused), "lsec_test_pattern_unused")
+    return nout.value, list(in_sel[:k]), list(out_sel[:max(0, nout.value)]), list(unused[:nu])
 
 
 def host_unpin_drain() -> None:
