@@ -28,6 +28,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/lstore_ec.h"
 #include "ec_hiperr.h"
 #include "ec_host.h"
 #include "ec_jit.h"
@@ -489,6 +490,85 @@ int lsec_test_jit_queue(int n, int wait_ms, int R, int K, int w, unsigned seed) 
   }
   for (int i = 0; i < n; ++i) lsec::jit::unbind(stand_in + i);
   return ready;
+}
+
+namespace {
+
+// The network of a test hook's shape (as lsec_test_jit_compile numbers them), or false with the
+// reason recorded under the hook's name `who`.  packet is read for the packet shapes only.
+bool test_net(const char *who, int shape, int R, int K, int w, int packet, lsec::jit::Net *net) {
+  using lsec::jit::Net;
+  if (shape < 0 || shape > 3) return lsec::set_error("%s: shape %d: 0 .. 3", who, shape), false;
+  if (R < 1 || R > lsec::jit::kMaxRows) return lsec::set_error("%s: R %d: 1 .. %d rows", who, R, lsec::jit::kMaxRows), false;
+  if (K < 1 || K > lsec::jit::kMaxCols) return lsec::set_error("%s: K %d: 1 .. %d inputs", who, K, lsec::jit::kMaxCols), false;
+  if (shape == 0 ? w != 8 : shape == 1 ? w != 16 && w != 32 : shape == 2 ? w < 2 || w > 32 : w != 8 && w != 16 && w != 32)
+    return lsec::set_error("%s: w %d: shape %d takes %s", who, w, shape,
+                           shape == 0 ? "8" : shape == 1 ? "16 or 32" : shape == 2 ? "2 .. 32" : "8, 16 or 32"),
+           false;
+  if (shape < 2) {
+    *net = Net::matrix(R, K, w);
+    return true;
+  }
+  if (packet < 4 || packet > (1 << 20)) return lsec::set_error("%s: packet %d: 4 .. %d bytes", who, packet, 1 << 20), false;
+  *net = Net::packets(R, K, w, packet);
+  if (net->D == 0) return lsec::set_error("%s: packet %d: no lane width (pkt_shape: a multiple of 4 bytes)", who, packet), false;
+  return true;
+}
+
+}  // namespace
+
+// Test hook, not in include/ (no GPU): the bytes of a shard (packet networks: column bytes) one
+// block of the shape's network covers per tile (Net::tile_bytes), or -1 on bad arguments, so that
+// tests size their inputs from the engine.
+int lsec_test_jit_tile(int shape, int R, int K, int w, int packet) {
+  lsec::jit::Net net;
+  return test_net("lsec_test_jit_tile", shape, R, K, w, packet, &net) ? net.tile_bytes() : -1;
+}
+
+// Test hook, not in include/ (GPU): run the network of any matrix, alone, by the production route:
+// bound to a stand-in image (never dereferenced), compiled, fetched with ready() and launched
+// through launch / launch_pkt over `in` (K shards) and `out` (R shards); `stream` is synchronised
+// before it returns 0.  `mat`: R*K coefficients (shapes 0, 1, 3; shape 3 expands them by
+// coef_masks as bind_pkt_field does) or R*w*K row masks [(r*w+l)*K + j] (shape 2).  At w = 16 / 32
+// the network covers whole tiles only and nothing follows it.  Every refusal is -1 with a message
+// naming the limit, before the first HIP call; a failed compile is -1 with the compiler's text.
+int lsec_test_jit_run(int shape, int R, int K, int w, int packet, const unsigned *mat, const lsec_shard_t *in,
+                      const lsec_shard_t *out, int nstripes, long long size, void *stream) {
+  static const char *who = "lsec_test_jit_run";
+  lsec::jit::Net net;
+  if (!test_net(who, shape, R, K, w, packet, &net)) return -1;
+  if (!mat || !in || !out) return lsec::set_error("%s: NULL %s", who, !mat ? "mat" : !in ? "in" : "out");
+  if (nstripes < 0) return lsec::set_error("%s: nstripes %d: negative", who, nstripes);
+  if (shape != 2 && w < 32)
+    for (int i = 0; i < R * K; ++i)
+      if (mat[i] >> w) return lsec::set_error("%s: coefficient %d is %u: above %u at w = %d", who, i, mat[i], (1u << w) - 1u, w);
+  const long long unit = shape < 2 ? 8 : static_cast<long long>(w) * packet;
+  if (size < 0 || size % unit)
+    return lsec::set_error("%s: size %lld: not a multiple of %lld bytes (%s)", who, size, unit, shape < 2 ? "8" : "w * packet");
+  std::vector<lsec::ShardRef> bi(K), bo(R);
+  for (int j = 0; j < K; ++j) bi[j] = {reinterpret_cast<uint64_t>(in[j].base), in[j].stride};
+  for (int r = 0; r < R; ++r) bo[r] = {reinterpret_cast<uint64_t>(out[r].base), out[r].stride};
+  if (shape >= 2 && !lsec::jit::pkt_aligned(bi.data(), K, bo.data(), R, w, packet))
+    return lsec::set_error("%s: a base or stride is not a multiple of the lane width, %d bytes (pkt_aligned)", who, 4 * net.D);
+  const std::vector<uint32_t> m = shape == 3 ? lsec::jit::coef_masks(mat, R, K, w) : std::vector<uint32_t>(mat, mat + net.words());
+  char stand_in;  // this call's own image address
+  lsec::jit::bind_net(&stand_in, net, m.data());
+  int rc = 0;
+  if (!lsec::jit::wait(&stand_in, 900 * 1000)) {
+    std::lock_guard<std::mutex> lk(lsec::jit::g_mu);
+    const auto &e = lsec::jit::g_by_image.at(&stand_in);
+    rc = lsec::set_error("%s: %s", who, e->state == lsec::jit::Entry::kCompiling ? "the compile took too long" : e->err.c_str());
+  } else if (hipFunction_t fn = lsec::jit::ready(&stand_in, R, K)) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t err = shape < 2 ? lsec::jit::launch(fn, R, K, bi.data(), bo.data(), nstripes, size, st, w)
+                               : lsec::jit::launch_pkt(fn, R, K, bi.data(), bo.data(), nstripes, size, packet, w, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) rc = lsec::set_error("%s: launch failed: %s", who, hipGetErrorString(err));
+  } else {
+    rc = lsec::set_error("%s: the compiled network did not load on this device", who);
+  }
+  lsec::jit::unbind(&stand_in);
+  return rc;
 }
 
 }  // extern "C"

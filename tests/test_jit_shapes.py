@@ -65,11 +65,13 @@ sys.exit(1 if bad else 0)
 
 @pytest.mark.parametrize("variant,pick", [
     (0x80000, lambda s: s[0] == 1 and s[3] == 32),    # w = 32 split off: the one-wave form at 4+ rows
-    (0x380000, lambda s: s[0] == 1 and s[1] >= 4),    # split: no prefetch, tree folds
+    (0x380000, lambda s: s[0] == 1 and s[1] >= 4),    # split off (bit 19): the one-wave form with serial folds (bit 21)
     (0x1000000, lambda s: s[0] == 1 and s[3] == 16),  # w = 16 split off
-    (0x2000000, lambda s: s[0] >= 2),                 # packet networks in 2 output groups
+    (0x2000000, lambda s: s[0] >= 2),                 # packet networks: one output group, forced (bits 25-26 = 1)
     (0x9, lambda s: s[0] == 0),                       # w = 8: uncapped pairs (bit 0), no pairs (bit 3)
     (0x28, lambda s: s[0] == 0),                      # w = 8: 2-dword lanes, no pairs
+    (0x4000000, lambda s: s[0] >= 2),                 # packet networks in 2 output groups (bits 25-26 = 2)
+    (0x300000, lambda s: s[0] == 1 and s[1] >= 4),    # split: no prefetch (bit 20), tree folds (bit 21)
 ])
 def test_knob_shapes_compile(built, variant, pick):
     shapes = [s for s in SHAPES if pick(s)]
