@@ -354,6 +354,64 @@ int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
                             unsigned int *counts, unsigned int *dev_faults,
                             int flags, void *stream);
 
+/* The scrub's two questions in one pass: is the parity of each stripe consistent with its data
+ * (lsec_check_dev's syndrome word), and are these the bytes that were written (the stripe's adler32
+ * "magic", below, against the quorum magic stored in front of the chunks: jerase_control_check,
+ * je_cksum_compare)?  The two do not catch the same faults -- a stale but self-consistent stripe (a
+ * lost full-stripe write) has syndrome 0 and the wrong magic; with m = 2 two corrupt chunks can
+ * imitate a third under the parity check -- and as lsec_check_dev followed by lsec_stripe_magic_dev
+ * they cost 2(k+m) chunk reads per stripe.  Here the check's tiles, which hold every byte of the
+ * stripe in registers, sum the magic too: k+m chunk reads.  The rotated call is also the one way to
+ * get the magics of a rotated LUN on the device (what a caller of lsec_encode_dev_rotated must
+ * store).  Purely additive too: the version stays 3, a caller detects the calls by their symbols.
+ *
+ * - shards, devs, n_shift and first_stripe mean exactly what they mean for lsec_check_dev /
+ *   lsec_check_dev_rotated.  Every chunk is only read, exactly once; nothing proportional to the
+ *   data is written.
+ * - syndrome[s] (nstripes 32-bit words, 4-byte aligned, required with nstripes > 0): exactly the
+ *   word lsec_check_dev / lsec_check_dev_rotated produces for stripe s.  The call sets it; it does
+ *   not add to it.
+ * - `magic` is device memory, 4*nstripes bytes, no alignment requirement, pure output, required
+ *   with nstripes > 0.  Word s is the 4 little-endian bytes of zlib's adler32 over the k+m chunks of
+ *   stripe s in LOGICAL order (for the rotated call: after un-rotating), exactly as
+ *   lsec_stripe_magic_dev writes it.  An inconsistent stripe gets the adler32 of exactly the bytes
+ *   stored: the call judges nothing but the syndrome and `expect`.
+ * - `expect` is optional (NULL): device memory, 4*nstripes bytes, no alignment requirement, only
+ *   read: the quorum magics.
+ * - `bad` is optional (NULL), with or without expect: nstripes bytes, no alignment requirement.
+ *   bad[s] = LSEC_SCRUB_BAD_PARITY when syndrome[s] != 0, OR'ed with LSEC_SCRUB_BAD_MAGIC when
+ *   expect is given and magic[s] != expect[s].  Without expect only the parity bit can appear.
+ * - `counts` is optional (NULL): two 32-bit words, 4-byte aligned.  counts[0] is the number of
+ *   stripes with a nonzero syndrome, counts[1] the number whose magic differs from expect (0
+ *   without expect).  The call sets both; it does not add to them.
+ * - The outputs must not overlap one another or the shards.
+ * - Scratch: the per-stripe accumulators, 16 bytes per stripe, come from the stream-ordered
+ *   allocator (hipMallocAsync on `stream`), are zeroed there and go back to it on the stream,
+ *   exactly as lsec_encode_magic_dev's do.  Nothing is uploaded: the kernels index the plan's
+ *   cached encode image.
+ * - n_shift == 0 behaves exactly as the unrotated call.
+ * - nstripes == 0 validates the arguments, returns 0 and touches no GPU; all outputs may then be
+ *   NULL.  Where lsec_check_dev accepts block_size == 0, every magic word comes out as 1 (adler32
+ *   of nothing) and every syndrome as 0.
+ * - Plans and limits are those of lsec_check_dev: lsec_plan_kernel 1 and 2, k <= 64, 1 <= m <= 8.
+ *   Layout, alignment and block_size rules are those of lsec_check_dev.
+ * - Everything lsec_check_dev / lsec_check_dev_rotated refuses is refused, in its order; behind
+ *   those a NULL magic with nstripes > 0 and a misaligned counts.  Each returns -1 with a message
+ *   for lsec_last_error that names this call and the limit, and nothing is enqueued: every
+ *   argument check comes before the first HIP call.  There is no fallback to two passes.
+ * Enqueued on `stream`; return without synchronising.  0 / -1. */
+#define LSEC_SCRUB_BAD_PARITY 1   /* bad[s]: syndrome[s] != 0 */
+#define LSEC_SCRUB_BAD_MAGIC  2   /* bad[s]: magic[s] != expect[s] */
+
+int lsec_check_magic_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
+                         long long block_size, unsigned int *syndrome, void *magic,
+                         const void *expect, unsigned char *bad, unsigned int *counts, void *stream);
+
+int lsec_check_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                                 long long block_size, int n_shift, long long first_stripe,
+                                 unsigned int *syndrome, void *magic, const void *expect,
+                                 unsigned char *bad, unsigned int *counts, void *stream);
+
 /* Parity update for a partial-stripe write, one pass: c of a stripe's k data chunks change, and the
  * parity follows without the other k - c chunks being read, or even being on the device.  Purely
  * additive too: the version stays 3, a caller detects the call by its symbol.

@@ -271,6 +271,12 @@ int decode_magic_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, 
                               const unsigned char *stripe_pattern, const MagicCheck &mc, hipStream_t st);
 int decode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
                              long long first_stripe, const MagicCheck &mc, hipStream_t st);
+// the check, and magic[s] = adler32 of stripe s's k+m logical chunks as stored; expect / bad / bad_count (here the
+// two words [parity-bad, magic-bad]): the verdicts, all optional
+int check_magic_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, const MagicCheck &mc,
+                    hipStream_t st);
+int check_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                            unsigned *syndrome, const MagicCheck &mc, hipStream_t st);
 void fp_encode_block(lio_erasure_plan_t *p, char **ptr, int block_size);         // ec_route.cpp
 int fp_dummy(lio_erasure_plan_t *);                                            // ec_route.cpp
 int encode_stripes_impl(PlanExt *e, char **ptrs, int nstripes, long long C);  // ec_route.cpp

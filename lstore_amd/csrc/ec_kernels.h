@@ -275,7 +275,45 @@ struct LocateRotArgs : CheckRotArgs {
   unsigned long long *hyp;
 };
 
-// What tells the four argument structs apart, to the host's launch path and to the kernels' tile
+// The check that also leaves each stripe's adler32 magic (lsec_check_magic_dev / _rotated): the scrub's
+// "is the parity consistent" and "are these the bytes that were written" from one read of the k + m
+// chunks.  A check tile holds every byte of its part of the stripe in registers -- the K data units
+// as they are loaded and the R stored parity units -- so the MG kernels (k_chkmagic_*, k_chkmagicrot_*:
+// the check's tile bodies under `if constexpr (MG)`) sum them into one MagicLane at their LOGICAL chunk
+// ids (j, K + r; for the rotated struct whatever device ChkShards fetched them from) and commit once
+// per tile into magic_acc[2s], [2s + 1] (zeroed before the first launch).  The syndrome words are the
+// check's.  The tile launches are given no bad_count: launch_check_magic_finalize folds the sums into
+// the magic words, compares and counts.  The structs derive from CheckArgs / CheckRotArgs, whose
+// layouts -- and with them every k_chk_*, k_loc_* kernel -- stay as they are.
+struct CheckMagicArgs : CheckArgs {
+  unsigned long long *magic_acc;  // 2 per stripe of this launch (8-byte aligned device memory)
+};
+struct CheckMagicRotArgs : CheckRotArgs {
+  unsigned long long *magic_acc;  // as CheckMagicArgs
+};
+static_assert(sizeof(CheckMagicArgs) == sizeof(CheckArgs) + 8, "CheckMagicArgs layout");
+static_assert(sizeof(CheckMagicRotArgs) == sizeof(CheckRotArgs) + 8, "CheckMagicRotArgs layout");
+static_assert(sizeof(CheckMagicArgs) < 4096 && sizeof(CheckMagicRotArgs) < 4096,
+              "CheckMagicArgs / CheckMagicRotArgs: under the 4 KiB of kernel arguments");
+
+// As launch_scrub_*, and magic_acc != NULL.  The launch shapes are chkmagic_bytewise_form and the
+// check's lane dwords.
+template <typename Args>
+hipError_t launch_check_magic_bytewise(const Args &a, hipStream_t stream);
+template <typename Args>
+hipError_t launch_check_magic_bitsliced(const Args &a, hipStream_t stream, int dw_pref = 0);
+constexpr unsigned kScrubBadParity = 1, kScrubBadMagic = 2;  // LSEC_SCRUB_BAD_PARITY / _MAGIC (lstore_ec.h)
+// One launch per call, behind the tile launches, one thread per stripe of the whole call: the 4
+// little-endian bytes at magic + 4s (no alignment) become A = (1 + acc[2s]) mod 65521,
+// B = (total_len + acc[2s + 1]) mod 65521.  bad[s] (may be null; no alignment) = kScrubBadParity when
+// syndrome[s] != 0, | kScrubBadMagic when expect (may be null; 4 bytes per stripe, no alignment) is
+// given and differs from the word.  counts (may be null; two words, zeroed by the caller): [0] the
+// stripes with a nonzero syndrome, [1] those whose magic differs from expect.
+hipError_t launch_check_magic_finalize(const unsigned long long *acc, const unsigned *syndrome, int nstripes,
+                                       int64_t total_len, uint8_t *magic, const uint8_t *expect, uint8_t *bad,
+                                       unsigned *counts, hipStream_t stream);
+
+// What tells the argument structs apart, to the host's launch path and to the kernels' tile
 // bodies alike: a locate struct adds ratio and hyp, a rotated one takes its refs from sh.
 template <typename Args>
 constexpr bool kLocArgs = std::is_same<Args, LocateArgs>::value || std::is_same<Args, LocateRotArgs>::value;
@@ -467,7 +505,7 @@ hipError_t launch_update_magic_finalize(const unsigned long long *acc, const uns
 // functions record the form at the one place where the template arguments are known; the record
 // is the calling thread's, holds the launches since launch_record_reset() in order (the engine
 // resets it on entry to each of those calls) and costs a few host stores per launch.
-enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic, kFormPatMagic };
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic, kFormPatMagic, kFormChkMagic, kFormChkMagicRot };
 struct LaunchForm {
   int family, sliced, R, KC, IT, VW, BF, DW;
 };
@@ -485,6 +523,8 @@ bool predict_masked_launch(bool sliced, int K, int R, int packet, int dw_pref, L
 bool predict_masked_magic_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // and for the patterned decode with the magic (kFormPatMagic; R: the table's rmax, at least 1)
 bool predict_pattern_magic_launch(bool sliced, int K, int R, int packet, LaunchForm *out);
+// and for the check with the magic (kFormChkMagic, or kFormChkMagicRot with `rotated`)
+bool predict_check_magic_launch(bool rotated, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // the K with fixed-K forms (LSEC_FIXED_K), ascending -> how many there are; out[0 .. min(that, max))
 int fixed_k_list(int *out, int max);
 

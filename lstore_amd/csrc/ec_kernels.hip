@@ -513,6 +513,39 @@ hipError_t launch_scrub_bitsliced(const Args &a, hipStream_t st, int dw_pref) {
 LSEC_SCRUB_LAUNCHES(CheckArgs) LSEC_SCRUB_LAUNCHES(LocateArgs) LSEC_SCRUB_LAUNCHES(CheckRotArgs) LSEC_SCRUB_LAUNCHES(LocateRotArgs)
 #undef LSEC_SCRUB_LAUNCHES
 
+// ------------------------------------------------------------------ the check that also leaves the stripe magics
+namespace {
+// dwords per lane of a bit-sliced check with the magic (more than kChkMagicWideRows rows: one)
+int check_magic_lane_dwords(int R, int dw_pref, int packet) { return lane_dwords(R <= kChkMagicWideRows ? dw_pref : 1, packet); }
+}  // namespace
+
+template <typename Args>
+hipError_t launch_check_magic_bytewise(const Args &a, hipStream_t st) {
+  if (!scrub_args_ok(a) || !a.magic_acc) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const BwForm f = chkmagic_bytewise_form(a.K, a.R);
+  const int grid = tile_grid(BwShape{f.it, f.vw, f.bf}.tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_chkmagic_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+template <typename Args>
+hipError_t launch_check_magic_bitsliced(const Args &a, hipStream_t st, int dw_pref) {
+  if (!scrub_args_ok(a) || !a.magic_acc || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int dw = check_magic_lane_dwords(a.R, dw_pref, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_chkmagic_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+}
+
+#define LSEC_CHKMAGIC_LAUNCHES(ARGS)                                                     \
+  template hipError_t launch_check_magic_bytewise<ARGS>(const ARGS &, hipStream_t);      \
+  template hipError_t launch_check_magic_bitsliced<ARGS>(const ARGS &, hipStream_t, int);
+LSEC_CHKMAGIC_LAUNCHES(CheckMagicArgs) LSEC_CHKMAGIC_LAUNCHES(CheckMagicRotArgs)
+#undef LSEC_CHKMAGIC_LAUNCHES
+
 hipError_t launch_locate_finalize(const unsigned *syndrome, unsigned long long *hyp, unsigned char *located,
                                   unsigned *counts, int nstripes, int K, int R, hipStream_t st) {
   if (!syndrome || !hyp || !located || K < 1 || K > kMaxK || R < 2 || R > 8) return hipErrorInvalidValue;
@@ -777,6 +810,19 @@ bool predict_pattern_magic_launch(bool sliced, int K, int R, int packet, LaunchF
   return true;
 }
 
+bool predict_check_magic_launch(bool rotated, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out) {
+  if (K < 1 || K > kMaxK || R < 1 || R > 8) return false;
+  const int family = rotated ? kFormChkMagicRot : kFormChkMagic;
+  if (sliced) {
+    if (packet <= 0 || packet % 4 != 0) return false;
+    *out = LaunchForm{family, 1, R, 0, 0, 0, 0, check_magic_lane_dwords(R, dw_pref, packet)};
+    return true;
+  }
+  const BwForm f = chkmagic_bytewise_form(K, R);
+  *out = LaunchForm{family, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
+  return true;
+}
+
 int fixed_k_list(int *out, int max) {
   int n = 0;
 #define LSEC_LIST_K(KK)     \
@@ -888,6 +934,34 @@ __global__ void k_pattern_magic_finalize(const unsigned long long *acc, const ui
   const bool differs = want != m;
   if (bad) bad[s] = differs ? 1 : 0;
   if (bad_count && differs) atomicAdd(bad_count, 1u);
+}
+
+// The check's magics and verdicts (launch_check_magic_finalize, ec_kernels.h): acc holds each stripe's
+// sums, per-tile values in [0, M) added up.  magic, expect and bad have no alignment: bytewise.
+__global__ void k_check_magic_finalize(const unsigned long long *acc, const unsigned *syndrome, int nstripes,
+                                       uint64_t total_len, uint8_t *magic, const uint8_t *expect, uint8_t *bad,
+                                       unsigned *counts) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nstripes) return;
+  const uint32_t A = static_cast<uint32_t>((1 + acc[2 * s]) % kAdlerMod);
+  const uint32_t B = static_cast<uint32_t>((total_len % kAdlerMod + acc[2 * s + 1]) % kAdlerMod);
+  const uint32_t m = (B << 16) | A;
+  uint8_t *w = magic + 4ll * s;
+  w[0] = m & 255;
+  w[1] = (m >> 8) & 255;
+  w[2] = (m >> 16) & 255;
+  w[3] = m >> 24;
+  unsigned verdict = syndrome[s] != 0 ? kScrubBadParity : 0;
+  if (expect) {
+    const uint8_t *x = expect + 4ll * s;
+    const uint32_t want = x[0] | (x[1] << 8) | (x[2] << 16) | (static_cast<uint32_t>(x[3]) << 24);
+    if (want != m) verdict |= kScrubBadMagic;
+  }
+  if (bad) bad[s] = static_cast<uint8_t>(verdict);
+  if (counts) {
+    if (verdict & kScrubBadParity) atomicAdd(counts, 1u);
+    if (verdict & kScrubBadMagic) atomicAdd(counts + 1, 1u);
+  }
 }
 
 // one block per (stripe, 8 KiB column tile): OR of a^b over every pair, one flag store per
@@ -1202,6 +1276,17 @@ hipError_t launch_pattern_magic_finalize(const unsigned long long *acc, const ui
   if (!acc || !magic || total_len < 0 || reinterpret_cast<uintptr_t>(bad_count) % 4 != 0) return hipErrorInvalidValue;
   return launch_kernel(&k_pattern_magic_finalize, dim3((nstripes + 255) / 256), dim3(256), st, acc, stripe_pattern, npat,
                        nstripes, static_cast<uint64_t>(total_len), magic, expect, bad, bad_count);
+}
+
+hipError_t launch_check_magic_finalize(const unsigned long long *acc, const unsigned *syndrome, int nstripes,
+                                       int64_t total_len, uint8_t *magic, const uint8_t *expect, uint8_t *bad,
+                                       unsigned *counts, hipStream_t st) {
+  if (nstripes <= 0) return hipSuccess;
+  if (!acc || !syndrome || !magic || total_len < 0 || reinterpret_cast<uintptr_t>(syndrome) % 4 != 0 ||
+      reinterpret_cast<uintptr_t>(counts) % 4 != 0)
+    return hipErrorInvalidValue;
+  return launch_kernel(&k_check_magic_finalize, dim3((nstripes + 255) / 256), dim3(256), st, acc, syndrome, nstripes,
+                       static_cast<uint64_t>(total_len), magic, expect, bad, counts);
 }
 
 hipError_t launch_update_magic_finalize(const unsigned long long *acc, const unsigned long long *stripe_cols,

@@ -1438,9 +1438,14 @@ __device__ __forceinline__ uint32_t pat_logical(const PatternArgs &a, uint32_t p
 
 // bw_inputs for the MG tiles of a full tile: the same loads and arithmetic (`work`: the pattern has
 // rows to form, wave-uniform), and every input's units handed to seen(j, units) once they are loaded.
-template <int R, int KC, int IT, int VW, bool BF, typename Addr, typename Seen>
+// X0 and extra() as bw_inputs (the check's MG tiles: its stored parity loads, issued where bw_inputs
+// issues them).  EARLY (K fixed; the caller always has work): an input is handed to seen() right
+// ahead of its own arithmetic, not behind everybody's, so its registers die with its pair as in
+// bw_inputs.  The patterned MG tiles leave all three at their defaults.
+template <int R, int KC, int IT, int VW, bool BF, bool X0 = false, bool EARLY = false, typename Addr, typename Seen,
+          typename Extra = NoLoads>
 __device__ __forceinline__ void bw_inputs_seen(typename VecT<VW>::type (&acc)[IT][R], ConstCell *cells, int K, bool work,
-                                               Addr &&addr, Seen &&seen) {
+                                               Addr &&addr, Seen &&seen, Extra &&extra = Extra()) {
   typedef typename VecT<VW>::type V;
   constexpr int kStep = BwTile<IT, VW>::kStep;
   if constexpr (KC > 0) {
@@ -1451,19 +1456,42 @@ __device__ __forceinline__ void bw_inputs_seen(typename VecT<VW>::type (&acc)[IT
 #pragma unroll
       for (int it = 0; it < IT; ++it) v[j][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
     }
-    if (work) {
+    extra();
+    if constexpr (EARLY) {
       if constexpr (BF) {
 #pragma unroll
-        for (int j = 0; j + 1 < KC; j += 2) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[j], v[j + 1], cells, K, j);
-        if constexpr (KC % 2) bw_accumulate_bf<R, IT, VW, false, false>(acc, v[KC - 1], v[KC - 1], cells, K, KC - 1);
+        for (int j = 0; j + 1 < KC; j += 2) {
+          seen(j, v[j]);
+          seen(j + 1, v[j + 1]);
+          bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[j], v[j + 1], cells, K, j);
+        }
+        if constexpr (KC % 2) {
+          seen(KC - 1, v[KC - 1]);
+          bw_accumulate_bf<R, IT, VW, false, X0>(acc, v[KC - 1], v[KC - 1], cells, K, KC - 1);
+        }
       } else {
 #pragma unroll
-        for (int j = 0; j < KC; ++j) bw_accumulate<R, IT, VW>(acc, v[j], cells, K, j);
+        for (int j = 0; j < KC; ++j) {
+          seen(j, v[j]);
+          bw_accumulate<R, IT, VW>(acc, v[j], cells, K, j);
+        }
       }
-    }
+    } else {
+      if (work) {
+        if constexpr (BF) {
 #pragma unroll
-    for (int j = 0; j < KC; ++j) seen(j, v[j]);
+          for (int j = 0; j + 1 < KC; j += 2) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[j], v[j + 1], cells, K, j);
+          if constexpr (KC % 2) bw_accumulate_bf<R, IT, VW, false, X0>(acc, v[KC - 1], v[KC - 1], cells, K, KC - 1);
+        } else {
+#pragma unroll
+          for (int j = 0; j < KC; ++j) bw_accumulate<R, IT, VW>(acc, v[j], cells, K, j);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < KC; ++j) seen(j, v[j]);
+    }
   } else {
+    extra();
     for (int j0 = 0; j0 < K; j0 += 4) {
       V v[4][IT];
       const int nj = min(4, K - j0);
@@ -1477,9 +1505,9 @@ __device__ __forceinline__ void bw_inputs_seen(typename VecT<VW>::type (&acc)[IT
       }
       if (work) {
         if constexpr (BF) {
-          if (nj >= 2) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[0], v[1], cells, K, j0);
-          if (nj == 4) bw_accumulate_bf<R, IT, VW, true, false>(acc, v[2], v[3], cells, K, j0 + 2);
-          if (nj == 1 || nj == 3) bw_accumulate_bf<R, IT, VW, false, false>(acc, v[nj - 1], v[nj - 1], cells, K, j0 + nj - 1);
+          if (nj >= 2) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[0], v[1], cells, K, j0);
+          if (nj == 4) bw_accumulate_bf<R, IT, VW, true, X0>(acc, v[2], v[3], cells, K, j0 + 2);
+          if (nj == 1 || nj == 3) bw_accumulate_bf<R, IT, VW, false, X0>(acc, v[nj - 1], v[nj - 1], cells, K, j0 + nj - 1);
         } else {
 #pragma unroll
           for (int jj = 0; jj < 4; ++jj)
@@ -2038,8 +2066,17 @@ struct ChkShards {
 // encode: 24 at RS(6+3)); with K at run time the parity loads go out ahead of the first four inputs.
 // Args: CheckArgs, or LocateArgs for the locate kernels (the same tile body up to the last call);
 // their rotated forms differ in ChkShards alone.
-template <int R, int KC, int IT, bool BF, int VW, bool X0, typename Args>
-__device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
+//
+// MG (lsec_check_magic_dev / _rotated; Args: CheckMagicArgs, CheckMagicRotArgs): the tile also sums the
+// stripe's adler32 magic over the k + m chunks it holds anyway.  One MagicLane takes every data unit
+// as it is loaded and every stored parity unit pv[r], each at its LOGICAL chunk id (j, K + r: what
+// ChkShards un-rotates), and the tile commits once through block_sum into a.magic_acc[2s], [2s + 1].
+// block_sum has barriers: every lane of the workgroup reaches it, and there is no exit ahead of it
+// (chk_publish's early return is its own).  Units past the end of a ragged tile read as zero and add
+// nothing.  red: kBlock / 64 words of LDS.  Without MG red is not looked at and the code is the plain
+// check's.
+template <int R, int KC, int IT, bool BF, int VW, bool X0, bool MG = false, typename Args>
+__device__ __forceinline__ void chk_bytewise_tiles(const Args &a, uint32_t *red = nullptr) {
   typedef typename VecT<VW>::type V;
   constexpr int kStep = BwTile<IT, VW>::kStep;
   constexpr int kTile = BwTile<IT, VW>::kBytes;
@@ -2061,23 +2098,33 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
     for (int it = 0; it < IT; ++it)
 #pragma unroll
       for (int r = 0; r < R; ++r) acc[it][r] = 0u;
+    MagicLane ml;  // the stripe magic's partial sums (MG only)
 
     if (full) {
-      bw_inputs<R, KC, IT, VW, BF, X0>(
-          acc, cells, K,
-          [&](int j) LSEC_INLINE {
-            const ShardRef in = sh.in(j);
-            return in.base + s * in.stride + off0;
-          },
-          [&]() LSEC_INLINE {
+      const auto addr = [&](int j) LSEC_INLINE {
+        const ShardRef in = sh.in(j);
+        return in.base + s * in.stride + off0;
+      };
+      const auto stored = [&]() LSEC_INLINE {
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-              const ShardRef par = sh.par(r);
-              const uint64_t q = par.base + s * par.stride + off0;
+        for (int r = 0; r < R; ++r) {
+          const ShardRef par = sh.par(r);
+          const uint64_t q = par.base + s * par.stride + off0;
 #pragma unroll
-              for (int it = 0; it < IT; ++it) pv[r][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
-            }
-          });
+          for (int it = 0; it < IT; ++it) pv[r][it] = __builtin_nontemporal_load(gptr<V>(q + it * kStep));
+        }
+      };
+      if constexpr (MG) {
+        // by the registers of the fixed-K forms: summing an input ahead of its own pair
+        // frees it early, which the wide forms need (R = 5, K = 20: 256 VGPRs and copies in AGPRs -> 168)
+        // and the narrow two-step ones pay for (R = 3, K = 6: 123 -> 137, four waves per SIMD -> three)
+        constexpr bool kEarly = BF && (R >= 4 || IT == 1);
+        bw_inputs_seen<R, KC, IT, VW, BF, X0, kEarly>(
+            acc, cells, K, true, addr,
+            [&](int j, const V(&v)[IT]) LSEC_INLINE { ml_add<IT, VW>(ml, v, static_cast<uint32_t>(j)); }, stored);
+      } else {
+        bw_inputs<R, KC, IT, VW, BF, X0>(acc, cells, K, addr, stored);
+      }
     } else {
       // ragged last tile: zero-filled inputs give zero parity there, and the stored parity is
       // zero-filled the same way, so bytes past C never show as a difference
@@ -2087,6 +2134,7 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
         V v[IT];
 #pragma unroll
         for (int it = 0; it < IT; ++it) v[it] = load_ragged<VW>(p, off0 + it * kStep, C);
+        if constexpr (MG) ml_add<IT, VW>(ml, v, static_cast<uint32_t>(j));
         bw_acc1<R, IT, VW, BF, X0>(acc, v, cells, K, j);
       }
 #pragma unroll
@@ -2108,19 +2156,25 @@ __device__ __forceinline__ void chk_bytewise_tiles(const Args &a) {
     }
     if constexpr (kLocArgs<Args>) loc_bytewise_wave<R, IT, VW>(a, s, d, acc, pv);
     else chk_publish<R>(a, s, d);
+    if constexpr (MG) {
+      // the stored parity rows, as loaded (a ragged tile's units past C are zero)
+#pragma unroll
+      for (int r = 0; r < R; ++r) ml_add<IT, VW>(ml, pv[r], static_cast<uint32_t>(K + r));
+      ml_commit(ml, a.magic_acc, s, K + R, static_cast<uint64_t>(C), static_cast<uint64_t>(off0), kStep, red);
+    }
   }, a.tile_phase);
 }
 
 // the XOR-row flag picks one of two whole instantiations, by k_gf8_bytewise's rule
-template <int R, int KC, int IT, bool BF, int VW, typename Args>
-__device__ __forceinline__ void chk_bytewise_body(const Args &a) {
+template <int R, int KC, int IT, bool BF, int VW, bool MG = false, typename Args>
+__device__ __forceinline__ void chk_bytewise_body(const Args &a, uint32_t *red = nullptr) {
   if constexpr (BF && R >= 2 && (KC == 0 || KC * R >= 40)) {
     if (const_cells(a.cells)->pad & kCellXorRow) {
-      chk_bytewise_tiles<R, KC, IT, BF, VW, true>(a);
+      chk_bytewise_tiles<R, KC, IT, BF, VW, true, MG>(a, red);
       return;
     }
   }
-  chk_bytewise_tiles<R, KC, IT, BF, VW, false>(a);
+  chk_bytewise_tiles<R, KC, IT, BF, VW, false, MG>(a, red);
 }
 
 template <int R, int KC, int IT, bool BF, int VW>
@@ -2147,8 +2201,12 @@ __global__ __launch_bounds__(kBlock) void k_locrot_bytewise(LocateRotArgs a) {
 // inputs while they fit beside the accumulators (R * DW <= 8: 8 * R * DW VGPRs), else row by row
 // after them.  Lanes past the end of a ragged last tile leave the tile body (whole waves may).
 // Args: as chk_bytewise_tiles.
-template <int R, int DW, typename Args>
-__device__ __forceinline__ void chk_bitsliced_tiles(const Args &a) {
+// MG as in chk_bytewise_tiles: every e[x] of input j and every stored parity word go into the
+// MagicLane (a row that shares pv[0] is summed before the next one overwrites it).  The lanes past
+// the end of a ragged last tile then skip the loads and the vote under `valid`, but still join the
+// tile's reduction (as pat_bitsliced_tiles' do).
+template <int R, int DW, bool MG = false, typename Args>
+__device__ __forceinline__ void chk_bitsliced_tiles(const Args &a, uint32_t *red = nullptr) {
   typedef typename VecT<DW>::type V;
   constexpr bool kAhead = R * DW <= 8;
   constexpr bool kLocate = kLocArgs<Args>;
@@ -2164,70 +2222,77 @@ __device__ __forceinline__ void chk_bitsliced_tiles(const Args &a) {
     const uint32_t s = t / tiles_per_stripe;
     const ChkShards<Args> sh(a, s);
     const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * (4 * DW);
-    if (colb >= col_bytes) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
+    const bool valid = colb < col_bytes;
+    if (!MG && !valid) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
     const uint32_t sp = colb / P;
     const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+    MagicLane ml;  // the stripe magic's partial sums (MG only)
 
-    V acc[R][8], pv[kAhead ? R : 1][8];
+    if (!MG || valid) {
+      V acc[R][8], pv[kAhead ? R : 1][8];
 #pragma unroll
-    for (int r = 0; r < R; ++r)
+      for (int r = 0; r < R; ++r)
 #pragma unroll
-      for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
-    if constexpr (kAhead) {
+        for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
+      if constexpr (kAhead) {
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const ShardRef par = sh.par(r);
-        const uint64_t q = par.base + s * par.stride + off;
+        for (int r = 0; r < R; ++r) {
+          const ShardRef par = sh.par(r);
+          const uint64_t q = par.base + s * par.stride + off;
 #pragma unroll
-        for (int x = 0; x < 8; ++x) pv[r][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
-      }
-    }
-
-    for (int j = 0; j < K; ++j) {
-      const ShardRef in = sh.in(j);
-      const uint64_t p = in.base + s * in.stride + off;
-      V e[8];
-#pragma unroll
-      for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<V>(p + x * P));
-      uint32_t c[R];
-      uint32_t cm = 0;  // bits used by any output: no doublings past the highest one
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        c[r] = cells[r * K + j].coef;
-        cm |= c[r];
-      }
-      gf8_sliced_mul_acc<0>(acc, e, c, cm);
-    }
-    uint32_t d[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if constexpr (!kAhead) {
-        const ShardRef par = sh.par(r);
-        const uint64_t q = par.base + s * par.stride + off;
-#pragma unroll
-        for (int x = 0; x < 8; ++x) pv[0][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
-      }
-      d[r] = 0;
-      if constexpr (kLocate && !kAhead) {
-        // the stored row is gone after this: keep the syndrome in the accumulator (one XOR and one
-        // OR per word where the check has one v_bitop3)
-#pragma unroll
-        for (int x = 0; x < 8; ++x) {
-          acc[r][x] ^= pv[0][x];
-#pragma unroll
-          for (int w = 0; w < DW; ++w) d[r] |= reinterpret_cast<const uint32_t *>(&acc[r][x])[w];
+          for (int x = 0; x < 8; ++x) pv[r][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
         }
-      } else {
-#pragma unroll
-        for (int x = 0; x < 8; ++x)
-#pragma unroll
-          for (int w = 0; w < DW; ++w)
-            d[r] = or_diff(reinterpret_cast<const uint32_t *>(&acc[r][x])[w],
-                           reinterpret_cast<const uint32_t *>(&pv[kAhead ? r : 0][x])[w], d[r]);
       }
+
+      for (int j = 0; j < K; ++j) {
+        const ShardRef in = sh.in(j);
+        const uint64_t p = in.base + s * in.stride + off;
+        V e[8];
+#pragma unroll
+        for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<V>(p + x * P));
+        if constexpr (MG) ml_add<8, DW>(ml, e, static_cast<uint32_t>(j));
+        uint32_t c[R];
+        uint32_t cm = 0;  // bits used by any output: no doublings past the highest one
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          c[r] = cells[r * K + j].coef;
+          cm |= c[r];
+        }
+        gf8_sliced_mul_acc<0>(acc, e, c, cm);
+      }
+      uint32_t d[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if constexpr (!kAhead) {
+          const ShardRef par = sh.par(r);
+          const uint64_t q = par.base + s * par.stride + off;
+#pragma unroll
+          for (int x = 0; x < 8; ++x) pv[0][x] = __builtin_nontemporal_load(gptr<V>(q + x * P));
+        }
+        if constexpr (MG) ml_add<8, DW>(ml, pv[kAhead ? r : 0], static_cast<uint32_t>(K + r));  // (before pv[0] is loaded over)
+        d[r] = 0;
+        if constexpr (kLocate && !kAhead) {
+          // the stored row is gone after this: keep the syndrome in the accumulator (one XOR and one
+          // OR per word where the check has one v_bitop3)
+#pragma unroll
+          for (int x = 0; x < 8; ++x) {
+            acc[r][x] ^= pv[0][x];
+#pragma unroll
+            for (int w = 0; w < DW; ++w) d[r] |= reinterpret_cast<const uint32_t *>(&acc[r][x])[w];
+          }
+        } else {
+#pragma unroll
+          for (int x = 0; x < 8; ++x)
+#pragma unroll
+            for (int w = 0; w < DW; ++w)
+              d[r] = or_diff(reinterpret_cast<const uint32_t *>(&acc[r][x])[w],
+                             reinterpret_cast<const uint32_t *>(&pv[kAhead ? r : 0][x])[w], d[r]);
+        }
+      }
+      if constexpr (kLocate) loc_bitsliced_wave<R, DW, kAhead>(a, s, d, acc, pv);
+      else chk_publish<R>(a, s, d);
     }
-    if constexpr (kLocate) loc_bitsliced_wave<R, DW, kAhead>(a, s, d, acc, pv);
-    else chk_publish<R>(a, s, d);
+    if constexpr (MG) ml_commit(ml, a.magic_acc, s, K + R, static_cast<uint64_t>(a.size), static_cast<uint64_t>(off), P, red);
   }, a.tile_phase);
 }
 
@@ -2249,6 +2314,31 @@ __global__ __launch_bounds__(kBlock) void k_chkrot_bitsliced(CheckRotArgs a) {
 template <int R, int DW>
 __global__ __launch_bounds__(kBlock) void k_locrot_bitsliced(LocateRotArgs a) {
   chk_bitsliced_tiles<R, DW>(a);
+}
+
+// the MG kernels (lsec_check_magic_dev / _rotated): the same tile bodies, and the LDS of their reduction
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_chkmagic_bytewise(CheckMagicArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  chk_bytewise_body<R, KC, IT, BF, VW, true>(a, red);
+}
+
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_chkmagicrot_bytewise(CheckMagicRotArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  chk_bytewise_body<R, KC, IT, BF, VW, true>(a, red);
+}
+
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_chkmagic_bitsliced(CheckMagicArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  chk_bitsliced_tiles<R, DW, true>(a, red);
+}
+
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_chkmagicrot_bitsliced(CheckMagicRotArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  chk_bitsliced_tiles<R, DW, true>(a, red);
 }
 
 // The check's launch shape is the encode's automatic one for the same K x R (bw_auto, without
@@ -2289,6 +2379,8 @@ LSEC_SCRUB_KERNELS(CheckArgs, kFormChk, chk)
 LSEC_SCRUB_KERNELS(LocateArgs, kFormLoc, loc)
 LSEC_SCRUB_KERNELS(CheckRotArgs, kFormChkRot, chkrot)
 LSEC_SCRUB_KERNELS(LocateRotArgs, kFormLocRot, locrot)
+LSEC_SCRUB_KERNELS(CheckMagicArgs, kFormChkMagic, chkmagic)
+LSEC_SCRUB_KERNELS(CheckMagicRotArgs, kFormChkMagicRot, chkmagicrot)
 #undef LSEC_SCRUB_KERNELS
 
 // one kernel's launch, and its record (the template arguments are known here and nowhere later)
@@ -2354,6 +2446,59 @@ hipError_t dispatch_scrub_bitsliced(const Args &a, hipStream_t st, int grid, int
 #ifndef LSEC_INSTANTIATING_SCRUB
 LSEC_DECLARE_SCRUB_R(CheckArgs, 1) LSEC_DECLARE_SCRUB_R(CheckRotArgs, 1)
 LSEC_DECLARE_SCRUB(CheckArgs) LSEC_DECLARE_SCRUB(LocateArgs) LSEC_DECLARE_SCRUB(CheckRotArgs) LSEC_DECLARE_SCRUB(LocateRotArgs)
+#endif
+
+// The MG forms (lsec_check_magic_dev / _rotated; DESIGN.md 3.8 has their registers): the check's own,
+// through a constant of their own, so that one family can move without the other.
+constexpr BwForm chkmagic_bytewise_form(int K, int R) { return chk_bytewise_form(K, R); }
+
+// dispatch_scrub_bytewise over chkmagic_bytewise_form (Args: CheckMagicArgs or CheckMagicRotArgs)
+template <int R, typename Args>
+hipError_t dispatch_chkmagic_bytewise(const Args &a, hipStream_t st, int grid) {
+  const BwForm f = chkmagic_bytewise_form(a.K, R);
+  switch (f.kc) {
+#define LSEC_CHKMAGIC_K(KK)                                                                     \
+  case KK: {                                                                                    \
+    constexpr BwForm ff = chkmagic_bytewise_form(KK, R);                                        \
+    if constexpr (ff.kc == KK)                                                                  \
+      return scrub_bytewise_kernel<R, KK, ff.it, ff.bf, ff.vw>(a, st, grid);                   \
+    break;                                                                                      \
+  }
+    LSEC_FIXED_K(LSEC_CHKMAGIC_K)
+#undef LSEC_CHKMAGIC_K
+    default: break;
+  }
+  if constexpr (R == 1) {
+    return scrub_bytewise_kernel<1, 0, 1, false, 2>(a, st, grid);
+  } else {
+    if (f.it == 1) return scrub_bytewise_kernel<R, 0, 1, true, 4>(a, st, grid);
+    return scrub_bytewise_kernel<R, 0, 2, true, 4>(a, st, grid);
+  }
+}
+
+// Bit-sliced, dw dwords per lane.  More than one only up to kChkMagicWideRows rows: the encode's policy
+// asks for none wider (cauchy8_bitsliced_dw: R <= 4), and with the sums the 4-dword forms of 7 and 8 rows
+// would pass the register file (8 bytes of scratch at R = 8), so those forms do not exist.
+constexpr int kChkMagicWideRows = 6;
+template <int R, typename Args>
+hipError_t dispatch_chkmagic_bitsliced(const Args &a, hipStream_t st, int grid, int dw) {
+  if constexpr (R <= kChkMagicWideRows) {
+    if (dw == 4) return scrub_bitsliced_kernel<R, 4>(a, st, grid);
+    if (dw == 2) return scrub_bitsliced_kernel<R, 2>(a, st, grid);
+  }
+  return dw == 1 ? scrub_bitsliced_kernel<R, 1>(a, st, grid) : hipErrorInvalidValue;
+}
+
+// instantiated per argument struct and R in ec_scrub_magic_inst.hip
+#define LSEC_DECLARE_CHKMAGIC_R(ARGS, RR)                                                              \
+  extern template hipError_t dispatch_chkmagic_bytewise<RR, ARGS>(const ARGS &, hipStream_t, int);     \
+  extern template hipError_t dispatch_chkmagic_bitsliced<RR, ARGS>(const ARGS &, hipStream_t, int, int);
+#define LSEC_DECLARE_CHKMAGIC(ARGS)                                                                    \
+  LSEC_DECLARE_CHKMAGIC_R(ARGS, 1) LSEC_DECLARE_CHKMAGIC_R(ARGS, 2) LSEC_DECLARE_CHKMAGIC_R(ARGS, 3)   \
+  LSEC_DECLARE_CHKMAGIC_R(ARGS, 4) LSEC_DECLARE_CHKMAGIC_R(ARGS, 5) LSEC_DECLARE_CHKMAGIC_R(ARGS, 6)   \
+  LSEC_DECLARE_CHKMAGIC_R(ARGS, 7) LSEC_DECLARE_CHKMAGIC_R(ARGS, 8)
+#ifndef LSEC_INSTANTIATING_CHKMAGIC
+LSEC_DECLARE_CHKMAGIC(CheckMagicArgs) LSEC_DECLARE_CHKMAGIC(CheckMagicRotArgs)
 #endif
 
 // ------------------------------------------------------------------ parity update

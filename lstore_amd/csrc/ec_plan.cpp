@@ -598,7 +598,8 @@ int cauchy8_bitsliced_dw(int K, int R, long long size) {
 // Stripes per launch of chunks of C bytes: batches split so that the indices of their tiles (of
 // tile_bytes: 4096, or the stripe-magic calls' 8192) stay 32-bit.  With `split`,
 // lsec_test_set_pattern_split can lower it: the patterned calls, the repair behind a locate, every
-// launch of the rotated check and locate, the parity update and the rotated encode and update.
+// launch of the rotated check and locate, the parity update and the rotated encode and update, and the
+// check with the magics, rotated or not.
 std::atomic<int> g_pattern_split{0};  // stripes per launch, 0 = the 32-bit tile limit only
 
 long long launch_stripes(long long C, bool split, long long tile_bytes) {
@@ -1202,7 +1203,15 @@ int decode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes,
 // so the outputs are those of the logical view; the finalize launch also names the device behind
 // each located chunk.  Each later launch's rot0 advances by (s0 mod n) * rot_step.
 //
-// The four calls are one path (scrub_dev) that a ScrubCall steers.
+// lsec_check_magic_dev / lsec_check_magic_dev_rotated: the check's pass with the MG kernels
+// (ec_kernels.h, CheckMagicArgs), which also sum each stripe's adler32 magic from the chunks the check
+// holds in registers, over 16 bytes per stripe of accumulators from the stream-ordered allocator --
+// zeroed before the first launch, advancing by 2 * s0 words per launch, freed on the stream -- and one
+// finalize launch behind the tile launches that writes the magic words, compares them with expect,
+// writes bad and counts.  The tile launches get no bad_count.  Their rungs sit behind the check's, and
+// every message of theirs carries the call's name.
+//
+// The six calls are one path (scrub_dev) that a ScrubCall steers.
 
 // The host ratio image.  The hypothesis test divides by g[0][j] and tells "row r untouched" from
 // "row r touched" by g[r][j] != 0, so a zero coefficient anywhere is refused.
@@ -1244,8 +1253,8 @@ int ratio_cells_dev(PlanExt *e, const CoefCell **out) {
   return 0;
 }
 
-// What tells the four calls apart.  A check leaves the locate fields null, an unrotated call the
-// rotation at 0 and located_dev / dev_faults null.
+// What tells the six calls apart.  A check leaves the locate fields null, an unrotated call the
+// rotation at 0 and located_dev / dev_faults null, a call without the magics the magic fields null.
 struct ScrubCall {
   const char *name;  // for messages
   bool rotated;
@@ -1256,7 +1265,15 @@ struct ScrubCall {
   unsigned char *located, *located_dev;
   unsigned *counts, *dev_faults;
   int flags;
+  bool magics;            // lsec_check_magic_dev(_rotated): the MG kernels and their finalize launch
+  uint8_t *magic;         // 4 bytes per stripe
+  const uint8_t *expect;  // may be null
+  uint8_t *bad;           // may be null
+  unsigned *verdicts;     // may be null: [parity-bad, magic-bad]
 };
+
+template <typename Args>
+constexpr bool kMagicScrub = std::is_same<Args, lsec::CheckMagicArgs>::value || std::is_same<Args, lsec::CheckMagicRotArgs>::value;
 
 // the fields of an argument struct that change from launch to launch, for the one that starts at stripe s0
 template <typename Args>
@@ -1278,8 +1295,8 @@ void scrub_launch_fields(Args &a, const ScrubCall &c, const lsec_shard_t *sh, un
 // The accumulate launches: one per 32-bit range of tiles, in the encode's launch shape for K x R.
 template <typename Args>
 int enqueue_scrub(const ScrubCall &c, const lio_erasure_plan_t *p, const void *cells, const CoefCell *ratio, const lsec_shard_t *sh,
-                  int nstripes, long long C, unsigned *syndrome, unsigned *bad_count, uint32_t rot0, uint32_t rot_step,
-                  hipStream_t st) {
+                  int nstripes, long long C, unsigned *syndrome, unsigned *bad_count, unsigned long long *acc, uint32_t rot0,
+                  uint32_t rot_step, hipStream_t st) {
   Args a;
   std::memset(static_cast<void *>(&a), 0, sizeof(a));
   a.cells = static_cast<const CoefCell *>(cells);
@@ -1296,13 +1313,43 @@ int enqueue_scrub(const ScrubCall &c, const lio_erasure_plan_t *p, const void *c
   // the encode's dwords per lane for this shape (0: its packet network, which the check has no form of)
   const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
   const int dw = sliced ? cauchy8_bitsliced_dw(a.K, a.R, C) : 0;
-  return for_launches(nstripes, launch_stripes(C, c.rotated), [&](long long s0, int ns) {
+  return for_launches(nstripes, launch_stripes(C, c.rotated || c.magics), [&](long long s0, int ns) {
     scrub_launch_fields(a, c, sh, syndrome, s0, ns, rot0);
-    const hipError_t err = sliced ? lsec::launch_scrub_bitsliced(a, st, dw) : lsec::launch_scrub_bytewise(a, st);
-    if (err != hipSuccess)
-      return fail("%s%s kernel launch failed: %s", c.rotated ? "rotated " : "", c.locates ? "locate" : "check", hipGetErrorString(err));
+    hipError_t err;
+    if constexpr (kMagicScrub<Args>) {
+      a.magic_acc = acc + 2 * s0;
+      err = sliced ? lsec::launch_check_magic_bitsliced(a, st, dw) : lsec::launch_check_magic_bytewise(a, st);
+      if (err != hipSuccess) return fail("%s: kernel launch failed: %s", c.name, hipGetErrorString(err));
+    } else {
+      err = sliced ? lsec::launch_scrub_bitsliced(a, st, dw) : lsec::launch_scrub_bytewise(a, st);
+      if (err != hipSuccess)
+        return fail("%s%s kernel launch failed: %s", c.rotated ? "rotated " : "", c.locates ? "locate" : "check", hipGetErrorString(err));
+    }
     return 0;
   });
+}
+
+// The tile launches and the finalize launch of a call with the magics, between the allocation and the
+// release of its accumulators on the stream.
+int enqueue_scrub_magic(const ScrubCall &c, const lio_erasure_plan_t *p, const void *cells, const lsec_shard_t *sh, int nstripes,
+                        long long C, unsigned *syndrome, uint32_t rot0, uint32_t rot_step, hipStream_t st) {
+  const int n = p->data_strips + p->parity_strips;
+  unsigned long long *acc = nullptr;
+  hipError_t err = hipMallocAsync(reinterpret_cast<void **>(&acc), 16ull * nstripes, st);
+  if (err == hipSuccess && (err = hipMemsetAsync(acc, 0, 16ull * nstripes, st)) != hipSuccess) (void)hipFreeAsync(acc, st);
+  if (err != hipSuccess) return fail("%s: the magic accumulators (%llu bytes): %s", c.name, 16ull * nstripes, hipGetErrorString(err));
+  int rc = 0;
+  if (C > 0) {
+    const auto enqueue = c.rotated ? enqueue_scrub<lsec::CheckMagicRotArgs> : enqueue_scrub<lsec::CheckMagicArgs>;
+    rc = enqueue(c, p, cells, nullptr, sh, nstripes, C, syndrome, nullptr, acc, rot0, rot_step, st);
+  }
+  if (rc == 0) {
+    err = lsec::launch_check_magic_finalize(acc, syndrome, nstripes, static_cast<int64_t>(n) * C, c.magic, c.expect, c.bad, c.verdicts, st);
+    if (err != hipSuccess) rc = fail("%s: finalize launch failed: %s", c.name, hipGetErrorString(err));
+  }
+  err = hipFreeAsync(acc, st);
+  if (err != hipSuccess && rc == 0) rc = fail("%s: freeing the magic accumulators: %s", c.name, hipGetErrorString(err));
+  return rc;
 }
 
 // Every limit's message names the limit; nothing is enqueued when one is passed.
@@ -1322,18 +1369,25 @@ int scrub_dev(PlanExt *e, const ScrubCall &c, const lsec_shard_t *sh, int nstrip
   if (m < 1 || m > 8) return fail("%s: m=%d outside 1..8 (one launch's parity rows)", c.name, m);
   if (c.flags & ~LSEC_LOCATE_REPAIR) return fail("%s: flags %#x has bits other than LSEC_LOCATE_REPAIR", c.name, c.flags);
   const bool repair = (c.flags & LSEC_LOCATE_REPAIR) != 0;
-  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
-  if (c.n_shift < 0) return fail("n_shift %d is negative", c.n_shift);
-  if (c.first_stripe < 0) return fail("first_stripe %lld is negative", c.first_stripe);
-  if (check_geometry(p, C)) return -1;
-  if (nstripes > 0 && !syndrome) return fail("syndrome is NULL");
+  // (the calls with the magics name themselves in every message; the older calls' messages stay as they are)
+  const std::string pre_s = c.magics ? std::string(c.name) + ": " : std::string();
+  const char *pre = pre_s.c_str();
+  if (nstripes < 0) return fail("%snstripes %d is negative", pre, nstripes);
+  if (c.n_shift < 0) return fail("%sn_shift %d is negative", pre, c.n_shift);
+  if (c.first_stripe < 0) return fail("%sfirst_stripe %lld is negative", pre, c.first_stripe);
+  if (check_geometry(p, C)) return c.magics ? named(c.name, -1) : -1;
+  if (nstripes > 0 && !syndrome) return fail("%ssyndrome is NULL", pre);
   if (c.locates && nstripes > 0 && !c.hyp) return fail("hyp is NULL");
   if (c.locates && nstripes > 0 && !c.located) return fail("located is NULL");
-  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0) return fail("syndrome %p is not a multiple of 4 bytes", static_cast<void *>(syndrome));
+  if (reinterpret_cast<uintptr_t>(syndrome) % 4 != 0)
+    return fail("%ssyndrome %p is not a multiple of 4 bytes", pre, static_cast<void *>(syndrome));
   if (reinterpret_cast<uintptr_t>(bad_count) % 4 != 0) return fail("bad_count %p is not a multiple of 4 bytes", static_cast<void *>(bad_count));
   if (reinterpret_cast<uintptr_t>(c.hyp) % 8 != 0) return fail("hyp %p is not a multiple of 8 bytes", static_cast<void *>(c.hyp));
   if (reinterpret_cast<uintptr_t>(c.counts) % 4 != 0) return fail("counts %p is not a multiple of 4 bytes", static_cast<void *>(c.counts));
   if (reinterpret_cast<uintptr_t>(c.dev_faults) % 4 != 0) return fail("dev_faults %p is not a multiple of 4 bytes", static_cast<void *>(c.dev_faults));
+  if (c.magics && nstripes > 0 && !c.magic) return fail("%s: magic is NULL (4 bytes per stripe, required with nstripes > 0)", c.name);
+  if (reinterpret_cast<uintptr_t>(c.verdicts) % 4 != 0)
+    return fail("%s: counts %p is not a multiple of 4 bytes (two 32-bit words)", c.name, static_cast<void *>(c.verdicts));
   const PatternTable *tab = nullptr;
   PatternTable::Dev dv;
   if (c.locates) {
@@ -1372,12 +1426,14 @@ int scrub_dev(PlanExt *e, const ScrubCall &c, const lsec_shard_t *sh, int nstrip
   if (c.locates) HIP_OK(hipMemsetAsync(c.hyp, 0xFF, sizeof(unsigned long long) * static_cast<size_t>(nstripes), st));
   if (c.counts) HIP_OK(hipMemsetAsync(c.counts, 0, 2 * sizeof(unsigned), st));
   if (c.dev_faults) HIP_OK(hipMemsetAsync(c.dev_faults, 0, sizeof(unsigned) * static_cast<size_t>(n), st));
+  if (c.verdicts) HIP_OK(hipMemsetAsync(c.verdicts, 0, 2 * sizeof(unsigned), st));
   const uint32_t rot_step = c.rotated ? static_cast<uint32_t>(c.n_shift % n) : 0;
   const uint32_t rot0 = c.rotated ? pattern_rot0(n, c.n_shift, c.first_stripe) : 0;
+  if (c.magics) return enqueue_scrub_magic(c, p, cells, sh, nstripes, C, syndrome, rot0, rot_step, st);
   if (C > 0) {
     const auto enqueue = c.rotated ? (c.locates ? enqueue_scrub<lsec::LocateRotArgs> : enqueue_scrub<lsec::CheckRotArgs>)
                                    : (c.locates ? enqueue_scrub<lsec::LocateArgs> : enqueue_scrub<lsec::CheckArgs>);
-    if (enqueue(c, p, cells, ratio, sh, nstripes, C, syndrome, bad_count, rot0, rot_step, st)) return -1;
+    if (enqueue(c, p, cells, ratio, sh, nstripes, C, syndrome, bad_count, nullptr, rot0, rot_step, st)) return -1;
   }
   if (!c.locates) return 0;
   const hipError_t err = c.rotated ? lsec::launch_locate_finalize_rot(syndrome, c.hyp, c.located, c.located_dev, c.counts, c.dev_faults,
@@ -1400,6 +1456,30 @@ int check_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long l
                       unsigned *syndrome, unsigned *bad_count, hipStream_t st) {
   const ScrubCall c = {"lsec_check_dev_rotated", true, n_shift, first_stripe};
   return scrub_dev(e, c, devs, nstripes, C, syndrome, bad_count, st);
+}
+
+namespace {
+// a check's ScrubCall with the magic fields filled in (mc.bad_count: the two verdict words)
+ScrubCall with_magics(ScrubCall c, const MagicCheck &mc) {
+  c.magics = true;
+  c.magic = mc.magic;
+  c.expect = mc.expect;
+  c.bad = mc.bad;
+  c.verdicts = mc.bad_count;
+  return c;
+}
+}  // namespace
+
+int check_magic_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, const MagicCheck &mc,
+                    hipStream_t st) {
+  const ScrubCall c = with_magics({"lsec_check_magic_dev"}, mc);
+  return scrub_dev(e, c, sh, nstripes, C, syndrome, nullptr, st);
+}
+
+int check_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                            unsigned *syndrome, const MagicCheck &mc, hipStream_t st) {
+  const ScrubCall c = with_magics({"lsec_check_magic_dev_rotated", true, n_shift, first_stripe}, mc);
+  return scrub_dev(e, c, devs, nstripes, C, syndrome, nullptr, st);
 }
 
 int locate_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, unsigned long long *hyp,
@@ -2150,7 +2230,8 @@ int lsec_test_apply_path(void) { return tl_apply_path; }
 // Test hook, not in include/: the kernel forms (ec_kernels.h, LaunchForm) that the calling thread's last
 // lsec_check_dev, lsec_locate_dev, lsec_decode_dev_patterns, lsec_decode_dev_rotated,
 // lsec_check_dev_rotated, lsec_locate_dev_rotated, lsec_update_dev, lsec_encode_dev_rotated,
-// lsec_update_dev_rotated, lsec_update_dev_masked(_rotated) or lsec_decode_magic_dev_patterns / _rotated launched, in order: a locate with repair its
+// lsec_update_dev_rotated, lsec_update_dev_masked(_rotated), lsec_decode_magic_dev_patterns / _rotated or
+// lsec_check_magic_dev(_rotated) launched, in order: a locate with repair its
 // patterned decode too, a split call every launch; the finalize launch, which has one form, is not
 // among them.  forms: 8 ints each (family, bit-sliced, R, KC, IT, VW, BF, DW).  Returns the number
 // of launches; at most min(that, max_forms, 16) are written.
@@ -2230,6 +2311,22 @@ int lsec_test_predict_pattern_magic_form(int plan_kernel, int K, int R, int pack
   return 0;
 }
 
+// Test hook, not in include/ (no GPU): the form (family 13 of the launch record, 14 with `rotated`) lsec_check_magic_dev
+// and lsec_check_magic_dev_rotated launch for a plan of kernel 1 or 2 with K inputs and R rows at that packet and
+// chunk size, from the functions the dispatch calls (cauchy8_bitsliced_dw here, lsec::predict_check_magic_launch).
+int lsec_test_predict_check_magic_form(int rotated, int plan_kernel, int K, int R, int packet, long long block_size, int *form) {
+  if (!form) return fail("lsec_test_predict_check_magic_form: NULL output");
+  if (plan_kernel != KBYTEWISE && plan_kernel != KBITSLICED)
+    return fail("lsec_test_predict_check_magic_form: plan kernel %d", plan_kernel);
+  const bool sliced = plan_kernel == KBITSLICED;
+  lsec::LaunchForm f;
+  if (!lsec::predict_check_magic_launch(rotated != 0, sliced, K, R, packet, sliced ? cauchy8_bitsliced_dw(K, R, block_size) : 0, &f))
+    return fail("lsec_test_predict_check_magic_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
+  const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
+  std::memcpy(form, v, sizeof(v));
+  return 0;
+}
+
 // Test hook, not in include/ (no GPU): what the magic form adds to entry pattern_id of the table of
 // lsec_test_pattern_table (same arguments): *nout its erasure count (0: the checksum-only path; -1: a rotation that
 // cannot occur), in_sel[0..k) the shard indices it loads as inputs (for nout 0 too: the data chunks),
@@ -2267,8 +2364,8 @@ void lsec_test_set_cauchy8_policy(int mode) { g_c8_policy.store(mode == 1 ? 1 : 
 void lsec_test_set_tile_phase(int mode) { lsec::set_tile_phase(mode); }
 
 // Test hook, not in include/: a patterned call (and lsec_update_dev, lsec_encode_dev_rotated,
-// lsec_update_dev_rotated, lsec_update_dev_masked(_rotated) and lsec_decode_magic_dev_patterns / _rotated) launches at
-// most `stripes` stripes at a time (0, the default: only the 32-bit tile limit splits), so a small batch exercises
+// lsec_update_dev_rotated, lsec_update_dev_masked(_rotated), lsec_decode_magic_dev_patterns / _rotated and
+// lsec_check_magic_dev(_rotated)) launches at most `stripes` stripes at a time (0, the default: only the 32-bit tile limit splits), so a small batch exercises
 // the split.
 void lsec_test_set_pattern_split(int stripes) { g_pattern_split.store(std::max(0, stripes), std::memory_order_relaxed); }
 

@@ -678,6 +678,32 @@ int lsec_check_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, i
                            static_cast<hipStream_t>(stream));
 }
 
+// (lsec_check_dev's ladder, every message behind the call's name; then a NULL magic and a misaligned counts)
+int lsec_check_magic_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
+                         unsigned int *syndrome, void *magic, const void *expect, unsigned char *bad, unsigned int *counts,
+                         void *stream) {
+  static const char name[] = "lsec_check_magic_dev";
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!shards) return fail("%s: shards is NULL", name);
+  if (named(name, check_shards(plan, shards, nstripes))) return -1;
+  const MagicCheck mc = {static_cast<uint8_t *>(magic), static_cast<const uint8_t *>(expect), bad, counts};
+  return check_magic_dev(e, shards, nstripes, block_size, syndrome, mc, static_cast<hipStream_t>(stream));
+}
+
+int lsec_check_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                                 int n_shift, long long first_stripe, unsigned int *syndrome, void *magic, const void *expect,
+                                 unsigned char *bad, unsigned int *counts, void *stream) {
+  static const char name[] = "lsec_check_magic_dev_rotated";
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!devs) return fail("%s: devs is NULL", name);
+  if (named(name, check_shards(plan, devs, nstripes))) return -1;
+  const MagicCheck mc = {static_cast<uint8_t *>(magic), static_cast<const uint8_t *>(expect), bad, counts};
+  return check_magic_dev_rotated(e, devs, nstripes, block_size, n_shift, first_stripe, syndrome, mc,
+                                 static_cast<hipStream_t>(stream));
+}
+
 int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
                             int n_shift, long long first_stripe, unsigned int *syndrome, unsigned long long *hyp,
                             unsigned char *located, unsigned char *located_dev, unsigned int *counts,

@@ -86,12 +86,15 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_check_dev_rotated", "lsec_locate_dev_rotated", "lsec_update_dev",
            "lsec_encode_dev_rotated", "lsec_update_dev_rotated", "lsec_update_dev_masked",
            "lsec_update_dev_masked_rotated", "lsec_update_magic_dev_masked", "lsec_update_magic_dev_masked_rotated",
-           "lsec_decode_magic_dev_patterns", "lsec_decode_magic_dev_rotated")
+           "lsec_decode_magic_dev_patterns", "lsec_decode_magic_dev_rotated",
+           "lsec_check_magic_dev", "lsec_check_magic_dev_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
 # lsec_locate_dev: the two sentinels of located[] and the flag
 LOCATE_CLEAN, LOCATE_MANY, LOCATE_REPAIR = 0xFF, 0xFE, 1
+# lsec_check_magic_dev: the bits of bad[]
+SCRUB_BAD_PARITY, SCRUB_BAD_MAGIC = 1, 2
 # lsec_update_dev: the flag
 UPDATE_STORE = 1
 STRIPE_OK, STRIPE_EMPTY, STRIPE_BAD_MAGIC, STRIPE_REPAIRED, STRIPE_LOST_MAGIC, STRIPE_LOST_MISMATCH = range(6)
@@ -171,6 +174,12 @@ def lib():
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lsec_decode_magic_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
                                                 C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lsec_check_magic_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lsec_check_magic_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lsec_test_predict_check_magic_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                                     C.POINTER(C.c_int)]
     L.lsec_test_predict_pattern_magic_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.lsec_test_pattern_unused.argtypes = [P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -689,6 +698,56 @@ class Plan:
                                             n_shift, first_stripe, syndrome_ptr or None, bad_count_ptr or None, stream),
                "lsec_check_dev_rotated")
 
+    def check_magic_dev_refs(self, refs, nstripes: int, block_size: int, syndrome_ptr: int, magic_ptr: int,
+                             expect_ptr: int = 0, bad_ptr: int = 0, counts_ptr: int = 0, stream: int = 0) -> None:
+        """lsec_check_magic_dev: check_dev_refs, and in the same pass the 4 bytes at magic_ptr + 4*s (device memory,
+        no alignment; 0: NULL) set to the adler32 of stripe s's k+m chunks as stored.  expect_ptr (4 bytes per
+        stripe: the quorum magics), bad_ptr (1 byte per stripe: SCRUB_BAD_PARITY | SCRUB_BAD_MAGIC) and counts_ptr
+        (two aligned uint32: parity-bad, magic-bad) are each optional (0)."""
+        _check(lib().lsec_check_magic_dev(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                          syndrome_ptr or None, magic_ptr or None, expect_ptr or None, bad_ptr or None,
+                                          counts_ptr or None, stream), "lsec_check_magic_dev")
+
+    def check_magic_dev_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
+                                     syndrome_ptr: int, magic_ptr: int, expect_ptr: int = 0, bad_ptr: int = 0,
+                                     counts_ptr: int = 0, stream: int = 0) -> None:
+        """lsec_check_magic_dev_rotated: check_magic_dev_refs over the PHYSICAL devices of a rotated LUN (refs[i]:
+        device i).  Syndromes and magics are those of each stripe's LOGICAL view, whatever the rotation."""
+        _check(lib().lsec_check_magic_dev_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes,
+                                                  block_size, n_shift, first_stripe, syndrome_ptr or None,
+                                                  magic_ptr or None, expect_ptr or None, bad_ptr or None,
+                                                  counts_ptr or None, stream), "lsec_check_magic_dev_rotated")
+
+    @staticmethod
+    def _check_magic_tensors(n, syndrome, magic, expect, bad, counts):
+        for what, t, item, count in (("syndrome", syndrome, 4, n), ("magic", magic, 1, 4 * n), ("expect", expect, 1, 4 * n),
+                                     ("bad", bad, 1, n), ("counts", counts, 4, 2)):
+            if t is not None and (t.dtype.itemsize != item or not t.is_cuda or not t.is_contiguous() or t.numel() != count):
+                raise ValueError(f"{what} must be a contiguous device tensor of {count} elements of {item} bytes")
+
+    def check_magic_dev(self, data, parity, syndrome, magic, expect=None, bad=None, counts=None, stream=None) -> None:
+        """torch: check_dev, and magic (uint8 device tensor of 4 bytes per stripe, contiguous) set to the stripes'
+        adler32 words as stripe_magic_dev writes them; expect (as magic), bad (uint8 [N]) and counts (32-bit [2])
+        compare them with the quorum magics."""
+        refs, n, size = self.tensor_refs(data, parity)
+        self._check_magic_tensors(n, syndrome, magic, expect, bad, counts)
+        self.check_magic_dev_refs(refs, n, size, syndrome.data_ptr(), magic.data_ptr(),
+                                  0 if expect is None else expect.data_ptr(), 0 if bad is None else bad.data_ptr(),
+                                  0 if counts is None else counts.data_ptr(), _stream_handle(stream))
+
+    def check_magic_dev_rotated(self, devs, n_shift: int, first_stripe: int, syndrome, magic, expect=None, bad=None,
+                                counts=None, stream=None) -> None:
+        """torch: check_magic_dev over devs [k+m, N, C], the physical devices of a rotated LUN (devs[i, s]: the chunk
+        of stripe s on device i)."""
+        if devs.dim() != 3 or devs.dtype.itemsize != 1 or not devs.is_cuda or devs.stride(2) != 1:
+            raise ValueError("devs must be a uint8 device tensor [k+m, N, C] with contiguous chunks")
+        n, size = devs.shape[1], devs.shape[2]
+        refs = [(devs[i].data_ptr(), devs.stride(1)) for i in range(devs.shape[0])]
+        self._check_magic_tensors(n, syndrome, magic, expect, bad, counts)
+        self.check_magic_dev_rotated_refs(refs, n, size, n_shift, first_stripe, syndrome.data_ptr(), magic.data_ptr(),
+                                          0 if expect is None else expect.data_ptr(), 0 if bad is None else bad.data_ptr(),
+                                          0 if counts is None else counts.data_ptr(), _stream_handle(stream))
+
     def locate_dev_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
                                 syndrome_ptr: int, hyp_ptr: int, located_ptr: int, located_dev_ptr: int = 0,
                                 counts_ptr: int = 0, dev_faults_ptr: int = 0, repair: bool = False, stream: int = 0) -> None:
@@ -910,14 +969,19 @@ MAGIC_FAMILIES = ("updmaskmagic",)
 PATMAGIC_FAMILIES = ("patmagic",)
 
 
+# and behind those (PATMAGIC_FAMILIES stays as it is too): family numbers 13 and 14, the check that leaves the magics
+# and its rotated form
+CHKMAGIC_FAMILIES = ("chkmagic", "chkmagicrot")
+
+
 def _form(v) -> Form:
-    return Form((FORM_FAMILIES + MASKED_FAMILIES + MAGIC_FAMILIES + PATMAGIC_FAMILIES)[v[0] - 1], bool(v[1]),
-                *(int(x) for x in v[2:8]))
+    return Form((FORM_FAMILIES + MASKED_FAMILIES + MAGIC_FAMILIES + PATMAGIC_FAMILIES + CHKMAGIC_FAMILIES)[v[0] - 1],
+                bool(v[1]), *(int(x) for x in v[2:8]))
 
 
 def launch_record() -> list:
     """Test hook: the Forms this thread's last check_dev / locate_dev / decode_dev_patterns / decode_dev_rotated
-    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated / update_dev_masked(_rotated) / update_magic_dev_masked(_rotated) / decode_magic_dev_patterns / decode_magic_dev_rotated call launched, in order (a locate with repair: its patterned
+    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated / update_dev_masked(_rotated) / update_magic_dev_masked(_rotated) / decode_magic_dev_patterns / decode_magic_dev_rotated / check_magic_dev(_rotated) call launched, in order (a locate with repair: its patterned
     decode too; a split call: every launch)."""
     buf = (C.c_int * (8 * 16))()
     n = lib().lsec_test_launch_record(buf, 16)
@@ -962,6 +1026,16 @@ def predict_pattern_magic_form(plan_kernel: int, k: int, rows: int, packet: int 
     out = (C.c_int * 8)()
     _check(lib().lsec_test_predict_pattern_magic_form(plan_kernel, k, rows, packet, out),
            "lsec_test_predict_pattern_magic_form")
+    return _form(out)
+
+
+def predict_check_magic_form(rotated: bool, plan_kernel: int, k: int, rows: int, packet: int = 0, block_size: int = 0) -> Form:
+    """Test hook (no GPU): the Form ("chkmagic", or "chkmagicrot" with `rotated`) check_magic_dev_refs and
+    check_magic_dev_rotated_refs launch for a plan of kernel 1 or 2 with k inputs and `rows` rows, asked of the
+    functions the dispatch itself calls."""
+    out = (C.c_int * 8)()
+    _check(lib().lsec_test_predict_check_magic_form(1 if rotated else 0, plan_kernel, k, rows, packet, block_size, out),
+           "lsec_test_predict_check_magic_form")
     return _form(out)
 
 
