@@ -361,9 +361,10 @@ int lsec_locate_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
  * lost full-stripe write) has syndrome 0 and the wrong magic; with m = 2 two corrupt chunks can
  * imitate a third under the parity check -- and as lsec_check_dev followed by lsec_stripe_magic_dev
  * they cost 2(k+m) chunk reads per stripe.  Here the check's tiles, which hold every byte of the
- * stripe in registers, sum the magic too: k+m chunk reads.  The rotated call is also the one way to
- * get the magics of a rotated LUN on the device (what a caller of lsec_encode_dev_rotated must
- * store).  Purely additive too: the version stays 3, a caller detects the calls by their symbols.
+ * stripe in registers, sum the magic too: k+m chunk reads.  The rotated call also gives the magics
+ * of a rotated LUN on the device for stripes that are already stored (a full-stripe write gets them
+ * from lsec_encode_magic_dev_rotated, below, in the pass that forms the parity).  Purely additive
+ * too: the version stays 3, a caller detects the calls by their symbols.
  *
  * - shards, devs, n_shift and first_stripe mean exactly what they mean for lsec_check_dev /
  *   lsec_check_dev_rotated.  Every chunk is only read, exactly once; nothing proportional to the
@@ -495,6 +496,9 @@ int lsec_update_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int ns
  *   written.
  * - For Cauchy at w = 8 the bit-sliced table kernel runs even where lsec_encode_dev would run a
  *   compiled packet network, as for the check; the bytes are identical.
+ * - The stripes' magics are not computed here.  A writer that stores [4-byte magic | chunk] on every
+ *   device takes lsec_encode_magic_dev_rotated, below: the same bytes, and the magics from the same
+ *   pass.
  *
  * lsec_update_dev_rotated: lsec_update_dev with the old chunks and the parity on the devices.
  * - `cols` is a -1 terminated list of c distinct LOGICAL data chunk ids, 1 <= c <= k, each in
@@ -520,6 +524,47 @@ int lsec_encode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
 int lsec_update_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
                             long long block_size, int n_shift, long long first_stripe,
                             const int *cols, const lsec_shard_t *fresh, int flags, void *stream);
+
+/* lsec_encode_dev_rotated that also leaves each stripe's adler32 magic, one pass: the full-stripe
+ * write of a rotated LUN together with the word LStore stores in front of every chunk
+ * ([4-byte magic | chunk] on every device, segjerase_write_func).  As lsec_encode_dev_rotated followed
+ * by lsec_check_magic_dev_rotated the writer pays 2k+m chunk reads and m chunk writes per stripe and a
+ * parity re-computation whose answer is known; here the encode's tiles, which hold every byte of the
+ * stripe in registers -- the k inputs as loaded, the m rows as formed -- sum the magic too: k chunk
+ * reads and m chunk writes.  Purely additive too: the version stays 3, a caller detects the call by
+ * its symbol.
+ *
+ * - devs, n_shift and first_stripe mean exactly what they mean for lsec_encode_dev_rotated, and the
+ *   bytes left on the devices are exactly those it leaves for the same arguments: the data chunks
+ *   are only read, once each, and no byte outside the m parity chunks of each stripe is written.
+ * - `magic` is device memory, 4*nstripes bytes, no alignment requirement, pure output, required with
+ *   nstripes > 0.  Word s is the 4 little-endian bytes of zlib's adler32 over the k+m chunks of
+ *   stripe s in LOGICAL order -- data 0..k-1, then the parity rows just formed -- exactly what
+ *   lsec_check_magic_dev_rotated would write behind the encode, and what lsec_encode_magic_dev
+ *   writes for the logical view.  Rotation moves where chunks live, never their position in the sum.
+ * - magic must not overlap the devices.
+ * - n_shift == 0 behaves exactly as lsec_encode_magic_dev over devs, in bytes and in magics.
+ * - Scratch: the per-stripe accumulators, 16 bytes per stripe, come from the stream-ordered
+ *   allocator (hipMallocAsync on `stream`), are zeroed there and go back to it on the stream,
+ *   exactly as lsec_encode_magic_dev's and lsec_check_magic_dev's do; they are freed too when a
+ *   launch fails.  Nothing is uploaded: the kernels use the plan's cached encode image.
+ * - Plans and limits: lsec_plan_kernel 1 and 2, k <= 64, 1 <= m <= 8.  Layout, alignment and
+ *   block_size rules are those of lsec_encode_dev_rotated; all k+m entries of devs are validated.
+ *   For Cauchy at w = 8 the bit-sliced table kernel runs at every shape, as for
+ *   lsec_encode_dev_rotated.
+ * - nstripes == 0 validates everything, returns 0 and touches no GPU; magic and all bases may then
+ *   be NULL.  Where lsec_encode_dev_rotated accepts block_size == 0 with nstripes > 0, every magic
+ *   word comes out as 1 (adler32 of nothing) and no chunk is touched: the rule of
+ *   lsec_check_magic_dev.
+ * - Everything lsec_encode_dev_rotated refuses is refused, in its order; behind that a NULL magic
+ *   with nstripes > 0.  Each returns -1 with a message for lsec_last_error that names this call and
+ *   the limit, and nothing is enqueued: every argument check comes before the first HIP call.
+ *   There is no fallback to two passes.
+ * - No `expect`: a write has no quorum to compare with.
+ * Enqueued on `stream`; returns without synchronising.  0 / -1. */
+int lsec_encode_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                                  long long block_size, int n_shift, long long first_stripe,
+                                  void *magic, void *stream);
 
 /* The parity update with a changed set PER STRIPE, one pass: lsec_update_dev and
  * lsec_update_dev_rotated for a batch whose stripes do not change in the same chunks -- the first

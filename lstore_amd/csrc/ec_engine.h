@@ -235,6 +235,9 @@ int locate_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
 // the parity update with old_i taken from the device that holds chunk cols[i] (fresh stays logical); all devs are used
 int encode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
                        hipStream_t st);
+// the rotated encode, and magic[s] (4 bytes per stripe, device memory, pure output) = adler32 of stripe s's k+m logical chunks
+int encode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                             uint8_t *magic, hipStream_t st);
 int update_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
                        const int *cols, const lsec_shard_t *fresh, int flags, hipStream_t st);
 // the update with a changed set per stripe: stripe_cols[s] bit j = data chunk j of stripe s changes (device memory),

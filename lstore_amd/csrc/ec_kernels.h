@@ -318,10 +318,11 @@ hipError_t launch_check_magic_finalize(const unsigned long long *acc, const unsi
 template <typename Args>
 constexpr bool kLocArgs = std::is_same<Args, LocateArgs>::value || std::is_same<Args, LocateRotArgs>::value;
 struct EncodeRotArgs;
+struct EncodeMagicRotArgs;
 struct UpdateRotArgs;
 template <typename Args>
 constexpr bool kRotArgs = std::is_base_of<CheckRotArgs, Args>::value || std::is_same<Args, EncodeRotArgs>::value ||
-                          std::is_same<Args, UpdateRotArgs>::value;
+                          std::is_same<Args, EncodeMagicRotArgs>::value || std::is_same<Args, UpdateRotArgs>::value;
 
 // The accumulate launch of a check or locate, for each of CheckArgs, LocateArgs, CheckRotArgs and
 // LocateRotArgs.  R <= 8 (a locate: 2 <= R); the launch shape is the encode's for the same K x R
@@ -437,6 +438,26 @@ hipError_t launch_encode_rot_bitsliced(const EncodeRotArgs &a, hipStream_t strea
 hipError_t launch_update_rot_bytewise(const UpdateRotArgs &a, hipStream_t stream);
 hipError_t launch_update_rot_bitsliced(const UpdateRotArgs &a, hipStream_t stream, int dw_pref = 0);
 
+// The rotated encode that also leaves each stripe's adler32 magic (lsec_encode_magic_dev_rotated): the
+// full-stripe write of a rotated LUN and the word LStore stores in front of every chunk, from k chunk
+// reads and m chunk writes.  An encode tile holds every byte of its part of the stripe in registers --
+// the K data units as they are loaded and the R rows as they are formed -- so the MG kernels
+// (k_encmagicrot_*: the rotated encode's tile bodies under `if constexpr (MG)`) sum them into one
+// MagicLane at their LOGICAL chunk ids (j, K + r, whatever device ChkShards fetched or stores them at)
+// and commit once per tile into magic_acc[2s], [2s + 1] (zeroed before the first launch);
+// launch_magic_finalize folds the sums into the magic words.  The struct derives from EncodeRotArgs,
+// whose layout -- and with it every k_encrot_* kernel -- stays as it is.
+struct EncodeMagicRotArgs : EncodeRotArgs {
+  unsigned long long *magic_acc;  // 2 per stripe of this launch (8-byte aligned device memory)
+};
+static_assert(sizeof(EncodeMagicRotArgs) == sizeof(EncodeRotArgs) + 8, "EncodeMagicRotArgs layout");
+static_assert(sizeof(EncodeMagicRotArgs) < 4096, "EncodeMagicRotArgs: under the 4 KiB of kernel arguments");
+
+// As launch_encode_rot_*, and magic_acc != NULL.  The launch shapes are encmagicrot_bytewise_form and
+// encode_magic_rot_lane_dwords: the rotated encode's.
+hipError_t launch_encode_magic_rot_bytewise(const EncodeMagicRotArgs &a, hipStream_t stream);
+hipError_t launch_encode_magic_rot_bitsliced(const EncodeMagicRotArgs &a, hipStream_t stream, int dw_pref = 0);
+
 // The parity update with a changed set per stripe (lsec_update_dev_masked / _masked_rotated): bit j of
 // stripe_cols[s] says that data chunk j of stripe s changes.  One kernel family and one struct for
 // both calls: the refs are the K + R devices as in UpdateRotArgs, and the unrotated call passes its
@@ -505,7 +526,7 @@ hipError_t launch_update_magic_finalize(const unsigned long long *acc, const uns
 // functions record the form at the one place where the template arguments are known; the record
 // is the calling thread's, holds the launches since launch_record_reset() in order (the engine
 // resets it on entry to each of those calls) and costs a few host stores per launch.
-enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic, kFormPatMagic, kFormChkMagic, kFormChkMagicRot };
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic, kFormPatMagic, kFormChkMagic, kFormChkMagicRot, kFormEncMagicRot };
 struct LaunchForm {
   int family, sliced, R, KC, IT, VW, BF, DW;
 };
@@ -525,6 +546,8 @@ bool predict_masked_magic_launch(bool sliced, int K, int R, int packet, int dw_p
 bool predict_pattern_magic_launch(bool sliced, int K, int R, int packet, LaunchForm *out);
 // and for the check with the magic (kFormChkMagic, or kFormChkMagicRot with `rotated`)
 bool predict_check_magic_launch(bool rotated, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
+// and for the rotated encode with the magic (kFormEncMagicRot)
+bool predict_encode_magic_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // the K with fixed-K forms (LSEC_FIXED_K), ascending -> how many there are; out[0 .. min(that, max))
 int fixed_k_list(int *out, int max);
 

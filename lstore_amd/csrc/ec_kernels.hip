@@ -735,6 +735,33 @@ hipError_t launch_encode_rot_bitsliced(const EncodeRotArgs &a, hipStream_t st, i
   return by_r(a.R, [&](auto r) { return dispatch_encrot_bitsliced<decltype(r)::value>(a, st, grid, dw); });
 }
 
+// ------------------------------------------------------------------ the rotated encode that leaves the stripe magics
+namespace {
+// dwords per lane of a bit-sliced rotated encode with the magic (more than kEncMagicRotWideRows rows: one)
+int encode_magic_rot_lane_dwords(int R, int dw_pref, int packet) {
+  return lane_dwords(R <= kEncMagicRotWideRows ? dw_pref : 1, packet);
+}
+}  // namespace
+
+hipError_t launch_encode_magic_rot_bytewise(const EncodeMagicRotArgs &a, hipStream_t st) {
+  if (!encode_rot_args_ok(a) || !a.magic_acc) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const BwForm f = encmagicrot_bytewise_form(a.K, a.R);
+  const int grid = tile_grid(BwShape{f.it, f.vw, f.bf}.tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_encmagicrot_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_encode_magic_rot_bitsliced(const EncodeMagicRotArgs &a, hipStream_t st, int dw_pref) {
+  if (!encode_rot_args_ok(a) || !a.magic_acc || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int dw = encode_magic_rot_lane_dwords(a.R, dw_pref, a.packet);
+  const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(a.R, [&](auto r) { return dispatch_encmagicrot_bitsliced<decltype(r)::value>(a, st, grid, dw); });
+}
+
 // ------------------------------------------------------------------ which kernel ran (test hooks)
 namespace {
 thread_local LaunchForm tl_forms[kLaunchRecordMax];
@@ -820,6 +847,18 @@ bool predict_check_magic_launch(bool rotated, bool sliced, int K, int R, int pac
   }
   const BwForm f = chkmagic_bytewise_form(K, R);
   *out = LaunchForm{family, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
+  return true;
+}
+
+bool predict_encode_magic_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out) {
+  if (K < 1 || K > kMaxK || R < 1 || R > 8) return false;
+  if (sliced) {
+    if (packet <= 0 || packet % 4 != 0) return false;
+    *out = LaunchForm{kFormEncMagicRot, 1, R, 0, 0, 0, 0, encode_magic_rot_lane_dwords(R, dw_pref, packet)};
+    return true;
+  }
+  const BwForm f = encmagicrot_bytewise_form(K, R);
+  *out = LaunchForm{kFormEncMagicRot, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
   return true;
 }
 

@@ -3277,10 +3277,26 @@ LSEC_DECLARE_UPDMAGIC_R(5) LSEC_DECLARE_UPDMAGIC_R(6) LSEC_DECLARE_UPDMAGIC_R(7)
 // doubling loop -- with the accumulators stored to the devices that hold the stripe's parity rows
 // where the check loads the stored rows and compares.  No stored-parity registers (the check's pv),
 // no votes, no atomics.
+//
+// MG (lsec_encode_magic_dev_rotated; Args: EncodeMagicRotArgs): the tile also sums the stripe's adler32
+// magic over the k + m chunks it holds anyway.  One MagicLane takes every data unit as it is loaded and
+// every row acc[.][r] as it is stored, each at its LOGICAL chunk id (j, K + r: what ChkShards
+// un-rotates), and the tile commits once through block_sum into a.magic_acc[2s], [2s + 1].  block_sum
+// has barriers: every lane of the workgroup reaches it, and the MG forms have no exit ahead of it.
+// red: kBlock / 64 words of LDS.  Without MG red is not looked at and the code is the plain encode's.
 
-// BF, X0, KC as chk_bytewise_tiles.
-template <int R, int KC, int IT, bool BF, int VW, bool X0>
-__device__ __forceinline__ void encrot_bytewise_tiles(const EncodeRotArgs &a) {
+// Whether a fixed-K MG tile sums an input ahead of its own pair's arithmetic (bw_inputs_seen's EARLY) or
+// all of them behind everybody's: by the registers of the fixed-K forms.  With one step
+// per lane the early order frees each input with its pair and never costs a wave (R = 3, K = 16: 96
+// VGPRs against 121, five waves per SIMD against four); with two steps the late order is the smaller
+// one (R = 5, K = 6: 157 against 215, three waves against two) at every form but R = 4 and 5 at K = 4,
+// where it costs four VGPRs and no wave.  The encode has no stored rows beside its accumulators, so the
+// MG check's R >= 4 rule does not carry over.  No form of either order spills.
+constexpr bool encmagicrot_early(int IT, bool BF) { return BF && IT == 1; }
+
+// BF, X0, KC as chk_bytewise_tiles.  Args: EncodeRotArgs, or EncodeMagicRotArgs with MG.
+template <int R, int KC, int IT, bool BF, int VW, bool X0, bool MG = false, typename Args>
+__device__ __forceinline__ void encrot_bytewise_tiles(const Args &a, uint32_t *red = nullptr) {
   typedef typename VecT<VW>::type V;
   constexpr int kStep = BwTile<IT, VW>::kStep;
   constexpr int kTile = BwTile<IT, VW>::kBytes;
@@ -3293,7 +3309,7 @@ __device__ __forceinline__ void encrot_bytewise_tiles(const EncodeRotArgs &a) {
 
   for_tiles<(kTile >= 8192 ? 1 : 8192 / kTile)>(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
     const uint32_t s = t / tiles_per_stripe;
-    const ChkShards<EncodeRotArgs> sh(a, s);
+    const ChkShards<Args> sh(a, s);
     const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
     const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
 
@@ -3302,15 +3318,21 @@ __device__ __forceinline__ void encrot_bytewise_tiles(const EncodeRotArgs &a) {
     for (int it = 0; it < IT; ++it)
 #pragma unroll
       for (int r = 0; r < R; ++r) acc[it][r] = 0u;
+    MagicLane ml;  // the stripe magic's partial sums (MG only)
 
     if (full) {
-      bw_inputs<R, KC, IT, VW, BF, X0>(
-          acc, cells, K,
-          [&](int j) LSEC_INLINE {
-            const ShardRef in = sh.in(j);
-            return in.base + s * in.stride + off0;
-          },
-          NoLoads());
+      const auto addr = [&](int j) LSEC_INLINE {
+        const ShardRef in = sh.in(j);
+        return in.base + s * in.stride + off0;
+      };
+      if constexpr (MG) {
+        // early or late by the registers of the fixed-K forms, as the MG check picks
+        bw_inputs_seen<R, KC, IT, VW, BF, X0, encmagicrot_early(IT, BF)>(
+            acc, cells, K, true, addr,
+            [&](int j, const V(&v)[IT]) LSEC_INLINE { ml_add<IT, VW>(ml, v, static_cast<uint32_t>(j)); });
+      } else {
+        bw_inputs<R, KC, IT, VW, BF, X0>(acc, cells, K, addr, NoLoads());
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const ShardRef par = sh.par(r);
@@ -3326,6 +3348,7 @@ __device__ __forceinline__ void encrot_bytewise_tiles(const EncodeRotArgs &a) {
         V v[IT];
 #pragma unroll
         for (int it = 0; it < IT; ++it) v[it] = load_ragged<VW>(p, off0 + it * kStep, C);
+        if constexpr (MG) ml_add<IT, VW>(ml, v, static_cast<uint32_t>(j));
         bw_acc1<R, IT, VW, BF, X0>(acc, v, cells, K, j);
       }
 #pragma unroll
@@ -3336,24 +3359,39 @@ __device__ __forceinline__ void encrot_bytewise_tiles(const EncodeRotArgs &a) {
         for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
       }
     }
+    if constexpr (MG) {
+      // The rows as formed.  Of a ragged tile only the units inside C are stored, and only those add to
+      // the sums: a formed row is zero past C (and in the upper half of a half unit) because every input
+      // read as zero there and the code is linear.  Nothing here may make a row nonzero past C.
+      bw_magic_out<R, IT, VW>(ml, K, acc);
+      ml_commit(ml, a.magic_acc, s, K + R, static_cast<uint64_t>(C), static_cast<uint64_t>(off0), kStep, red);
+    }
   }, a.tile_phase);
 }
 
 // the XOR-row flag picks one of two whole instantiations, by k_gf8_bytewise's rule
-template <int R, int KC, int IT, bool BF, int VW>
-__global__ __launch_bounds__(kBlock) void k_encrot_bytewise(EncodeRotArgs a) {
+template <int R, int KC, int IT, bool BF, int VW, bool MG = false, typename Args>
+__device__ __forceinline__ void encrot_bytewise_body(const Args &a, uint32_t *red = nullptr) {
   if constexpr (BF && R >= 2 && (KC == 0 || KC * R >= 40)) {
     if (const_cells(a.cells)->pad & kCellXorRow) {
-      encrot_bytewise_tiles<R, KC, IT, BF, VW, true>(a);
+      encrot_bytewise_tiles<R, KC, IT, BF, VW, true, MG>(a, red);
       return;
     }
   }
-  encrot_bytewise_tiles<R, KC, IT, BF, VW, false>(a);
+  encrot_bytewise_tiles<R, KC, IT, BF, VW, false, MG>(a, red);
+}
+
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_encrot_bytewise(EncodeRotArgs a) {
+  encrot_bytewise_body<R, KC, IT, BF, VW>(a);
 }
 
 // k_gf8_bitsliced's lanes and doubling loop.  Lanes past the end of a ragged last tile leave the tile body.
-template <int R, int DW>
-__global__ __launch_bounds__(kBlock) void k_encrot_bitsliced(EncodeRotArgs a) {
+// MG as in encrot_bytewise_tiles: every e[x] of input j and every formed word acc[r][x] go into the
+// MagicLane.  The lanes past the end of a ragged last tile then skip the loads and the stores under
+// `valid`, but still join the tile's reduction with zero sums (as chk_bitsliced_tiles' do).
+template <int R, int DW, bool MG = false, typename Args>
+__device__ __forceinline__ void encrot_bitsliced_tiles(const Args &a, uint32_t *red = nullptr) {
   typedef typename VecT<DW>::type V;
   const int K = a.K;
   const uint32_t P = static_cast<uint32_t>(a.packet);
@@ -3365,41 +3403,66 @@ __global__ __launch_bounds__(kBlock) void k_encrot_bitsliced(EncodeRotArgs a) {
 
   for_tiles(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
     const uint32_t s = t / tiles_per_stripe;
-    const ChkShards<EncodeRotArgs> sh(a, s);
+    const ChkShards<Args> sh(a, s);
     const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * (4 * DW);
-    if (colb >= col_bytes) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
+    const bool valid = colb < col_bytes;
+    if (!MG && !valid) return;  // (P % (4 * DW) == 0 keeps a lane's DW dwords inside one packet)
     const uint32_t sp = colb / P;
     const int64_t off = static_cast<int64_t>(sp) * 8 * P + (colb - sp * P);
+    MagicLane ml;  // the stripe magic's partial sums (MG only)
 
-    V acc[R][8];
+    if (!MG || valid) {
+      V acc[R][8];
 #pragma unroll
-    for (int r = 0; r < R; ++r)
+      for (int r = 0; r < R; ++r)
 #pragma unroll
-      for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
+        for (int x = 0; x < 8; ++x) acc[r][x] = 0u;
 
-    for (int j = 0; j < K; ++j) {
-      const ShardRef in = sh.in(j);
-      const uint64_t p = in.base + s * in.stride + off;
-      V e[8];
+      for (int j = 0; j < K; ++j) {
+        const ShardRef in = sh.in(j);
+        const uint64_t p = in.base + s * in.stride + off;
+        V e[8];
 #pragma unroll
-      for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<V>(p + x * P));
-      uint32_t c[R];
-      uint32_t cm = 0;  // bits used by any output: no doublings past the highest one
+        for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<V>(p + x * P));
+        if constexpr (MG) ml_add<8, DW>(ml, e, static_cast<uint32_t>(j));
+        uint32_t c[R];
+        uint32_t cm = 0;  // bits used by any output: no doublings past the highest one
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          c[r] = cells[r * K + j].coef;
+          cm |= c[r];
+        }
+        gf8_sliced_mul_acc<0>(acc, e, c, cm);
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        c[r] = cells[r * K + j].coef;
-        cm |= c[r];
+        const ShardRef par = sh.par(r);
+        const uint64_t q = par.base + s * par.stride + off;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) put_nt<false, V>(q + x * P, acc[r][x]);
+        if constexpr (MG) ml_add<8, DW>(ml, acc[r], static_cast<uint32_t>(K + r));
       }
-      gf8_sliced_mul_acc<0>(acc, e, c, cm);
     }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const ShardRef par = sh.par(r);
-      const uint64_t q = par.base + s * par.stride + off;
-#pragma unroll
-      for (int x = 0; x < 8; ++x) put_nt<false, V>(q + x * P, acc[r][x]);
-    }
+    if constexpr (MG) ml_commit(ml, a.magic_acc, s, K + R, static_cast<uint64_t>(a.size), static_cast<uint64_t>(off), P, red);
   }, a.tile_phase);
+}
+
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_encrot_bitsliced(EncodeRotArgs a) {
+  encrot_bitsliced_tiles<R, DW>(a);
+}
+
+// the MG kernels (lsec_encode_magic_dev_rotated): the same tile bodies, and the LDS of their reduction
+template <int R, int KC, int IT, bool BF, int VW>
+__global__ __launch_bounds__(kBlock) void k_encmagicrot_bytewise(EncodeMagicRotArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  encrot_bytewise_body<R, KC, IT, BF, VW, true>(a, red);
+}
+
+template <int R, int DW>
+__global__ __launch_bounds__(kBlock) void k_encmagicrot_bitsliced(EncodeMagicRotArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  encrot_bitsliced_tiles<R, DW, true>(a, red);
 }
 
 template <int R, int KC, int IT, bool BF, int VW>
@@ -3412,6 +3475,18 @@ template <int R, int DW>
 hipError_t encrot_bitsliced_kernel(const EncodeRotArgs &a, hipStream_t st, int grid) {
   record_launch({kFormEncRot, 1, R, 0, 0, 0, 0, DW});
   return launch_tiled(&k_encrot_bitsliced<R, DW>, grid, st, a);
+}
+
+template <int R, int KC, int IT, bool BF, int VW>
+hipError_t encmagicrot_bytewise_kernel(const EncodeMagicRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormEncMagicRot, 0, R, KC, IT, VW, BF ? 1 : 0, 0});
+  return launch_tiled(&k_encmagicrot_bytewise<R, KC, IT, BF, VW>, grid, st, a);
+}
+
+template <int R, int DW>
+hipError_t encmagicrot_bitsliced_kernel(const EncodeMagicRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormEncMagicRot, 1, R, 0, 0, 0, 0, DW});
+  return launch_tiled(&k_encmagicrot_bitsliced<R, DW>, grid, st, a);
 }
 
 // the form is the rotated check's for the same K x R (chk_bytewise_form), switched on as dispatch_scrub_bytewise does
@@ -3458,6 +3533,54 @@ hipError_t dispatch_encrot_bitsliced(const EncodeRotArgs &a, hipStream_t st, int
 #ifndef LSEC_INSTANTIATING_ENCROT
 LSEC_DECLARE_ENCROT_R(1) LSEC_DECLARE_ENCROT_R(2) LSEC_DECLARE_ENCROT_R(3) LSEC_DECLARE_ENCROT_R(4)
 LSEC_DECLARE_ENCROT_R(5) LSEC_DECLARE_ENCROT_R(6) LSEC_DECLARE_ENCROT_R(7) LSEC_DECLARE_ENCROT_R(8)
+#endif
+
+// The MG forms (lsec_encode_magic_dev_rotated; DESIGN.md 3.9 has their registers): the rotated encode's
+// own, through constants of their own, so that one family can move without the other.
+constexpr BwForm encmagicrot_bytewise_form(int K, int R) { return chk_bytewise_form(K, R); }
+
+// dispatch_encrot_bytewise over encmagicrot_bytewise_form
+template <int R>
+hipError_t dispatch_encmagicrot_bytewise(const EncodeMagicRotArgs &a, hipStream_t st, int grid) {
+  const BwForm f = encmagicrot_bytewise_form(a.K, R);
+  switch (f.kc) {
+#define LSEC_ENCMAGICROT_K(KK)                                                        \
+  case KK: {                                                                          \
+    constexpr BwForm ff = encmagicrot_bytewise_form(KK, R);                           \
+    if constexpr (ff.kc == KK)                                                        \
+      return encmagicrot_bytewise_kernel<R, KK, ff.it, ff.bf, ff.vw>(a, st, grid);    \
+    break;                                                                            \
+  }
+    LSEC_FIXED_K(LSEC_ENCMAGICROT_K)
+#undef LSEC_ENCMAGICROT_K
+    default: break;
+  }
+  if constexpr (R == 1) {
+    return encmagicrot_bytewise_kernel<1, 0, 1, false, 2>(a, st, grid);
+  } else {
+    if (f.it == 1) return encmagicrot_bytewise_kernel<R, 0, 1, true, 4>(a, st, grid);
+    return encmagicrot_bytewise_kernel<R, 0, 2, true, 4>(a, st, grid);
+  }
+}
+
+// dw dwords per lane: the rotated encode's, more than one up to kEncMagicRotWideRows rows
+constexpr int kEncMagicRotWideRows = kEncRotWideRows;
+template <int R>
+hipError_t dispatch_encmagicrot_bitsliced(const EncodeMagicRotArgs &a, hipStream_t st, int grid, int dw) {
+  if constexpr (R <= kEncMagicRotWideRows) {
+    if (dw == 4) return encmagicrot_bitsliced_kernel<R, 4>(a, st, grid);
+    if (dw == 2) return encmagicrot_bitsliced_kernel<R, 2>(a, st, grid);
+  }
+  return dw == 1 ? encmagicrot_bitsliced_kernel<R, 1>(a, st, grid) : hipErrorInvalidValue;
+}
+
+// instantiated per R in ec_encode_magic_rot_inst.hip
+#define LSEC_DECLARE_ENCMAGICROT_R(RR)                                                                        \
+  extern template hipError_t dispatch_encmagicrot_bytewise<RR>(const EncodeMagicRotArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_encmagicrot_bitsliced<RR>(const EncodeMagicRotArgs &, hipStream_t, int, int);
+#ifndef LSEC_INSTANTIATING_ENCMAGICROT
+LSEC_DECLARE_ENCMAGICROT_R(1) LSEC_DECLARE_ENCMAGICROT_R(2) LSEC_DECLARE_ENCMAGICROT_R(3) LSEC_DECLARE_ENCMAGICROT_R(4)
+LSEC_DECLARE_ENCMAGICROT_R(5) LSEC_DECLARE_ENCMAGICROT_R(6) LSEC_DECLARE_ENCMAGICROT_R(7) LSEC_DECLARE_ENCMAGICROT_R(8)
 #endif
 
 #define LSEC_DECLARE_R(RR)                                                                         \

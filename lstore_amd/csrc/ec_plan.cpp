@@ -1796,29 +1796,30 @@ int update_magic_dev_masked_rotated(PlanExt *e, const lsec_shard_t *devs, int ns
 // of tiles, rot0 advancing from launch to launch), over the cached encode image.  A Cauchy plan
 // takes the bit-sliced table kernel at every shape, as the check does: the compiled packet
 // networks have no rotated form, and the bytes are the same.
-int encode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
-                       hipStream_t st) {
-  static const char *const name = "lsec_encode_dev_rotated";
-  lsec::launch_record_reset();  // (lsec_test_launch_record)
-  lio_erasure_plan_t *p = &e->pub;
-  const int kind = kernel_kind(p->method, p->w);
-  if (kind != KBYTEWISE && kind != KBITSLICED)
-    return fail("%s needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d", name,
-                JE_method[p->method], p->w, kind);
+//
+// lsec_encode_magic_dev_rotated: the same pass with the MG kernels (ec_kernels.h, EncodeMagicRotArgs),
+// which also sum each stripe's adler32 magic from the chunks the encode holds in registers, over 16
+// bytes per stripe of accumulators from the stream-ordered allocator -- zeroed before the first launch,
+// advancing by 2 * s0 words per launch, freed on the stream -- and launch_magic_finalize behind the tile
+// launches.  Its one rung of its own, a NULL magic, sits behind the plain call's, and every message of
+// its carries the call's name.
+//
+// The two calls are one path (encode_rot_path) that an EncodeRotCall steers.
+namespace {
+
+struct EncodeRotCall {
+  const char *name;  // for messages
+  bool magics;       // lsec_encode_magic_dev_rotated: the MG kernels and the finalize launch
+  uint8_t *magic;    // 4 bytes per stripe
+};
+
+// The tile launches: one per 32-bit range of tiles, in the rotated check's launch shape for K x R.
+// acc: the magic accumulators of the whole call (Args = EncodeMagicRotArgs), else unused.
+template <typename Args>
+int enqueue_encode_rot(const EncodeRotCall &c, const lio_erasure_plan_t *p, const void *cells, const lsec_shard_t *devs, int nstripes,
+                       long long C, int n_shift, long long first_stripe, unsigned long long *acc, hipStream_t st) {
   const int k = p->data_strips, m = p->parity_strips, n = k + m;
-  if (k < 1 || k > lsec::kMaxK) return fail("%s: k=%d outside 1..%d (one launch's inputs)", name, k, lsec::kMaxK);
-  if (m < 1 || m > 8) return fail("%s: m=%d outside 1..8 (one launch's parity rows)", name, m);
-  if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
-  if (n_shift < 0) return fail("n_shift %d is negative", n_shift);
-  if (first_stripe < 0) return fail("first_stripe %lld is negative", first_stripe);
-  if (check_geometry(p, C)) return -1;
-  if (nstripes == 0) return 0;
-  const void *cells = nullptr;
-  if (encode_image(e, &cells)) return -1;
-  const int R = encode_rows(e);
-  if (R != m) return fail("%s: the plan encodes %d parity rows, m=%d", name, R, m);
-  if (C == 0) return 0;
-  lsec::EncodeRotArgs a;
+  Args a;
   std::memset(static_cast<void *>(&a), 0, sizeof(a));
   a.cells = static_cast<const CoefCell *>(cells);
   a.K = k;
@@ -1829,16 +1830,78 @@ int encode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
   a.rot_n = static_cast<uint32_t>(n);
   const uint32_t rot0 = pattern_rot0(n, n_shift, first_stripe);
   // the encode's dwords per lane for this shape (0: its packet network, which the rotated encode has no form of)
-  const bool sliced = kind == KBITSLICED;
+  const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
   const int dw = sliced ? cauchy8_bitsliced_dw(k, m, C) : 0;
   return for_launches(nstripes, launch_stripes(C, true), [&](long long s0, int ns) {
     a.nstripes = ns;
     a.rot0 = rot0_from(rot0, a.rot_step, n, s0);
     for (int i = 0; i < n; ++i) a.sh[i] = shard_from(devs[i], s0);
-    const hipError_t err = sliced ? lsec::launch_encode_rot_bitsliced(a, st, dw) : lsec::launch_encode_rot_bytewise(a, st);
-    if (err != hipSuccess) return fail("rotated encode kernel launch failed: %s", hipGetErrorString(err));
+    if constexpr (std::is_same<Args, lsec::EncodeMagicRotArgs>::value) {
+      a.magic_acc = acc + 2 * s0;
+      const hipError_t err = sliced ? lsec::launch_encode_magic_rot_bitsliced(a, st, dw) : lsec::launch_encode_magic_rot_bytewise(a, st);
+      if (err != hipSuccess) return fail("%s: kernel launch failed: %s", c.name, hipGetErrorString(err));
+    } else {
+      const hipError_t err = sliced ? lsec::launch_encode_rot_bitsliced(a, st, dw) : lsec::launch_encode_rot_bytewise(a, st);
+      if (err != hipSuccess) return fail("rotated encode kernel launch failed: %s", hipGetErrorString(err));
+    }
     return 0;
   });
+}
+
+// Every limit's message names the limit; nothing is enqueued when one is passed.
+int encode_rot_path(PlanExt *e, const EncodeRotCall &c, const lsec_shard_t *devs, int nstripes, long long C, int n_shift,
+                    long long first_stripe, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("%s needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d", c.name,
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  if (k < 1 || k > lsec::kMaxK) return fail("%s: k=%d outside 1..%d (one launch's inputs)", c.name, k, lsec::kMaxK);
+  if (m < 1 || m > 8) return fail("%s: m=%d outside 1..8 (one launch's parity rows)", c.name, m);
+  // (the call with the magics names itself in every message; the plain call's messages stay as they are)
+  const std::string pre_s = c.magics ? std::string(c.name) + ": " : std::string();
+  const char *pre = pre_s.c_str();
+  if (nstripes < 0) return fail("%snstripes %d is negative", pre, nstripes);
+  if (n_shift < 0) return fail("%sn_shift %d is negative", pre, n_shift);
+  if (first_stripe < 0) return fail("%sfirst_stripe %lld is negative", pre, first_stripe);
+  if (check_geometry(p, C)) return c.magics ? named(c.name, -1) : -1;
+  if (c.magics && nstripes > 0 && !c.magic) return fail("%s: magic is NULL (4 bytes per stripe, required with nstripes > 0)", c.name);
+  if (nstripes == 0) return 0;
+  const void *cells = nullptr;
+  if (encode_image(e, &cells)) return -1;
+  const int R = encode_rows(e);
+  if (R != m) return fail("%s: the plan encodes %d parity rows, m=%d", c.name, R, m);
+  if (!c.magics) return C == 0 ? 0 : enqueue_encode_rot<lsec::EncodeRotArgs>(c, p, cells, devs, nstripes, C, n_shift, first_stripe, nullptr, st);
+  // the tile launches and the finalize launch, between the allocation and the release of the accumulators on the
+  // stream; an empty chunk launches the finalize alone, over zero sums: every word 1, adler32 of nothing
+  unsigned long long *acc = nullptr;
+  hipError_t err = hipMallocAsync(reinterpret_cast<void **>(&acc), 16ull * nstripes, st);
+  if (err == hipSuccess && (err = hipMemsetAsync(acc, 0, 16ull * nstripes, st)) != hipSuccess) (void)hipFreeAsync(acc, st);
+  if (err != hipSuccess) return fail("%s: the magic accumulators (%llu bytes): %s", c.name, 16ull * nstripes, hipGetErrorString(err));
+  int rc = C > 0 ? enqueue_encode_rot<lsec::EncodeMagicRotArgs>(c, p, cells, devs, nstripes, C, n_shift, first_stripe, acc, st) : 0;
+  if (rc == 0) {
+    err = lsec::launch_magic_finalize(acc, nstripes, static_cast<int64_t>(n) * C, c.magic, st);
+    if (err != hipSuccess) rc = fail("%s: finalize launch failed: %s", c.name, hipGetErrorString(err));
+  }
+  err = hipFreeAsync(acc, st);
+  if (err != hipSuccess && rc == 0) rc = fail("%s: freeing the magic accumulators: %s", c.name, hipGetErrorString(err));
+  return rc;
+}
+
+}  // namespace
+
+int encode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                       hipStream_t st) {
+  const EncodeRotCall c = {"lsec_encode_dev_rotated", false, nullptr};
+  return encode_rot_path(e, c, devs, nstripes, C, n_shift, first_stripe, st);
+}
+
+int encode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                             uint8_t *magic, hipStream_t st) {
+  const EncodeRotCall c = {"lsec_encode_magic_dev_rotated", true, magic};
+  return encode_rot_path(e, c, devs, nstripes, C, n_shift, first_stripe, st);
 }
 
 }  // namespace eng
@@ -2230,8 +2293,8 @@ int lsec_test_apply_path(void) { return tl_apply_path; }
 // Test hook, not in include/: the kernel forms (ec_kernels.h, LaunchForm) that the calling thread's last
 // lsec_check_dev, lsec_locate_dev, lsec_decode_dev_patterns, lsec_decode_dev_rotated,
 // lsec_check_dev_rotated, lsec_locate_dev_rotated, lsec_update_dev, lsec_encode_dev_rotated,
-// lsec_update_dev_rotated, lsec_update_dev_masked(_rotated), lsec_decode_magic_dev_patterns / _rotated or
-// lsec_check_magic_dev(_rotated) launched, in order: a locate with repair its
+// lsec_update_dev_rotated, lsec_update_dev_masked(_rotated), lsec_decode_magic_dev_patterns / _rotated,
+// lsec_check_magic_dev(_rotated) or lsec_encode_magic_dev_rotated launched, in order: a locate with repair its
 // patterned decode too, a split call every launch; the finalize launch, which has one form, is not
 // among them.  forms: 8 ints each (family, bit-sliced, R, KC, IT, VW, BF, DW).  Returns the number
 // of launches; at most min(that, max_forms, 16) are written.
@@ -2322,6 +2385,22 @@ int lsec_test_predict_check_magic_form(int rotated, int plan_kernel, int K, int 
   lsec::LaunchForm f;
   if (!lsec::predict_check_magic_launch(rotated != 0, sliced, K, R, packet, sliced ? cauchy8_bitsliced_dw(K, R, block_size) : 0, &f))
     return fail("lsec_test_predict_check_magic_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
+  const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
+  std::memcpy(form, v, sizeof(v));
+  return 0;
+}
+
+// Test hook, not in include/ (no GPU): the form (family 15 of the launch record) lsec_encode_magic_dev_rotated launches
+// for a plan of kernel 1 or 2 with K inputs and R rows at that packet and chunk size, from the functions the dispatch
+// calls (cauchy8_bitsliced_dw here, lsec::predict_encode_magic_launch).
+int lsec_test_predict_encode_magic_form(int plan_kernel, int K, int R, int packet, long long block_size, int *form) {
+  if (!form) return fail("lsec_test_predict_encode_magic_form: NULL output");
+  if (plan_kernel != KBYTEWISE && plan_kernel != KBITSLICED)
+    return fail("lsec_test_predict_encode_magic_form: plan kernel %d", plan_kernel);
+  const bool sliced = plan_kernel == KBITSLICED;
+  lsec::LaunchForm f;
+  if (!lsec::predict_encode_magic_launch(sliced, K, R, packet, sliced ? cauchy8_bitsliced_dw(K, R, block_size) : 0, &f))
+    return fail("lsec_test_predict_encode_magic_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
   const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
   std::memcpy(form, v, sizeof(v));
   return 0;

@@ -725,6 +725,18 @@ int lsec_encode_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, 
   return encode_dev_rotated(e, devs, nstripes, block_size, n_shift, first_stripe, static_cast<hipStream_t>(stream));
 }
 
+// (lsec_encode_dev_rotated's ladder, every message behind the call's name; then a NULL magic)
+int lsec_encode_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                                  int n_shift, long long first_stripe, void *magic, void *stream) {
+  static const char name[] = "lsec_encode_magic_dev_rotated";
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!devs) return fail("%s: devs is NULL", name);
+  if (named(name, check_shards(plan, devs, nstripes))) return -1;
+  return encode_magic_dev_rotated(e, devs, nstripes, block_size, n_shift, first_stripe, static_cast<uint8_t *>(magic),
+                                  static_cast<hipStream_t>(stream));
+}
+
 // (no check_shards: update_path's ladder validates all k+m devices where lsec_update_dev's validates its shards)
 int lsec_update_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
                             int n_shift, long long first_stripe, const int *cols, const lsec_shard_t *fresh, int flags,

@@ -87,7 +87,7 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_encode_dev_rotated", "lsec_update_dev_rotated", "lsec_update_dev_masked",
            "lsec_update_dev_masked_rotated", "lsec_update_magic_dev_masked", "lsec_update_magic_dev_masked_rotated",
            "lsec_decode_magic_dev_patterns", "lsec_decode_magic_dev_rotated",
-           "lsec_check_magic_dev", "lsec_check_magic_dev_rotated")
+           "lsec_check_magic_dev", "lsec_check_magic_dev_rotated", "lsec_encode_magic_dev_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -180,6 +180,9 @@ def lib():
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lsec_test_predict_check_magic_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
                                                      C.POINTER(C.c_int)]
+    L.lsec_encode_magic_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
+                                                C.c_void_p, C.c_void_p]
+    L.lsec_test_predict_encode_magic_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
     L.lsec_test_predict_pattern_magic_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.lsec_test_pattern_unused.argtypes = [P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -792,6 +795,27 @@ class Plan:
         _check(lib().lsec_encode_dev_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
                                              n_shift, first_stripe, stream), "lsec_encode_dev_rotated")
 
+    def encode_magic_dev_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
+                                      magic_ptr: int, stream: int = 0) -> None:
+        """lsec_encode_magic_dev_rotated: encode_dev_rotated_refs, and in the same pass the 4 bytes at magic_ptr + 4*s
+        (device memory, no alignment, pure output; 0: NULL) set to the adler32 of stripe s's k+m chunks in LOGICAL
+        order, the parity rows as just formed: what check_magic_dev_rotated_refs would write behind the encode.
+        refs None: NULL."""
+        _check(lib().lsec_encode_magic_dev_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes,
+                                                   block_size, n_shift, first_stripe, magic_ptr or None, stream),
+               "lsec_encode_magic_dev_rotated")
+
+    def encode_magic_dev_rotated(self, devs, n_shift: int, first_stripe: int, magic, stream=None) -> None:
+        """torch: encode_magic_dev_rotated_refs over devs [k+m, N, C], the physical devices of a rotated LUN (devs[i, s]:
+        the chunk of stripe s on device i); magic: uint8 device tensor of 4 bytes per stripe, contiguous."""
+        if devs.dim() != 3 or devs.dtype.itemsize != 1 or not devs.is_cuda or devs.stride(2) != 1:
+            raise ValueError("devs must be a uint8 device tensor [k+m, N, C] with contiguous chunks")
+        n, size = devs.shape[1], devs.shape[2]
+        if magic.dtype.itemsize != 1 or not magic.is_cuda or not magic.is_contiguous() or magic.numel() != 4 * n:
+            raise ValueError(f"magic must be a contiguous device tensor of {4 * n} elements of 1 byte")
+        refs = [(devs[i].data_ptr(), devs.stride(1)) for i in range(devs.shape[0])]
+        self.encode_magic_dev_rotated_refs(refs, n, size, n_shift, first_stripe, magic.data_ptr(), _stream_handle(stream))
+
     def update_dev_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int, cols,
                                 fresh_refs, store: bool = False, stream: int = 0) -> None:
         """lsec_update_dev_rotated: update_dev_refs over the PHYSICAL devices of a rotated LUN.  cols are logical
@@ -974,14 +998,18 @@ PATMAGIC_FAMILIES = ("patmagic",)
 CHKMAGIC_FAMILIES = ("chkmagic", "chkmagicrot")
 
 
+# and behind those (CHKMAGIC_FAMILIES stays as it is too): family number 15, the rotated encode that leaves the magics
+ENCMAGIC_FAMILIES = ("encmagicrot",)
+
+
 def _form(v) -> Form:
-    return Form((FORM_FAMILIES + MASKED_FAMILIES + MAGIC_FAMILIES + PATMAGIC_FAMILIES + CHKMAGIC_FAMILIES)[v[0] - 1],
-                bool(v[1]), *(int(x) for x in v[2:8]))
+    return Form((FORM_FAMILIES + MASKED_FAMILIES + MAGIC_FAMILIES + PATMAGIC_FAMILIES + CHKMAGIC_FAMILIES +
+                 ENCMAGIC_FAMILIES)[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
 
 
 def launch_record() -> list:
     """Test hook: the Forms this thread's last check_dev / locate_dev / decode_dev_patterns / decode_dev_rotated
-    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated / update_dev_masked(_rotated) / update_magic_dev_masked(_rotated) / decode_magic_dev_patterns / decode_magic_dev_rotated / check_magic_dev(_rotated) call launched, in order (a locate with repair: its patterned
+    / check_dev_rotated / locate_dev_rotated / update_dev / encode_dev_rotated / update_dev_rotated / update_dev_masked(_rotated) / update_magic_dev_masked(_rotated) / decode_magic_dev_patterns / decode_magic_dev_rotated / check_magic_dev(_rotated) / encode_magic_dev_rotated call launched, in order (a locate with repair: its patterned
     decode too; a split call: every launch)."""
     buf = (C.c_int * (8 * 16))()
     n = lib().lsec_test_launch_record(buf, 16)
@@ -1039,6 +1067,15 @@ def predict_check_magic_form(rotated: bool, plan_kernel: int, k: int, rows: int,
     return _form(out)
 
 
+def predict_encode_magic_form(plan_kernel: int, k: int, rows: int, packet: int = 0, block_size: int = 0) -> Form:
+    """Test hook (no GPU): the Form ("encmagicrot") encode_magic_dev_rotated_refs launches for a plan of kernel 1 or 2
+    with k inputs and `rows` rows, asked of the functions the dispatch itself calls."""
+    out = (C.c_int * 8)()
+    _check(lib().lsec_test_predict_encode_magic_form(plan_kernel, k, rows, packet, block_size, out),
+           "lsec_test_predict_encode_magic_form")
+    return _form(out)
+
+
 def predict_forms(call: str, plan_kernel: int, k: int, rows: int, packet: int = 0, block_size: int = 0,
                   repair: bool = False) -> list:
     """Test hook (no GPU): what launch_record() holds after one unsplit call of `call` (a family name): its
@@ -1056,7 +1093,7 @@ def fixed_k() -> tuple:
 
 
 def set_pattern_split(stripes: int = 0) -> None:
-    """Test hook: a patterned decode (and update_dev, encode_dev_rotated, update_dev_rotated) launches at most `stripes` stripes at a time (0: no extra split)."""
+    """Test hook: a patterned decode (and update_dev, encode_dev_rotated, encode_magic_dev_rotated, update_dev_rotated) launches at most `stripes` stripes at a time (0: no extra split)."""
     lib().lsec_test_set_pattern_split(int(stripes))
 
 
