@@ -44,13 +44,18 @@ FIRST_HUGE = (1 << 40) + 3
 _ref_plans = {}
 
 
+def spec(code):
+    """(method, k, m, packet) of a code: a name of CODES, or the tuple itself (tests/scrub_forms.py's plans)"""
+    return CODES[code] if isinstance(code, str) else tuple(code)
+
+
 def sliced(code):
-    return CODES[code][3] != 0
+    return spec(code)[3] != 0
 
 
 def patterns_of(code):
     """empty, one data chunk, one parity chunk (raid4: the parity alone, which writes nothing), two mixed, m erasures"""
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     pats = [[], [1], [k + m - 1]]
     if m >= 2:
         pats.append([2, k])
@@ -70,7 +75,7 @@ def ids_of(npat):
 
 
 def form_of(code, packet, rmax=None):
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     return E.predict_pattern_magic_form(2 if sliced(code) else 1, k, m if rmax is None else rmax, packet)
 
 
@@ -86,20 +91,20 @@ def shapes(code, rmax=None):
 
 
 def make_plan(code, packet, size):
-    method, k, m, _ = CODES[code]
+    method, k, m, _ = spec(code)
     p = L.Plan.new(method, size, k, m, 8, packet, 1 if method == L.RAID4 else 8)
     assert p.form_encoding_matrix() == 0 and p.form_decoding_matrix() == 0
     return p
 
 
 def effective(code, pat):
-    method, k, _, _ = CODES[code]
+    method, k, _, _ = spec(code)
     return [] if (method == L.RAID4 and pat and min(pat) >= k) else sorted(set(pat))
 
 
 def ref_decode(code, packet, stripe, pat):
     """the reference's decode of stripe [k+m, C] as it lies in memory (the erased rows hold whatever they hold)"""
-    method, k, m, _ = CODES[code]
+    method, k, m, _ = spec(code)
     out = np.ascontiguousarray(stripe).copy()
     pat = effective(code, pat)
     if not pat:
@@ -144,7 +149,7 @@ class Case:
 
     def __init__(self, torch, code, packet, size, layout, before, outputs):
         self.torch, self.code, self.packet, self.size = torch, code, packet, size
-        _, self.k, self.m, _ = CODES[code]
+        _, self.k, self.m, _ = spec(code)
         self.lay = LY.plan_layout(layout, self.k, self.m, NSTRIPES, size, outputs=tuple(outputs))
         LY.check_layout(self.lay)
         self.before = LY.images(self.lay, before, ())[0]
@@ -203,8 +208,8 @@ def patterned_inputs(code, packet, size, pats, ids, full=None):
     """(before, want, words): the stripes as the call finds them -- garbage in the erased slots, and in two chunks of
     the skipped stripe -- the reference's decode of each, and zlib's magics of those (the skipped stripe: its entry
     word)"""
-    _, k, m, _ = CODES[code]
-    full = TC.stripes(CODES[code], packet, size, NSTRIPES) if full is None else full
+    _, k, m, _ = spec(code)
+    full = TC.stripes(spec(code), packet, size, NSTRIPES) if full is None else full
     before = np.array(full)
     want = np.empty_like(before)
     words = []
@@ -232,9 +237,9 @@ def test_the_yardstick_decodes_what_the_reference_encoded(cuda):
     for the form, and the `cuda` fixture has torch bring up its HIP runtime before that library is loaded: the
     order every GPU test here has.)"""
     for code in CODES:
-        _, k, m, _ = CODES[code]
+        _, k, m, _ = spec(code)
         packet, size = shapes(code)[1]
-        full = TC.stripes(CODES[code], packet, size, NSTRIPES)
+        full = TC.stripes(spec(code), packet, size, NSTRIPES)
         for pat in patterns_of(code):
             broken = np.array(full[0])
             broken[pat] = LY.GARBAGE
@@ -268,7 +273,7 @@ def test_tables_of_one_row_and_of_none(cuda, code):
     the empty pattern, for raid4 the parity alone too -- whose tiles only checksum: the paranoid read's verify"""
     import torch
 
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     for pats in ([[0], [k - 1], [k]] if m > 1 else [[0], [k - 1]], [[], [k]] if m == 1 else [[]]):
         ids = ids_of(len(pats))
         rmax = max(1, max(len(effective(code, p)) for p in pats))
@@ -287,11 +292,11 @@ def test_corruption_in_an_unused_survivor(cuda, code):
     positions"""
     import torch
 
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     pats = [[1], [0, 2]] if m > 2 else [[1]]  # the decode reads the first k survivors; the last parity chunk is unused
     ids = [s % len(pats) for s in range(NSTRIPES)]
     packet, size = shapes(code)[-1]
-    full = np.array(TC.stripes(CODES[code], packet, size, NSTRIPES))
+    full = np.array(TC.stripes(spec(code), packet, size, NSTRIPES))
     clean_before, clean_want, clean_words = patterned_inputs(code, packet, size, pats, ids)
     with make_plan(code, packet, size) as p:
         for s in range(NSTRIPES):
@@ -310,11 +315,11 @@ def test_corruption_in_a_used_survivor(cuda, code):
     corrupt stripe"""
     import torch
 
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     pats = [[1], [0, k]]
     ids = [s % len(pats) for s in range(NSTRIPES)]
     packet, size = shapes(code)[-1]
-    full = np.array(TC.stripes(CODES[code], packet, size, NSTRIPES))
+    full = np.array(TC.stripes(spec(code), packet, size, NSTRIPES))
     _, clean_want, _ = patterned_inputs(code, packet, size, pats, ids)
     for s in range(NSTRIPES):
         full[s, 3, (s * 977 + 5) % size] ^= TC.FLIP
@@ -370,9 +375,9 @@ def rotated_inputs(code, packet, size, lost, n_shift, first):
     """(before, want, words): the PHYSICAL devices [N, n, C] -- device i holds logical chunk (i + rot_s) mod n, the lost
     devices garbage -- the devices after the reference's decode of each logical stripe, zlib's magics of the logical
     stripes"""
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     n = k + m
-    full = TC.stripes(CODES[code], packet, size, NSTRIPES)
+    full = TC.stripes(spec(code), packet, size, NSTRIPES)
     before, want, words = np.empty_like(full), np.empty_like(full), []
     for s in range(NSTRIPES):
         rot = ((first + s) * n_shift) % n
@@ -432,7 +437,7 @@ def test_two_streams(cuda, code):
     ids = ids_of(len(pats))
     packet, size = shapes(code)[-1]
     b1, w1, m1 = patterned_inputs(code, packet, size, pats, ids)
-    other = np.array(TC.stripes(CODES[code], packet, size, 2 * NSTRIPES)[NSTRIPES:])
+    other = np.array(TC.stripes(spec(code), packet, size, 2 * NSTRIPES)[NSTRIPES:])
     b2, w2, m2 = patterned_inputs(code, packet, size, pats, ids, other)
     assert m1 != m2
     c1 = Case(torch, code, packet, size, "packed", b1, outputs_of(pats))
@@ -457,7 +462,7 @@ def test_torch_form(cuda):
     import torch
 
     code, size = "rs63", 4096
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     pats = [[0], [1, 7], []]
     ids = [s % 3 for s in range(NSTRIPES)]
     before, want, words = patterned_inputs(code, 0, size, pats, ids)

@@ -48,6 +48,9 @@ FIRSTS, NOISE, SPLIT = TRW.FIRSTS, TRW.NOISE, 3
 
 
 def spec(code):
+    """(method, k, m, packet) of a code: a name of CODES or EDGES, or the tuple itself (tests/scrub_forms.py's plans)"""
+    if not isinstance(code, str):
+        return tuple(code)
     return CODES[code] if code in CODES else EDGES[code]
 
 

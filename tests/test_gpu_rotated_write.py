@@ -42,12 +42,17 @@ NOISE = 0x9D
 _updated = {}
 
 
+def spec(code):
+    """(method, k, m, packet) of a code: a name of CODES, or the tuple itself (tests/scrub_forms.py's plans)"""
+    return CODES[code] if isinstance(code, str) else tuple(code)
+
+
 def shapes(code):
     return list(SLICED_SIZES[code] if code in SLICED else BYTEWISE_SIZES)
 
 
 def geometry(code):
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     return k, m, k + m, k + m + 2
 
 
@@ -62,13 +67,13 @@ def rotations(n):
 
 
 def col_lists(code):
-    k = CODES[code][1]
+    k = spec(code)[1]
     return [(0,), (k - 1,), (k - 2, 1), tuple(range(k))]
 
 
 def form_of(family, code, packet, size):
-    _, k, m, _ = CODES[code]
-    return E.predict_form(family, 2 if code in SLICED else 1, k, m, packet, size)
+    _, k, m, _ = spec(code)
+    return E.predict_form(family, 2 if spec(code)[3] else 1, k, m, packet, size)
 
 
 def fresh_chunks(code, packet, size, cols):
@@ -79,12 +84,12 @@ def fresh_chunks(code, packet, size, cols):
 
 def updated(code, packet, full, cols, fresh):
     """the logical stripes [N, k+m, C] the reference has after the write: data with the chunks replaced, its encode"""
-    k = CODES[code][1]
+    k = spec(code)[1]
     out = full.copy()
     for i, j in enumerate(cols):
         out[:, j] = fresh[:, i]
     for s in range(full.shape[0]):
-        out[s, k:] = TC.ref_encode(CODES[code], packet, out[s, :k])
+        out[s, k:] = TC.ref_encode(spec(code), packet, out[s, :k])
     return out
 
 
@@ -94,7 +99,7 @@ def updated_consistent(code, packet, size, cols):
     if key not in _updated:
         nstripes = geometry(code)[3]
         fresh = fresh_chunks(code, packet, size, cols)
-        u = updated(code, packet, TC.stripes(CODES[code], packet, size, nstripes), cols, fresh)
+        u = updated(code, packet, TC.stripes(spec(code), packet, size, nstripes), cols, fresh)
         fresh.setflags(write=False)
         u.setflags(write=False)
         _updated[key] = (fresh, u)
@@ -107,11 +112,11 @@ class Bench:
     def __init__(self, torch, code, packet, size, layout, cols=None, fresh=None):
         self.torch, self.code, self.packet, self.size = torch, code, packet, size
         self.k, self.m, self.n, self.nstripes = geometry(code)
-        self.full = TC.stripes(CODES[code], packet, size, self.nstripes)
+        self.full = TC.stripes(spec(code), packet, size, self.nstripes)
         self.lay = LY.plan_layout(layout, self.k, self.m, self.nstripes, size, outputs=range(self.k, self.n))
         LY.check_layout(self.lay)
         self.arena, self.refs, _ = LY.to_device(torch, self.lay, np.full(self.lay.total, LY.GARBAGE, np.uint8))
-        self.plan = TC.make_plan(CODES[code], packet, size)
+        self.plan = TC.make_plan(spec(code), packet, size)
         self.tag = f"{code} packet={packet} C={size} {layout}"
         if cols is not None:
             self.cols = tuple(cols)
@@ -314,7 +319,7 @@ def test_update_keeps_the_syndrome(cuda, code):
                     stored[s, c] = got[a:a + size]
             assert np.array_equal(got, bench.image(stored, n_shift, first)), "a data chunk is not where the write put it"
             new = check()
-            want = np.array([TC.expected_mask(CODES[code], packet, stored[s]) for s in range(nstripes)], np.uint32)
+            want = np.array([TC.expected_mask(spec(code), packet, stored[s]) for s in range(nstripes)], np.uint32)
             assert np.array_equal(new, want), (store, new, want)
             assert np.array_equal(new, old), (store, new, old)
     finally:

@@ -42,16 +42,22 @@ NSTRIPES, SPLIT = 5, 2  # split: three launches of 2, 2 and 1 stripes
 _fresh, _parity = {}, {}
 
 
+def spec(code):
+    """(method, k, m, packet) of a code: a name of CODES, or the tuple itself (tests/scrub_forms.py's plans)"""
+    return CODES[code] if isinstance(code, str) else tuple(code)
+
+
 def case_id(case):
-    return case[0] + "-" + "_".join(str(j) for j in case[1])
+    name = case[0] if isinstance(case[0], str) else "_".join(str(x) for x in case[0])
+    return name + "-" + "_".join(str(j) for j in case[1])
 
 
 def sliced(code):
-    return CODES[code][3] != 0
+    return spec(code)[3] != 0
 
 
 def form_of(code, packet, size):
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     return E.predict_form("upd", 2 if sliced(code) else 1, k, m, packet, size)
 
 
@@ -73,7 +79,7 @@ def fresh_chunks(code, packet, size, cols):
     """uint8 [N, c, C], random; computed once per shape, never modified"""
     key = (code, packet, size, tuple(cols))
     if key not in _fresh:
-        rng = np.random.default_rng([CODES[code][1], packet, size, *cols])
+        rng = np.random.default_rng([spec(code)[1], packet, size, *cols])
         f = rng.integers(0, 256, (NSTRIPES, len(cols), size), dtype=np.uint8)
         f.setflags(write=False)
         _fresh[key] = f
@@ -82,19 +88,19 @@ def fresh_chunks(code, packet, size, cols):
 
 def updated(code, packet, full, cols, fresh):
     """the stripes [N, k+m, C] the reference has after the write: data with the chunks replaced, its encode"""
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     out = full.copy()
     for i, j in enumerate(cols):
         out[:, j] = fresh[:, i]
     for s in range(full.shape[0]):
-        out[s, k:] = TC.ref_encode(CODES[code], packet, out[s, :k])
+        out[s, k:] = TC.ref_encode(spec(code), packet, out[s, :k])
     return out
 
 
 def updated_consistent(code, packet, size, cols):
     key = (code, packet, size, tuple(cols))
     if key not in _parity:
-        full = TC.stripes(CODES[code], packet, size, NSTRIPES)
+        full = TC.stripes(spec(code), packet, size, NSTRIPES)
         u = updated(code, packet, full, cols, fresh_chunks(code, packet, size, cols))
         u.setflags(write=False)
         _parity[key] = u
@@ -106,9 +112,9 @@ class Bench:
 
     def __init__(self, torch, code, packet, size, layout, cols, fresh=None):
         self.torch, self.code, self.packet, self.size, self.cols = torch, code, packet, size, tuple(cols)
-        _, self.k, self.m, _ = CODES[code]
+        _, self.k, self.m, _ = spec(code)
         k, m, c = self.k, self.m, len(cols)
-        self.full = TC.stripes(CODES[code], packet, size, NSTRIPES)
+        self.full = TC.stripes(spec(code), packet, size, NSTRIPES)
         self.fresh = fresh_chunks(code, packet, size, cols) if fresh is None else fresh
         self.lay = LY.plan_layout(layout, k, m, NSTRIPES, size, outputs=range(k, k + m))
         self.flay = LY.plan_layout(layout, c, 0, NSTRIPES, size)
@@ -122,7 +128,7 @@ class Bench:
         self.dbefore = rng.integers(0, 256, self.lay.total, dtype=np.uint8)
         self.darena, decoys, _ = LY.to_device(torch, self.lay, self.dbefore)
         self.refs = [self.real_refs[i] if i in cols or i >= k else decoys[i] for i in range(k + m)]
-        self.plan = TC.make_plan(CODES[code], packet, size)
+        self.plan = TC.make_plan(spec(code), packet, size)
         self.form = form_of(code, packet, size)
 
     def close(self):
@@ -189,7 +195,7 @@ def test_on_a_stream_of_its_own(cuda, code):
     import torch
 
     packet, size = shapes(code)[-1]
-    bench = Bench(torch, code, packet, size, "off8", (CODES[code][1] - 1,))
+    bench = Bench(torch, code, packet, size, "off8", (spec(code)[1] - 1,))
     try:
         st = torch.cuda.Stream()
         bench.run(True, stream=st.cuda_stream)
@@ -202,14 +208,14 @@ def test_torch_form(cuda):
     import torch
 
     code, size, cols = "rs63", 4096, (3, 0)
-    _, k, m, _ = CODES[code]
-    full = TC.stripes(CODES[code], 0, size, NSTRIPES)
+    _, k, m, _ = spec(code)
+    full = TC.stripes(spec(code), 0, size, NSTRIPES)
     fresh = fresh_chunks(code, 0, size, cols)
     want = updated(code, 0, full, cols, fresh)
     for store in (False, True):
         data, par = torch.from_numpy(full[:, :k].copy()).cuda(), torch.from_numpy(full[:, k:].copy()).cuda()
         f = torch.from_numpy(fresh.copy()).cuda()
-        with TC.make_plan(CODES[code], 0, size) as p:
+        with TC.make_plan(spec(code), 0, size) as p:
             p.update_dev(data, par, cols, f, store=store)
             torch.cuda.synchronize()
         assert np.array_equal(par.cpu().numpy(), want[:, k:])
@@ -229,7 +235,7 @@ def test_keeps_the_syndrome_of_an_inconsistent_stripe(cuda, case):
     import torch
 
     code, cols = case
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     packet, size = shapes(code)[-1]
     bench = Bench(torch, code, packet, size, "mixed", cols)
     words = TC.Words(torch, NSTRIPES)
@@ -266,7 +272,7 @@ def test_keeps_the_syndrome_of_an_inconsistent_stripe(cuda, case):
             st = stored()
             for i, j in enumerate(cols):
                 assert np.array_equal(st[:, j], bench.fresh[:, i])
-            want = np.array([TC.expected_mask(CODES[code], packet, st[s]) for s in range(NSTRIPES)], np.uint32)
+            want = np.array([TC.expected_mask(spec(code), packet, st[s]) for s in range(NSTRIPES)], np.uint32)
             assert np.array_equal(new, want), (store, new, want)
             assert np.array_equal(new, old), (store, new, old)
     finally:
@@ -282,7 +288,7 @@ def test_identity(cuda, case):
 
     code, cols = case
     for packet, size in shapes(code)[-2:]:
-        full = TC.stripes(CODES[code], packet, size, NSTRIPES)
+        full = TC.stripes(spec(code), packet, size, NSTRIPES)
         bench = Bench(torch, code, packet, size, "off8", cols, fresh=np.ascontiguousarray(full[:, list(cols)]))
         try:
             for store in (False, True):

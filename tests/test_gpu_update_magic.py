@@ -39,7 +39,7 @@ PAD = 16  # canary bytes on each side of the magic words
 
 
 def form_of(code, packet, size):
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = TM.spec(code)
     return E.predict_masked_magic_form(2 if TM.sliced(code) else 1, k, m, packet, size)
 
 
@@ -211,11 +211,11 @@ def test_extremes(cuda, code, old, new):
     0xFF (the largest positive one): all k columns enabled, the all-ones mask in every stripe"""
     import torch
 
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = TM.spec(code)
     packet, size = shapes(code)[-1]
     full = np.empty((NSTRIPES, k + m, size), np.uint8)
     full[:, :k] = old
-    full[:, k:] = TC.ref_encode(CODES[code], packet, full[0, :k])
+    full[:, k:] = TC.ref_encode(TM.spec(code), packet, full[0, :k])
     fresh = np.full((NSTRIPES, k, size), new, np.uint8)
     words = [TM.ALL_ONES] * NSTRIPES
     after = TM.updated(code, packet, full, TM.effective(k, words, ()), fresh)
@@ -239,7 +239,7 @@ def test_inconsistent_stripe(cuda, code):
     in the columns that do not change); its magic is zlib's over it"""
     import torch
 
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = TM.spec(code)
     packet, size = shapes(code)[-1]
     bench = Bench(torch, code, packet, size, "mixed")
     sets = bench.sets()
@@ -259,8 +259,8 @@ def test_inconsistent_stripe(cuda, code):
             for j in cols:
                 delta[j] = bad[s, j] ^ bench.fresh[s, j]
                 want[s, j] = bench.fresh[s, j]
-            want[s, k:] = bad[s, k:] ^ TC.ref_encode(CODES[code], packet, delta)
-        assert any(TC.expected_mask(CODES[code], packet, want[s]) for s in range(NSTRIPES))  # still inconsistent
+            want[s, k:] = bad[s, k:] ^ TC.ref_encode(TM.spec(code), packet, delta)
+        assert any(TC.expected_mask(TM.spec(code), packet, want[s]) for s in range(NSTRIPES))  # still inconsistent
         entry = adlers(bad)
         for store in (False, True):
             bench.magics = Magics(torch, entry)
@@ -334,13 +334,13 @@ def test_untouched_words(cuda, code):
     0xFFFFFFFF, one random -- come out byte-identical, split or not"""
     import torch
 
-    _, k, _, _ = CODES[code]
+    _, k, _, _ = TM.spec(code)
     packet, size = shapes(code)[-2]
     words = TM.masks_of(k)
     words[4] = 1 << DISABLED
     assert TM.effective(k, words)[2] == [] and TM.effective(k, words)[4] == []
     fresh, _ = TM.after_write(code, packet, size)
-    full = TC.stripes(CODES[code], packet, size, NSTRIPES)
+    full = TC.stripes(TM.spec(code), packet, size, NSTRIPES)
     after = TM.updated(code, packet, full, TM.effective(k, words), fresh)
     for rotated in (False, True):
         bench = Bench(torch, code, packet, size, "packed", rotated=rotated, masks=words)
@@ -378,7 +378,7 @@ def test_two_calls_compose(cuda, code):
     the first left, and the result is zlib's over the final stripes"""
     import torch
 
-    _, k, _, _ = CODES[code]
+    _, k, _, _ = TM.spec(code)
     packet, size = shapes(code)[-1]
     bench = Bench(torch, code, packet, size, "packed")
     first_words = bench.words

@@ -47,12 +47,17 @@ ALL_ONES = (1 << 64) - 1
 _after = {}
 
 
+def spec(code):
+    """(method, k, m, packet) of a code: a name of CODES, or the tuple itself (tests/scrub_forms.py's plans)"""
+    return CODES[code] if isinstance(code, str) else tuple(code)
+
+
 def sliced(code):
-    return CODES[code][3] != 0
+    return spec(code)[3] != 0
 
 
 def form_of(code, packet, size):
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     return E.predict_masked_form(2 if sliced(code) else 1, k, m, packet, size)
 
 
@@ -83,7 +88,7 @@ def effective(k, masks, disabled=(DISABLED,)):
 
 
 def fresh_chunks(code, packet, size):
-    _, k, _, _ = CODES[code]
+    _, k, _, _ = spec(code)
     rng = np.random.default_rng([k, packet, size, 77])
     return rng.integers(0, 256, (NSTRIPES, k, size), dtype=np.uint8)
 
@@ -91,14 +96,14 @@ def fresh_chunks(code, packet, size):
 def updated(code, packet, full, sets, fresh):
     """the logical stripes [N, k+m, C] the reference has after the write: each stripe's chunks `sets[s]` replaced,
     its encode; a stripe with an empty set as it was"""
-    _, k, _, _ = CODES[code]
+    _, k, _, _ = spec(code)
     out = full.copy()
     for s, cols in enumerate(sets):
         if not cols:
             continue
         for j in cols:
             out[s, j] = fresh[s, j]
-        out[s, k:] = TC.ref_encode(CODES[code], packet, out[s, :k])
+        out[s, k:] = TC.ref_encode(spec(code), packet, out[s, :k])
     return out
 
 
@@ -106,9 +111,9 @@ def after_write(code, packet, size):
     """(fresh, the reference's stripes after the masked write of the consistent stripes); once per shape, never modified"""
     key = (code, packet, size)
     if key not in _after:
-        _, k, _, _ = CODES[code]
+        _, k, _, _ = spec(code)
         fresh = fresh_chunks(code, packet, size)
-        u = updated(code, packet, TC.stripes(CODES[code], packet, size, NSTRIPES), effective(k, masks_of(k)), fresh)
+        u = updated(code, packet, TC.stripes(spec(code), packet, size, NSTRIPES), effective(k, masks_of(k)), fresh)
         fresh.setflags(write=False)
         u.setflags(write=False)
         _after[key] = (fresh, u)
@@ -135,10 +140,10 @@ class Bench:
 
     def __init__(self, torch, code, packet, size, layout, rotated=False, masks=None, fresh=None):
         self.torch, self.code, self.packet, self.size, self.rotated = torch, code, packet, size, rotated
-        _, self.k, self.m, _ = CODES[code]
+        _, self.k, self.m, _ = spec(code)
         k, m = self.k, self.m
         self.n = k + m
-        self.full = TC.stripes(CODES[code], packet, size, NSTRIPES)
+        self.full = TC.stripes(spec(code), packet, size, NSTRIPES)
         self.words = masks_of(k) if masks is None else list(masks)
         self.fresh = after_write(code, packet, size)[0] if fresh is None else fresh
         self.lay = LY.plan_layout(layout, k, m, NSTRIPES, size, outputs=range(k, k + m))
@@ -155,7 +160,7 @@ class Bench:
         # rotated: every device is real; unrotated: the column that is not enabled has a decoy behind its ref
         self.refs = list(self.real_refs) if rotated else [decoys[i] if i == DISABLED else self.real_refs[i] for i in range(k + m)]
         self.masks = Masks(torch, self.words)
-        self.plan = TC.make_plan(CODES[code], packet, size)
+        self.plan = TC.make_plan(spec(code), packet, size)
         self.form = form_of(code, packet, size)
         self.tag = f"{code} packet={packet} C={size} {layout}" + (" rotated" if rotated else "")
 
@@ -309,8 +314,8 @@ def test_torch_form(cuda):
     import torch
 
     code, size = "rs63", 4096
-    _, k, m, _ = CODES[code]
-    full = TC.stripes(CODES[code], 0, size, NSTRIPES)
+    _, k, m, _ = spec(code)
+    full = TC.stripes(spec(code), 0, size, NSTRIPES)
     fresh = fresh_chunks(code, 0, size)
     words = masks_of(k)
     want = updated(code, 0, full, effective(k, words, disabled=()), fresh)  # every column has a fresh buffer here
@@ -318,7 +323,7 @@ def test_torch_form(cuda):
         data, par = torch.from_numpy(full[:, :k].copy()).cuda(), torch.from_numpy(full[:, k:].copy()).cuda()
         f = torch.from_numpy(fresh.copy()).cuda()
         cols = torch.from_numpy(np.array(words, dtype=np.uint64).view(np.int64)).cuda()
-        with TC.make_plan(CODES[code], 0, size) as p:
+        with TC.make_plan(spec(code), 0, size) as p:
             p.update_dev_masked(data, par, cols, f, store=store)
             torch.cuda.synchronize()
         assert np.array_equal(par.cpu().numpy(), want[:, k:])
@@ -340,7 +345,7 @@ def test_keeps_the_syndrome_of_an_inconsistent_stripe(cuda, code, rotated):
     the data as stored after the update against the stored parity -- and the words the check gave before it."""
     import torch
 
-    _, k, m, _ = CODES[code]
+    _, k, m, _ = spec(code)
     n = k + m
     packet, size = shapes(code)[-1]
     n_shift, first = (1, FIRST_BIG) if rotated else (0, 0)
@@ -388,7 +393,7 @@ def test_keeps_the_syndrome_of_an_inconsistent_stripe(cuda, code, rotated):
                 for j in range(k):
                     assert np.array_equal(stored[s, j], bench.fresh[s, j] if j in cols else logical[s, j]), (s, j)
             new = check()
-            want = np.array([TC.expected_mask(CODES[code], packet, stored[s]) for s in range(NSTRIPES)], np.uint32)
+            want = np.array([TC.expected_mask(spec(code), packet, stored[s]) for s in range(NSTRIPES)], np.uint32)
             assert np.array_equal(new, want), (store, new, want)
             assert np.array_equal(new, old), (store, new, old)
     finally:
