@@ -22,6 +22,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdint>
@@ -188,6 +189,9 @@ struct CodingJob {
   const void *image = nullptr;  // on the current device, cached on the plan
   int R = 0;                    // its output rows
   std::vector<int> in_ids, out_ids;
+  // the host's R x k GF(2^8) rows behind a CoefCell image (the plan's, kept as long as the image), else null:
+  // what the launch record reads an image's plain-XOR row flags from (apply_first_row_ones)
+  const uint8_t *gf8_rows = nullptr;
 };
 int encode_job(PlanExt *e, CodingJob *job);  // in 0..k-1, out k..k+R-1 (R: m; 2 for r6, 1 for raid4)
 // `ids`: parse_erasures' list.  in: the survivors, out: the erased; kind: the plan's, or KBYTEWISE for a
@@ -211,8 +215,40 @@ inline ShardRef shard_from(const lsec_shard_t &sh, long long s0) {
 inline ShardRef shard_from(const ShardRef &sh, long long s0) {
   return {sh.base + static_cast<uint64_t>(s0) * sh.stride, sh.stride};
 }
+// gf8_rows: CodingJob::gf8_rows, for the launch record alone (null: every launch records the flag as clear)
 int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in, const ShardRef *out, int nstripes,
-                  long long size, int packet, hipStream_t st, int w = 8);
+                  long long size, int packet, hipStream_t st, int w = 8, const uint8_t *gf8_rows = nullptr);
+
+// The plain-XOR row rule: every coefficient of the row is 1.  host_cells flags such a row's first cell
+// (kCellXorRow) by it, and the launch record reads the flag of a launch's first cell back by it.
+inline bool row_all_ones(const uint8_t *row, int cols) {
+  return std::all_of(row, row + cols, [](uint8_t c) { return c == 1; });
+}
+
+// The launches of one K x R apply of `kind` at word size w: input groups of at most lsec::kMaxK (the later ones
+// accumulate), each cut into launches of at most 8 rows, 2 for the bitmatrix kernels and 4 at w = 32.
+// fn(k0, kg, r0, rn) -> 0 or -1 takes inputs [k0, k0 + kg) and rows [r0, r0 + rn).  enqueue_apply launches by
+// it and the prediction hooks (lsec_test_predict_apply) list by it.
+inline int apply_rows_per_launch(int kind, int w) {
+  return kind == KBITMATRIX ? 2 : ((kind == KBITSLICEDW || kind == KWORDWISE) && w == 32) ? 4 : 8;
+}
+template <typename F>
+int for_apply_launches(int kind, int K, int R, int w, F &&fn) {
+  const int rmax = apply_rows_per_launch(kind, w);
+  for (int k0 = 0; k0 < K; k0 += lsec::kMaxK)
+    for (int r0 = 0; r0 < R; r0 += rmax)
+      if (fn(k0, std::min(lsec::kMaxK, K - k0), r0, std::min(rmax, R - r0))) return -1;
+  return 0;
+}
+// The kCellXorRow flag of the first cell of the launch that starts at input k0 and row r0 of a CoefCell image
+// of the K-column rows gf8_rows (host_cells, group_image): set on a row of ones, in its first group's cell alone
+inline bool apply_first_row_ones(const uint8_t *gf8_rows, int K, int k0, int r0) {
+  return gf8_rows && k0 == 0 && row_all_ones(gf8_rows + static_cast<size_t>(r0) * K, K);
+}
+// lsec_encode_magic_dev's one-pass condition on the plan's shape (its geometry check comes on top)
+bool encode_magic_fuses(int kind, int k, int m);
+// test hook (lsec_test_hold_networks): while set, no compiled network counts as ready
+bool networks_held();
 int encode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, hipStream_t st);
 int decode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *erasures, hipStream_t st);
 // one-pass parity check: syndrome[s] bit r = parity row r of stripe s differs from the stored chunk

@@ -551,6 +551,38 @@ bool predict_encode_magic_launch(bool sliced, int K, int R, int packet, int dw_p
 // the K with fixed-K forms (LSEC_FIXED_K), ascending -> how many there are; out[0 .. min(that, max))
 int fixed_k_list(int *out, int max);
 
+// The apply family: what lsec_encode_dev, lsec_decode_dev and lsec_encode_magic_dev launch (test hooks
+// lsec_test_apply_record / lsec_test_predict_apply, ec_plan.cpp).  Its kernels take more template arguments
+// than a LaunchForm names, so it has a record of its own, kept apart from the one above:
+//   kind   1 k_gf8_bytewise, 2 k_gf8_bitsliced, 3 k_bitmatrix / k_bitmatrix_any, 4 k_gfw_wordwise /
+//          k_gfw_transposed, 5 k_gfw_bitsliced (the KernelKind of ec_engine.h)
+//   R, KC, IT, VW, BF   bytewise, as in a LaunchForm;  DW  kind 2's dwords per lane;  w  kinds 3-5
+//   acc    the ACC instantiation (a later input group of a stripe of more than kMaxK inputs)
+//   magic  the MG instantiation (lsec_encode_magic_dev's fused pass)
+//   sub    kind 3: 1 the kernel of its word size, 0 k_bitmatrix_any;  kind 4: 1 k_gfw_transposed,
+//          0 the mask-per-bit k_gfw_wordwise;  else 0
+//   loop   bytewise kernels that hold two whole tile loops (bw_dual_loops): 1 the plain-XOR first row's
+//          (X0), 0 the other's, as the flag of the launch's first cell selects; -1: the kernel has one loop
+// The per-R dispatch functions record the form where the template arguments are spelled out; `loop` comes
+// from apply_record_first_row, which the engine sets from its host matrix before each launch (nothing is
+// read back from the device).
+struct ApplyForm {
+  int kind, R, KC, IT, VW, BF, DW, w, acc, magic, sub, loop;
+};
+constexpr int kApplyFormInts = 12;
+constexpr int kApplyRecordMax = 64;  // forms kept (the count goes on); RS(200+17): 4 input groups x 3 row launches
+constexpr int kApplyCountMax = 1 << 20;  // where the launch count stops (record_apply)
+void record_apply(const ApplyForm &f);  // nothing on a thread that never called apply_record_reset()
+void apply_record_reset();
+void apply_record_first_row(bool all_ones);  // of the launches that follow, until set again
+int apply_record(ApplyForm *out, int max);   // -> launches recorded; out[0 .. min(that, max, kApplyRecordMax))
+// The form one launch_bytewise / launch_bytewise_magic / launch_bitsliced / launch_bitmatrix /
+// launch_wordwise / launch_gfw_bitsliced call takes for K x R, from the functions those call; bw_variant
+// and bs_variant as lsec_set_kernel_variant takes them, dw_pref as launch_bitsliced does, first_row_ones
+// as apply_record_first_row.  No GPU is touched.  false: the launch would be refused.
+bool predict_apply_launch(int kind, int K, int R, int w, int packet, bool acc, bool magic, int dw_pref, int bw_variant,
+                          int bs_variant, bool first_row_ones, ApplyForm *out);
+
 // Work-sharing tiles.  The streaming kernels deal each XCD a contiguous eighth of the tiles
 // (xcd_remap), but the XCDs do not run at one rate: on the headline's memory shape the odd ones
 // take ~15 % longer per tile, every launch, so the even ones idle for the last 6-8 % of it

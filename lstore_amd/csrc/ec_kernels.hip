@@ -77,10 +77,11 @@ hipError_t by_r(int R, F f) {
 
 // Launch shape for a K x R bytewise launch (codes in ec_kernels_impl.h): an A/B variant when one
 // is set, else the automatic policy (bw_auto_code)
-int bytewise_shape(int K, int R) {
-  if (g_bw_variant > 0) return (g_bw_variant - 1) % kBwShapes;
+int bytewise_shape_for(int variant, int K, int R) {
+  if (variant > 0) return (variant - 1) % kBwShapes;
   return bw_auto_code(K, R);
 }
+int bytewise_shape(int K, int R) { return bytewise_shape_for(g_bw_variant, K, R); }
 
 // The grid of a tile-loop launch: nstripes stripes of `bytes` bytes of tile space each, in tiles
 // of `tile` bytes; grid_blocks > 0 overrides the default of one block per tile.  0: the tile
@@ -99,6 +100,18 @@ int lane_dwords(int want, int packet) {
   while (dw > 1 && packet % (4 * dw) != 0) dw >>= 1;
   return dw;
 }
+
+// dwords per lane of launch_bitsliced: the A/B variant when one is set, else the caller's preference (1, 2, 4),
+// else 1; the fused-magic and the accumulate kernels (not `plain`) have one dword per lane
+int apply_lane_dwords(int bs_variant, int dw_pref, bool plain, int packet) {
+  const int want = bs_variant != 0 ? bs_variant : dw_pref;
+  return lane_dwords(plain ? want : 1, packet);
+}
+
+// launch_wordwise's kernel: the transposed bit-sliced one (4*w bytes per lane) up to 8 rows at w = 16 and 4 at
+// w = 32; the mask-per-bit kernel (16 / 8 bytes per lane) beyond that
+// (lsec_set_kernel_variant's second argument 10 selects the mask-per-bit kernel: A/B runs)
+bool wordwise_transposed(int bs_variant, int w, int R) { return bs_variant != 10 && (w == 16 || R <= 4); }
 
 // dwords per lane of a bit-sliced check or locate (a locate of more than kLocWideRows rows: one)
 int scrub_lane_dwords(bool locates, int R, int dw_pref, int packet) {
@@ -312,9 +325,7 @@ hipError_t launch_bitsliced(const ApplyArgs &a, hipStream_t st, int grid_blocks,
       a.size % (8LL * a.packet) != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  // dwords per lane: the A/B variant when one is set, else the caller's preference (1, 2, 4), else 1
-  const int want = g_bs_variant != 0 ? g_bs_variant : dw_pref;
-  const int dw = lane_dwords(!a.magic_acc && !a.accumulate ? want : 1, a.packet);
+  const int dw = apply_lane_dwords(g_bs_variant, dw_pref, !a.magic_acc && !a.accumulate, a.packet);
   const int grid = tile_grid(kBlock * 4ull * dw, a.size / 8, a.nstripes, grid_blocks);
   if (!grid) return hipErrorInvalidValue;
   return by_r(a.R, [&](auto r) { return dispatch_bitsliced<decltype(r)::value>(a, st, grid, dw); });
@@ -345,10 +356,7 @@ hipError_t launch_wordwise(const ApplyArgs &a, hipStream_t st, int grid_blocks) 
   if (a.K < 1 || a.K > kMaxK || a.R < 1 || a.R > 8 || (a.w != 16 && a.w != 32) || !a.masks || a.size % 8 != 0)
     return hipErrorInvalidValue;
   if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
-  // transposed bit-sliced kernel (4*w bytes per lane) up to 8 rows at w = 16 and 4 at w = 32;
-  // the mask-per-bit kernel (16 / 8 bytes per lane) beyond that
-  // (lsec_set_kernel_variant's second argument 10 selects the mask-per-bit kernel: A/B runs)
-  const bool transposed = g_bs_variant != 10 && (a.w == 16 || a.R <= 4);
+  const bool transposed = wordwise_transposed(g_bs_variant, a.w, a.R);
   const int grid = tile_grid(kBlock * (transposed ? 4ull * a.w : a.w == 16 ? 16ull : 8ull), a.size, a.nstripes, grid_blocks);
   if (!grid) return hipErrorInvalidValue;
   if (transposed) return by_r(a.R, [&](auto r) { return dispatch_gfw_transposed<decltype(r)::value>(a, st, grid); });
@@ -860,6 +868,83 @@ bool predict_encode_magic_launch(bool sliced, int K, int R, int packet, int dw_p
   const BwForm f = encmagicrot_bytewise_form(K, R);
   *out = LaunchForm{kFormEncMagicRot, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
   return true;
+}
+
+// ------------------------------------------------------------------ the apply family's record
+namespace {
+thread_local ApplyForm tl_apply_forms[kApplyRecordMax];
+thread_local int tl_napply = 0;
+thread_local bool tl_first_row_ones = false;
+// Set by the first apply_record_reset() of a thread: only a thread that has made one of the three device calls
+// keeps a record.  The host-memory paths launch through the same dispatch from dispatcher, staging and
+// zero-copy threads that never reset: there record_apply does nothing.
+thread_local bool tl_apply_armed = false;
+
+// a form whose kernel holds the two loops takes the one the first row selects
+ApplyForm with_loop(ApplyForm f, bool first_row_ones) {
+  if (f.loop >= 0) f.loop = first_row_ones ? 1 : 0;
+  return f;
+}
+}  // namespace
+
+void record_apply(const ApplyForm &f) {
+  if (!tl_apply_armed) return;
+  if (tl_napply < kApplyRecordMax) tl_apply_forms[tl_napply] = with_loop(f, tl_first_row_ones);
+  // the count goes on past what is kept, and stops at kApplyCountMax: an armed thread that then launches through
+  // another path for days (the plan's function pointers) neither overflows it nor indexes by it
+  if (tl_napply < kApplyCountMax) ++tl_napply;
+}
+
+void apply_record_reset() {
+  tl_apply_armed = true;
+  tl_napply = 0;
+  tl_first_row_ones = false;
+}
+
+void apply_record_first_row(bool all_ones) { tl_first_row_ones = all_ones; }
+
+int apply_record(ApplyForm *out, int max) {
+  for (int i = 0; i < tl_napply && i < max && i < kApplyRecordMax; ++i) out[i] = tl_apply_forms[i];
+  return tl_napply;
+}
+
+bool predict_apply_launch(int kind, int K, int R, int w, int packet, bool acc, bool magic, int dw_pref, int bw_variant,
+                          int bs_variant, bool first_row_ones, ApplyForm *out) {
+  if (K < 1 || K > kMaxK || R < 1 || R > 8) return false;
+  switch (kind) {
+    case 1: {  // launch_bytewise / launch_bytewise_magic, dispatch_bytewise / bytewise_k / dispatch_bytewise_magic
+      const int kc = has_fixed_k(K) ? K : 0;
+      if (magic) {
+        if (acc) return false;
+        *out = with_loop(bw_apply_form(R, kc, bytewise_magic_it(K), true, 4, true), first_row_ones);
+        return true;
+      }
+      const BwShape sh = bw_shape(acc ? 1 : bytewise_shape_for(bw_variant, K, R));
+      *out = with_loop(acc ? bw_apply_form(R, 0, 1, true, 4, false, true) : bw_apply_form(R, kc, sh.it, sh.bf, sh.vw), first_row_ones);
+      return true;
+    }
+    case 2: {  // launch_bitsliced, dispatch_bitsliced
+      if (packet <= 0 || packet % 4 != 0 || (acc && magic)) return false;
+      *out = bs_apply_form(R, apply_lane_dwords(bs_variant, dw_pref, !magic && !acc, packet), magic, acc);
+      return true;
+    }
+    case 3:  // launch_bitmatrix, dispatch_bitmatrix
+      if (R > 2 || w < 2 || w > kMaxW || packet <= 0 || packet % 4 != 0 || magic) return false;
+      *out = bm_apply_form(R, w, !acc && bitmatrix_w_supported(w), acc);
+      return true;
+    case 4: {  // launch_wordwise, dispatch_gfw_transposed / dispatch_wordwise
+      if ((w != 16 && w != 32) || magic) return false;
+      const bool transposed = wordwise_transposed(bs_variant, w, R);
+      if (transposed && w == 32 && R > 4) return false;
+      *out = gfw_apply_form(4, R, w, transposed, acc);
+      return true;
+    }
+    case 5:  // launch_gfw_bitsliced, dispatch_gfw_bitsliced
+      if ((w != 16 && w != 32) || R > (w == 32 ? 4 : 8) || packet <= 0 || packet % 4 != 0 || magic) return false;
+      *out = gfw_apply_form(5, R, w, false, acc);
+      return true;
+    default: return false;
+  }
 }
 
 int fixed_k_list(int *out, int max) {

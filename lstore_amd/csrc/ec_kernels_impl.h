@@ -655,9 +655,11 @@ __device__ __forceinline__ void bytewise_tiles(const ApplyArgs &a) {
 // instantiations once per wave: a uniform branch outside the tile loop, no merges inside it.
 // Only codes with K*R >= 40 cells take the dual form: narrow codes are HBM-bound, and the
 // second path would only raise the kernel's register allocation (RS 6+3: 56 -> 108 VGPRs).
+constexpr bool bw_dual_loops(int R, int KC, bool BF) { return BF && R >= 2 && (KC == 0 || KC * R >= 40); }
+
 template <int R, int KC, int IT, bool BF, int VW, bool MG = false, bool ACC = false>
 __global__ __launch_bounds__(kBlock) void k_gf8_bytewise(ApplyArgs a) {
-  if constexpr (BF && R >= 2 && (KC == 0 || KC * R >= 40)) {
+  if constexpr (bw_dual_loops(R, KC, BF)) {
     if (const_cells(a.cells)->pad & kCellXorRow) {
       bytewise_tiles<R, KC, IT, BF, VW, MG, true, ACC>(a);
       return;
@@ -1252,20 +1254,31 @@ constexpr BwShape bw_auto(int K, int R) { return bw_shape(bw_auto_code(K, R)); }
 // encode + magic is branch-free at 16 B units for every R: the rule's steps for two or more rows
 constexpr int bytewise_magic_it(int K) { return bw_auto(K, 2).it; }
 
+// the record of a k_gf8_bytewise<R, KC, IT, BF, VW, MG, ACC> launch (ec_kernels.h, ApplyForm); loop: 1 where the
+// kernel holds the two loops, which record_apply and predict_apply_launch turn into the loop the first row selects
+constexpr ApplyForm bw_apply_form(int R, int KC, int IT, bool BF, int VW, bool MG = false, bool ACC = false) {
+  return ApplyForm{1, R, KC, IT, VW, BF ? 1 : 0, 0, 0, ACC ? 1 : 0, MG ? 1 : 0, 0, bw_dual_loops(R, KC, BF) ? 1 : -1};
+}
+
 template <int R, int IT, bool BF, int VW>
 hipError_t bytewise_k(const ApplyArgs &a, hipStream_t st, int grid) {
   switch (a.K) {
-#define LSEC_BW_K(KK) \
-  case KK: return launch_tiled(&k_gf8_bytewise<R, KK, IT, BF, VW>, grid, st, a);
+#define LSEC_BW_K(KK)                                \
+  case KK:                                           \
+    record_apply(bw_apply_form(R, KK, IT, BF, VW)); \
+    return launch_tiled(&k_gf8_bytewise<R, KK, IT, BF, VW>, grid, st, a);
     LSEC_FIXED_K(LSEC_BW_K)
 #undef LSEC_BW_K
-    default: return launch_tiled(&k_gf8_bytewise<R, 0, IT, BF, VW>, grid, st, a);
+    default:
+      record_apply(bw_apply_form(R, 0, IT, BF, VW));
+      return launch_tiled(&k_gf8_bytewise<R, 0, IT, BF, VW>, grid, st, a);
   }
 }
 
 template <int R>
 hipError_t dispatch_bytewise(const ApplyArgs &a, hipStream_t st, int grid, int shape) {
   if (a.accumulate) {  // a later input group of a wide stripe: generic K, 16 B per lane (shape 1)
+    record_apply(bw_apply_form(R, 0, 1, true, 4, false, true));
     return launch_tiled(&k_gf8_bytewise<R, 0, 1, true, 4, false, true>, grid, st, a);
   }
   switch (shape) {
@@ -1281,28 +1294,46 @@ hipError_t dispatch_bytewise(const ApplyArgs &a, hipStream_t st, int grid, int s
 template <int R>
 hipError_t dispatch_bytewise_magic(const ApplyArgs &a, hipStream_t st, int grid) {
   switch (a.K) {
-#define LSEC_BWM_K(KK) \
-  case KK: return launch_tiled(&k_gf8_bytewise<R, KK, bytewise_magic_it(KK), true, 4, true>, grid, st, a);
+#define LSEC_BWM_K(KK)                                                           \
+  case KK:                                                                      \
+    record_apply(bw_apply_form(R, KK, bytewise_magic_it(KK), true, 4, true)); \
+    return launch_tiled(&k_gf8_bytewise<R, KK, bytewise_magic_it(KK), true, 4, true>, grid, st, a);
     LSEC_FIXED_K(LSEC_BWM_K)
 #undef LSEC_BWM_K
     default:
-      if (bytewise_magic_it(a.K) == 1) return launch_tiled(&k_gf8_bytewise<R, 0, 1, true, 4, true>, grid, st, a);
+      if (bytewise_magic_it(a.K) == 1) {
+        record_apply(bw_apply_form(R, 0, 1, true, 4, true));
+        return launch_tiled(&k_gf8_bytewise<R, 0, 1, true, 4, true>, grid, st, a);
+      }
+      record_apply(bw_apply_form(R, 0, 2, true, 4, true));
       return launch_tiled(&k_gf8_bytewise<R, 0, 2, true, 4, true>, grid, st, a);
   }
+}
+
+// the records of the other apply kernels: k_gf8_bitsliced<R, 0, DW, MG, ACC>, k_bitmatrix<R, W> (per_w) or
+// k_bitmatrix_any<R>, k_gfw_transposed<R, W, ACC> (transposed) or k_gfw_wordwise<R, W, ACC>, k_gfw_bitsliced<R, W, ACC>
+constexpr ApplyForm bs_apply_form(int R, int DW, bool MG = false, bool ACC = false) {
+  return ApplyForm{2, R, 0, 0, 0, 0, DW, 8, ACC ? 1 : 0, MG ? 1 : 0, 0, -1};
+}
+constexpr ApplyForm bm_apply_form(int R, int w, bool per_w, bool ACC) { return ApplyForm{3, R, 0, 0, 0, 0, 0, w, ACC ? 1 : 0, 0, per_w ? 1 : 0, -1}; }
+constexpr ApplyForm gfw_apply_form(int kind, int R, int w, bool transposed, bool ACC) {
+  return ApplyForm{kind, R, 0, 0, 0, 0, 0, w, ACC ? 1 : 0, 0, transposed ? 1 : 0, -1};
 }
 
 template <int R>
 hipError_t dispatch_bitsliced(const ApplyArgs &a, hipStream_t st, int grid, int dw) {
   if (a.magic_acc) {  // encode + stripe magic, one lane dword wide
+    record_apply(bs_apply_form(R, 1, true, false));
     return launch_tiled(&k_gf8_bitsliced<R, 0, 1, true>, grid, st, a);
   }
   if (a.accumulate) {  // a later input group of a wide stripe, one lane dword wide
+    record_apply(bs_apply_form(R, 1, false, true));
     return launch_tiled(&k_gf8_bitsliced<R, 0, 1, false, true>, grid, st, a);
   }
   switch (dw) {
-    case 4: return launch_tiled(&k_gf8_bitsliced<R, 0, 4>, grid, st, a);
-    case 2: return launch_tiled(&k_gf8_bitsliced<R, 0, 2>, grid, st, a);
-    default: return launch_tiled(&k_gf8_bitsliced<R, 0, 1>, grid, st, a);
+    case 4: record_apply(bs_apply_form(R, 4)); return launch_tiled(&k_gf8_bitsliced<R, 0, 4>, grid, st, a);
+    case 2: record_apply(bs_apply_form(R, 2)); return launch_tiled(&k_gf8_bitsliced<R, 0, 2>, grid, st, a);
+    default: record_apply(bs_apply_form(R, 1)); return launch_tiled(&k_gf8_bitsliced<R, 0, 1>, grid, st, a);
   }
 }
 
@@ -1310,14 +1341,19 @@ template <int R>
 hipError_t dispatch_bitmatrix(const ApplyArgs &a, hipStream_t st, int grid) {
   if constexpr (R <= 2) {
     if (a.accumulate) {  // wide stripes (k > 64) only occur at w > 64: the any-w kernel
+      record_apply(bm_apply_form(R, a.w, false, true));
       return launch_kernel(&k_bitmatrix_any<R>, dim3(grid), dim3(kBlock), st, a);
     }
     switch (a.w) {
-#define LSEC_BM_W(WW) \
-  case WW: return launch_kernel(&k_bitmatrix<R, WW>, dim3(grid), dim3(kBlock), st, a);
+#define LSEC_BM_W(WW)                                 \
+  case WW:                                            \
+    record_apply(bm_apply_form(R, WW, true, false)); \
+    return launch_kernel(&k_bitmatrix<R, WW>, dim3(grid), dim3(kBlock), st, a);
       LSEC_BITMATRIX_W(LSEC_BM_W)
 #undef LSEC_BM_W
-      default: return launch_kernel(&k_bitmatrix_any<R>, dim3(grid), dim3(kBlock), st, a);
+      default:
+        record_apply(bm_apply_form(R, a.w, false, false));
+        return launch_kernel(&k_bitmatrix_any<R>, dim3(grid), dim3(kBlock), st, a);
     }
   } else {
     return hipErrorInvalidValue;
@@ -1327,10 +1363,10 @@ hipError_t dispatch_bitmatrix(const ApplyArgs &a, hipStream_t st, int grid) {
 template <int R>
 hipError_t dispatch_wordwise(const ApplyArgs &a, hipStream_t st, int grid) {
   switch (a.w * 2 + (a.accumulate ? 1 : 0)) {
-    case 32: return launch_kernel(&k_gfw_wordwise<R, 16>, dim3(grid), dim3(kBlock), st, a);
-    case 33: return launch_kernel(&k_gfw_wordwise<R, 16, true>, dim3(grid), dim3(kBlock), st, a);
-    case 64: return launch_kernel(&k_gfw_wordwise<R, 32>, dim3(grid), dim3(kBlock), st, a);
-    case 65: return launch_kernel(&k_gfw_wordwise<R, 32, true>, dim3(grid), dim3(kBlock), st, a);
+    case 32: record_apply(gfw_apply_form(4, R, 16, false, false)); return launch_kernel(&k_gfw_wordwise<R, 16>, dim3(grid), dim3(kBlock), st, a);
+    case 33: record_apply(gfw_apply_form(4, R, 16, false, true)); return launch_kernel(&k_gfw_wordwise<R, 16, true>, dim3(grid), dim3(kBlock), st, a);
+    case 64: record_apply(gfw_apply_form(4, R, 32, false, false)); return launch_kernel(&k_gfw_wordwise<R, 32>, dim3(grid), dim3(kBlock), st, a);
+    case 65: record_apply(gfw_apply_form(4, R, 32, false, true)); return launch_kernel(&k_gfw_wordwise<R, 32, true>, dim3(grid), dim3(kBlock), st, a);
     default: return hipErrorInvalidValue;
   }
 }
@@ -1339,12 +1375,20 @@ hipError_t dispatch_wordwise(const ApplyArgs &a, hipStream_t st, int grid) {
 template <int R>
 hipError_t dispatch_gfw_transposed(const ApplyArgs &a, hipStream_t st, int grid) {
   if (a.w == 16) {
-    if (a.accumulate) return launch_kernel(&k_gfw_transposed<R, 16, true>, dim3(grid), dim3(kBlock), st, a);
-    else return launch_kernel(&k_gfw_transposed<R, 16>, dim3(grid), dim3(kBlock), st, a);
+    if (a.accumulate) {
+      record_apply(gfw_apply_form(4, R, 16, true, true));
+      return launch_kernel(&k_gfw_transposed<R, 16, true>, dim3(grid), dim3(kBlock), st, a);
+    }
+    record_apply(gfw_apply_form(4, R, 16, true, false));
+    return launch_kernel(&k_gfw_transposed<R, 16>, dim3(grid), dim3(kBlock), st, a);
   } else if constexpr (R <= 4) {
     if (a.w != 32) return hipErrorInvalidValue;
-    if (a.accumulate) return launch_kernel(&k_gfw_transposed<R, 32, true>, dim3(grid), dim3(kBlock), st, a);
-    else return launch_kernel(&k_gfw_transposed<R, 32>, dim3(grid), dim3(kBlock), st, a);
+    if (a.accumulate) {
+      record_apply(gfw_apply_form(4, R, 32, true, true));
+      return launch_kernel(&k_gfw_transposed<R, 32, true>, dim3(grid), dim3(kBlock), st, a);
+    }
+    record_apply(gfw_apply_form(4, R, 32, true, false));
+    return launch_kernel(&k_gfw_transposed<R, 32>, dim3(grid), dim3(kBlock), st, a);
   } else {
     return hipErrorInvalidValue;
   }
@@ -1353,12 +1397,20 @@ hipError_t dispatch_gfw_transposed(const ApplyArgs &a, hipStream_t st, int grid)
 template <int R>
 hipError_t dispatch_gfw_bitsliced(const ApplyArgs &a, hipStream_t st, int grid) {
   if (a.w == 16) {
-    if (a.accumulate) return launch_kernel(&k_gfw_bitsliced<R, 16, true>, dim3(grid), dim3(kBlock), st, a);
-    else return launch_kernel(&k_gfw_bitsliced<R, 16>, dim3(grid), dim3(kBlock), st, a);
+    if (a.accumulate) {
+      record_apply(gfw_apply_form(5, R, 16, false, true));
+      return launch_kernel(&k_gfw_bitsliced<R, 16, true>, dim3(grid), dim3(kBlock), st, a);
+    }
+    record_apply(gfw_apply_form(5, R, 16, false, false));
+    return launch_kernel(&k_gfw_bitsliced<R, 16>, dim3(grid), dim3(kBlock), st, a);
   } else if constexpr (R <= 4) {
     if (a.w != 32) return hipErrorInvalidValue;
-    if (a.accumulate) return launch_kernel(&k_gfw_bitsliced<R, 32, true>, dim3(grid), dim3(kBlock), st, a);
-    else return launch_kernel(&k_gfw_bitsliced<R, 32>, dim3(grid), dim3(kBlock), st, a);
+    if (a.accumulate) {
+      record_apply(gfw_apply_form(5, R, 32, false, true));
+      return launch_kernel(&k_gfw_bitsliced<R, 32, true>, dim3(grid), dim3(kBlock), st, a);
+    }
+    record_apply(gfw_apply_form(5, R, 32, false, false));
+    return launch_kernel(&k_gfw_bitsliced<R, 32>, dim3(grid), dim3(kBlock), st, a);
   } else {
     return hipErrorInvalidValue;
   }

@@ -301,11 +301,8 @@ void host_cells(const lsec::gf8::Mat &mat, int rows, int cols, std::vector<CoefC
   cells.resize(static_cast<size_t>(rows) * cols);
   for (int i = 0; i < rows * cols; ++i) lsec::make_cell(mat[i], cells[i]);
   // flag plain-XOR rows (any launch whose first row is one takes the XOR-row kernel path)
-  for (int r = 0; r < rows; ++r) {
-    bool ones = true;
-    for (int j = 0; j < cols && ones; ++j) ones = mat[static_cast<size_t>(r) * cols + j] == 1;
-    if (ones) cells[static_cast<size_t>(r) * cols].pad |= lsec::kCellXorRow;
-  }
+  for (int r = 0; r < rows; ++r)
+    if (row_all_ones(mat.data() + static_cast<size_t>(r) * cols, cols)) cells[static_cast<size_t>(r) * cols].pad |= lsec::kCellXorRow;
 }
 
 int upload(const void *host, size_t nbytes, const char *what, void **out) {
@@ -436,6 +433,7 @@ int encode_job(PlanExt *e, CodingJob *job) {
   job->out_ids.resize(job->R);
   for (int j = 0; j < k; ++j) job->in_ids[j] = j;
   for (int r = 0; r < job->R; ++r) job->out_ids[r] = k + r;
+  job->gf8_rows = uses_u32_image(job->kind) ? nullptr : e->impl->coding.data();
   return 0;
 }
 
@@ -559,6 +557,7 @@ int decode_job(PlanExt *e, const std::vector<int> &ids, CodingJob *job) {
   job->R = static_cast<int>(ent->dp.erased.size());
   job->in_ids = ent->dp.survivors;
   job->out_ids = ent->dp.erased;
+  job->gf8_rows = uses_u32_image(job->kind) ? nullptr : ent->dp.rows.data();
   return 0;
 }
 
@@ -609,6 +608,42 @@ long long launch_stripes(long long C, bool split, long long tile_bytes) {
   return per;
 }
 
+// What enqueue_apply hands launch_bitsliced as its preference: Cauchy w = 8 under the automatic policy takes the
+// shape's dwords per lane (cauchy8_bitsliced_dw; 0 = the network, and one dword where none is ready)
+int apply_dw_pref(int kind, int K, int R, int w, long long size, int bs_variant) {
+  return kind == KBITSLICED && w == 8 && bs_variant == 0 ? cauchy8_bitsliced_dw(K, R, size) : 0;
+}
+
+// The forms one unsplit K x R call launches from the table kernels (no network ready, or none wanted), in order:
+// lsec_encode_magic_dev's one fused launch where it fuses (`magic`), else enqueue_apply's launches -- for
+// lsec_encode_magic_dev then followed by the magic pass, which is not of this family.  row_ones[r]: row r of the
+// matrix is all ones (null: none is).  It walks for_apply_launches and asks predict_apply_launch, as the launches do.
+int predict_apply(int kind, int K, int R, int w, int packet, long long size, bool magic, int bw_variant, int bs_variant,
+                  const unsigned char *row_ones, std::vector<lsec::ApplyForm> &out) {
+  out.clear();
+  const auto one = [&](int kg, int rn, bool acc, bool mg, int dw_pref, bool ones) {
+    lsec::ApplyForm f;
+    if (!lsec::predict_apply_launch(kind, kg, rn, w, packet, acc, mg, dw_pref, bw_variant, bs_variant, ones, &f))
+      return fail("no kernel of kind %d for K=%d R=%d w=%d packet=%d", kind, kg, rn, w, packet);
+    out.push_back(f);
+    return 0;
+  };
+  if (kind < KBYTEWISE || kind > KBITSLICEDW || K < 1 || R < 1) return fail("kind %d K=%d R=%d", kind, K, R);
+  if (magic && encode_magic_fuses(kind, K, R)) return one(K, R, false, true, 0, row_ones && row_ones[0]);
+  const int dw_pref = apply_dw_pref(kind, K, R, w, size, bs_variant);
+  return for_apply_launches(kind, K, R, w, [&](int k0, int kg, int r0, int rn) {
+    return one(kg, rn, k0 > 0, false, dw_pref, k0 == 0 && row_ones && row_ones[r0]);
+  });
+}
+
+// lsec_test_hold_networks: while set, enqueue_apply takes no compiled network for ready, as on a plan's first calls
+std::atomic<int> g_hold_networks{0};
+bool networks_held() { return g_hold_networks.load(std::memory_order_relaxed) != 0; }
+
+bool encode_magic_fuses(int kind, int k, int m) {
+  return (kind == KBYTEWISE || kind == KBITSLICED) && m <= 8 && k <= lsec::kMaxK && k + m <= lsec::kMaxMagicShards;
+}
+
 // Enqueue out[r] = rows[r] . in  for every stripe, splitting R into launches of <= 8 rows
 // (<= 2 for the bitmatrix kernel) and K into groups of <= lsec::kMaxK inputs.  `image` is the
 // CoefCell[R][K] matrix image, the uint32 row masks [((r*w+l)*K + j)*NW + q] (KBITMATRIX) or the
@@ -616,14 +651,14 @@ long long launch_stripes(long long C, bool split, long long tile_bytes) {
 thread_local int tl_apply_path = 0;  // lsec_test_apply_path: what this thread's last enqueue_apply launched
 
 int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in, const ShardRef *out,
-                  int nstripes, long long size, int packet, hipStream_t st, int w) {
+                  int nstripes, long long size, int packet, hipStream_t st, int w, const uint8_t *gf8_rows) {
   tl_apply_path = 0;
   const bool net = kind == KBYTEWISE   ? lsec::bytewise_variant() == 0 && lsec::jit::wants_xornet(R, K)
                    : kind == KWORDWISE ? lsec::bitsliced_variant() == 0 && lsec::jit::wants_gfw_net(R, K, w)
                                        : false;
   ShardRef tin[lsec::kMaxK], tout[lsec::kMaxR];  // a w = 16 / 32 network's ragged tail, below
   if (net) {
-    if (hipFunction_t fn = lsec::jit::ready(image, R, K)) {  // the matrix's compiled XOR network
+    if (hipFunction_t fn = networks_held() ? nullptr : lsec::jit::ready(image, R, K)) {  // the matrix's compiled XOR network
       // w = 16 / 32 networks take whole tiles only: the tail columns go to the generic kernel
       const long long whole = kind == KWORDWISE ? size / lsec::jit::gfw_tile(w, R) * lsec::jit::gfw_tile(w, R) : size;
       ShardRef bi[lsec::jit::kMaxCols], bo[lsec::jit::kMaxRows];
@@ -645,54 +680,49 @@ int enqueue_apply(int kind, const void *image, int K, int R, const ShardRef *in,
     }
   }
   // Cauchy w = 8: the shape's kernel (cauchy8_bitsliced_dw; 0 = the network)
-  const int c8_dw = kind == KBITSLICED && w == 8 && lsec::bitsliced_variant() == 0 ? cauchy8_bitsliced_dw(K, R, size) : 0;
+  const int c8_dw = apply_dw_pref(kind, K, R, w, size, lsec::bitsliced_variant());
   if ((kind == KBITMATRIX || kind == KBITSLICEDW || kind == KBITSLICED) && lsec::bitsliced_variant() == 0 && c8_dw == 0 &&
       lsec::jit::wants_pktnet(R, K, w) &&
       lsec::jit::pkt_aligned(in, K, out, R, w, packet))
-    if (hipFunction_t fn = lsec::jit::ready(image, R, K)) {  // the bitmatrix's compiled packet network
+    if (hipFunction_t fn = networks_held() ? nullptr : lsec::jit::ready(image, R, K)) {  // the bitmatrix's compiled packet network
       const hipError_t err = lsec::jit::launch_pkt(fn, R, K, in, out, nstripes, size, packet, w, st);
       if (err != hipSuccess) return fail("packet network launch failed: %s", hipGetErrorString(err));
       tl_apply_path |= 2;
       return 0;
     }
-  const int rmax = kind == KBITMATRIX ? 2 : ((kind == KBITSLICEDW || kind == KWORDWISE) && w == 32) ? 4 : 8;
   const int rpr = image_rows_per_output(kind, w), unit = image_unit(kind, w);
   // input groups of at most kMaxK (grouped image layout); groups after the first accumulate
-  for (int k0 = 0; k0 < K; k0 += lsec::kMaxK) {
-    const int kg = std::min(lsec::kMaxK, K - k0);
+  return for_apply_launches(kind, K, R, w, [&](int k0, int kg, int r0, int rn) {
     const size_t group_base = static_cast<size_t>(k0) * R * rpr * unit;  // earlier groups: kMaxK inputs each
-    for (int r0 = 0; r0 < R; r0 += rmax) {
-      lsec::ApplyArgs a;
-      std::memset(&a, 0, sizeof(a));
-      a.K = kg;
-      a.R = std::min(rmax, R - r0);
-      a.accumulate = k0 > 0;
-      const size_t at = group_base + static_cast<size_t>(r0) * rpr * kg * unit;
-      if (uses_u32_image(kind)) {  // w words per (row, input), or mask words per (bit-row, input)
-        a.masks = static_cast<const uint32_t *>(image) + at;
-        a.w = w;
-      } else {
-        a.cells = static_cast<const CoefCell *>(image) + at;
-      }
-      a.size = size;
-      a.packet = packet;
-      if (for_launches(nstripes, launch_stripes(size, false), [&](long long s0, int n) {
-            a.nstripes = n;
-            for (int j = 0; j < kg; ++j) a.in[j] = shard_from(in[k0 + j], s0);
-            for (int r = 0; r < a.R; ++r) a.out[r] = shard_from(out[r0 + r], s0);
-            const hipError_t err = kind == KBYTEWISE     ? lsec::launch_bytewise(a, st)
-                                   : kind == KBITMATRIX  ? lsec::launch_bitmatrix(a, st)
-                                   : kind == KWORDWISE   ? lsec::launch_wordwise(a, st)
-                                   : kind == KBITSLICEDW ? lsec::launch_gfw_bitsliced(a, st)
-                                                         : lsec::launch_bitsliced(a, st, 0, c8_dw);
-            if (err != hipSuccess) return fail("kernel launch failed: %s", hipGetErrorString(err));
-            tl_apply_path |= 4;
-            return 0;
-          }))
-        return -1;
+    lsec::ApplyArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.K = kg;
+    a.R = rn;
+    a.accumulate = k0 > 0;
+    const size_t at = group_base + static_cast<size_t>(r0) * rpr * kg * unit;
+    if (uses_u32_image(kind)) {  // w words per (row, input), or mask words per (bit-row, input)
+      a.masks = static_cast<const uint32_t *>(image) + at;
+      a.w = w;
+    } else {
+      a.cells = static_cast<const CoefCell *>(image) + at;
+      lsec::apply_record_first_row(apply_first_row_ones(gf8_rows, K, k0, r0));  // (lsec_test_apply_record)
     }
-  }
-  return 0;
+    a.size = size;
+    a.packet = packet;
+    return for_launches(nstripes, launch_stripes(size, false), [&](long long s0, int n) {
+      a.nstripes = n;
+      for (int j = 0; j < kg; ++j) a.in[j] = shard_from(in[k0 + j], s0);
+      for (int r = 0; r < a.R; ++r) a.out[r] = shard_from(out[r0 + r], s0);
+      const hipError_t err = kind == KBYTEWISE     ? lsec::launch_bytewise(a, st)
+                             : kind == KBITMATRIX  ? lsec::launch_bitmatrix(a, st)
+                             : kind == KWORDWISE   ? lsec::launch_wordwise(a, st)
+                             : kind == KBITSLICEDW ? lsec::launch_gfw_bitsliced(a, st)
+                                                   : lsec::launch_bitsliced(a, st, 0, c8_dw);
+      if (err != hipSuccess) return fail("kernel launch failed: %s", hipGetErrorString(err));
+      tl_apply_path |= 4;
+      return 0;
+    });
+  });
 }
 
 // ---------------------------------------------------------------- device-resident core
@@ -702,7 +732,7 @@ int apply_job(const PlanExt *e, const CodingJob &job, const lsec_shard_t *sh, in
   const int K = static_cast<int>(job.in_ids.size());
   for (int j = 0; j < K; ++j) in[j] = shard_from(sh[job.in_ids[j]], 0);
   for (int r = 0; r < job.R; ++r) out[r] = shard_from(sh[job.out_ids[r]], 0);
-  return enqueue_apply(job.kind, job.image, K, job.R, in, out, nstripes, C, e->pub.packet_size, st, e->pub.w);
+  return enqueue_apply(job.kind, job.image, K, job.R, in, out, nstripes, C, e->pub.packet_size, st, e->pub.w, job.gf8_rows);
 }
 
 int encode_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, hipStream_t st) {
@@ -2432,6 +2462,98 @@ int lsec_test_pattern_unused(lio_erasure_plan_t *plan, const int *patterns, int 
 
 // Test hook, not in include/ (no GPU): the K that have fixed-K forms (LSEC_FIXED_K), ascending
 int lsec_test_fixed_k(int *out, int max) { return lsec::fixed_k_list(out, max); }
+
+namespace {
+int put_apply_forms(const lsec::ApplyForm *f, int n, int *forms, int max_forms) {
+  for (int i = 0; forms && i < n && i < max_forms; ++i) {
+    const int v[lsec::kApplyFormInts] = {f[i].kind, f[i].R, f[i].KC, f[i].IT, f[i].VW, f[i].BF, f[i].DW, f[i].w, f[i].acc, f[i].magic, f[i].sub, f[i].loop};
+    std::memcpy(forms + lsec::kApplyFormInts * i, v, sizeof(v));
+  }
+  return n;
+}
+}  // namespace
+
+// Test hook, not in include/: the kernels (ec_kernels.h, ApplyForm) that the calling thread's last lsec_encode_dev,
+// lsec_decode_dev or lsec_encode_magic_dev launched through the table dispatch, in order: input groups x row
+// launches x stripe ranges.  A compiled network's launch is not among them (lsec_test_apply_path tells), nor is
+// the magic pass of a two-pass lsec_encode_magic_dev.  forms: 12 ints each (kind, R, KC, IT, VW, BF, DW, w,
+// accumulate, fused magic, sub, loop).  Returns the number of launches; at most min(that, max_forms, 64) are written.
+int lsec_test_apply_record(int *forms, int max_forms) {
+  lsec::ApplyForm rec[lsec::kApplyRecordMax];
+  const int n = lsec::apply_record(rec, lsec::kApplyRecordMax);
+  put_apply_forms(rec, std::min(n, lsec::kApplyRecordMax), forms, max_forms);
+  return n;
+}
+
+// Test hook, not in include/ (no GPU): the forms, as lsec_test_apply_record lists them, that one unsplit call of a
+// K x R matrix of kernel `kind` (1-5) launches at word size w, that packet and chunk size under the two variant
+// values of lsec_set_kernel_variant, while no network is ready; fused_magic: lsec_encode_magic_dev.  row_ones:
+// R bytes, nonzero where the row is all ones (NULL: none).  It asks the functions the calls themselves go
+// through (predict_apply).  Returns the number of launches (at most max_forms are written), or -1 with a message.
+int lsec_test_predict_apply(int kind, int K, int R, int w, int packet, long long block_size, int fused_magic, int bw_variant,
+                            int bs_variant, const unsigned char *row_ones, int *forms, int max_forms) {
+  std::vector<lsec::ApplyForm> f;
+  if (predict_apply(kind, K, R, w, packet, block_size, fused_magic != 0, bw_variant, bs_variant, row_ones, f)) return -1;
+  return put_apply_forms(f.data(), static_cast<int>(f.size()), forms, max_forms);
+}
+
+// Test hook, not in include/ (no GPU): the form one launch of K inputs and R rows takes (lsec::predict_apply_launch),
+// unsplit: lsec_test_predict_apply cuts a call into the launches enqueue_apply makes, so a kernel that is compiled
+// for more rows than a launch ever gets is named by this hook alone.  0, or -1 where the launch would be refused.
+int lsec_test_predict_apply_launch(int kind, int K, int R, int w, int packet, int accumulate, int fused_magic, int dw_pref,
+                                   int bw_variant, int bs_variant, int first_row_ones, int *form) {
+  if (!form) return fail("lsec_test_predict_apply_launch: NULL output");
+  lsec::ApplyForm f;
+  if (!lsec::predict_apply_launch(kind, K, R, w, packet, accumulate != 0, fused_magic != 0, dw_pref, bw_variant, bs_variant,
+                                  first_row_ones != 0, &f))
+    return fail("lsec_test_predict_apply_launch: no kernel of kind %d for K=%d R=%d w=%d packet=%d", kind, K, R, w, packet);
+  put_apply_forms(&f, 1, form, 1);
+  return 0;
+}
+
+// Test hook, not in include/ (no GPU): lsec_test_predict_apply for a plan's own matrices under the variant
+// values in force -- the encode (erasures NULL; fused_magic: lsec_encode_magic_dev) or the decode of a
+// -1 terminated erasure list, whose kernel kind, row count and rows of ones come from the host side of the
+// plan's decode cache.  0 launches where the call has nothing to do.
+int lsec_test_predict_apply_plan(lio_erasure_plan_t *plan, const int *erasures, long long block_size, int fused_magic,
+                                 int *forms, int max_forms) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (ensure_coding(e)) return -1;
+  const int k = plan->data_strips;
+  int kind = kernel_kind(plan->method, plan->w), R = 0;
+  const uint8_t *rows = nullptr;
+  if (!erasures) {
+    R = encode_rows(e);
+    if (!uses_u32_image(kind)) rows = e->impl->coding.data();
+  } else {
+    std::vector<int> ids;
+    const int pr = parse_erasures(plan, erasures, ids);
+    if (pr < 0) return -1;
+    if (pr == 1 || (plan->method == RAID4 && ids[0] >= k)) return 0;
+    DecodeEntry *ent = nullptr;
+    {
+      std::lock_guard<std::mutex> lk(e->impl->mu);
+      if (decode_host_locked(e, ids, &ent)) return -1;
+    }
+    const bool field = kind == KBITSLICED || kind == KWORDWISE || kind == KBITSLICEDW;
+    if (field && ent->xor_only) kind = KBYTEWISE;  // (decode_job)
+    R = static_cast<int>(ent->dp.erased.size());
+    if (!uses_u32_image(kind)) rows = ent->dp.rows.data();
+  }
+  std::vector<unsigned char> ones(R, 0);
+  for (int r = 0; rows && r < R; ++r) ones[r] = apply_first_row_ones(rows, k, 0, r) ? 1 : 0;
+  std::vector<lsec::ApplyForm> f;
+  if (predict_apply(kind, k, R, plan->w, plan->packet_size, block_size, fused_magic != 0, lsec::bytewise_variant(),
+                    lsec::bitsliced_variant(), ones.data(), f))
+    return -1;
+  return put_apply_forms(f.data(), static_cast<int>(f.size()), forms, max_forms);
+}
+
+// Test hook, not in include/: while `on` is nonzero no compiled network counts as ready, so every call runs the
+// table kernels under the automatic policy, as a plan's first calls do before its network is compiled.  It reads
+// an atomic per call: no compile timing and no environment variable is involved.
+void lsec_test_hold_networks(int on) { g_hold_networks.store(on ? 1 : 0, std::memory_order_relaxed); }
 
 // Test hook, not in include/: 1 = Cauchy at w = 8 on its compiled packet network wherever one exists,
 // 0 = by shape (cauchy8_bitsliced_dw, the default).

@@ -576,6 +576,7 @@ int et_decode_stripes(lio_erasure_plan_t *plan, char **ptrs, int nstripes, int b
 
 int lsec_encode_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
                     void *stream) {
+  lsec::apply_record_reset();  // (lsec_test_apply_record)
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
   if (!shards) return fail("shards is NULL");
@@ -585,6 +586,7 @@ int lsec_encode_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int ns
 
 int lsec_decode_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
                     const int *erasures, void *stream) {
+  lsec::apply_record_reset();  // (lsec_test_apply_record)
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
   if (!shards) return fail("shards is NULL");
@@ -808,6 +810,7 @@ int lsec_encode_magic_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, 
                           void *magic, void *stream) {
   PlanExt *e = ext_of(plan);
   if (!e) return fail("not an lstore_ec plan");
+  lsec::apply_record_reset();  // (lsec_test_apply_record)
   if (!shards || !magic) return fail("shards / magic is NULL");
   if (check_shards(plan, shards, nstripes)) return -1;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -818,8 +821,7 @@ int lsec_encode_magic_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, 
   // RS 12+4 5.9 ms fused vs 5.7 + 5.2 ms as two passes, Cauchy 6+3 5.9 vs 5.9 + 6.2 ms
   // (profiles/r01_v12_kbench_fused_magic.txt).
   const int kind = kernel_kind(plan->method, plan->w);
-  const bool fuse = kind == KBYTEWISE || kind == KBITSLICED;
-  if (fuse && m <= 8 && k <= lsec::kMaxK && !check_geometry(plan, block_size) && k + m <= lsec::kMaxMagicShards) {
+  if (encode_magic_fuses(kind, k, m) && !check_geometry(plan, block_size)) {
     if (nstripes <= 0 || block_size == 0) return 0;
     CodingJob job;
     if (encode_job(e, &job)) return -1;
@@ -834,6 +836,7 @@ int lsec_encode_magic_dev(lio_erasure_plan_t *plan, const lsec_shard_t *shards, 
     a.R = m;
     a.size = block_size;
     a.packet = plan->packet_size;
+    lsec::apply_record_first_row(apply_first_row_ones(job.gf8_rows, k, 0, 0));  // (lsec_test_apply_record)
     if (for_launches(nstripes, launch_stripes(block_size, false, 8192), [&](long long s0, int n) {
           a.nstripes = n;
           a.magic_acc = acc + 2ull * s0;

@@ -198,6 +198,13 @@ def lib():
     L.lsec_test_launch_record.argtypes = [C.POINTER(C.c_int), C.c_int]
     L.lsec_test_predict_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
     L.lsec_test_fixed_k.argtypes = [C.POINTER(C.c_int), C.c_int]
+    L.lsec_test_apply_record.argtypes = [C.POINTER(C.c_int), C.c_int]
+    L.lsec_test_predict_apply.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                          C.c_char_p, C.POINTER(C.c_int), C.c_int]
+    L.lsec_test_predict_apply_launch.argtypes = [C.c_int] * 11 + [C.POINTER(C.c_int)]
+    L.lsec_test_predict_apply_plan.argtypes = [P, C.POINTER(C.c_int), C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_int]
+    L.lsec_test_hold_networks.argtypes = [C.c_int]
+    L.lsec_test_hold_networks.restype = None
     L.lsec_prepare_decode.argtypes = [P, C.POINTER(C.c_int)]
     L.lsec_prepare_encode.argtypes = [P]
     L.lsec_plan_jit.argtypes = [P, C.POINTER(C.c_int)]
@@ -1084,6 +1091,75 @@ def predict_forms(call: str, plan_kernel: int, k: int, rows: int, packet: int = 
     if repair:
         forms.append(predict_form({"loc": "pat", "locrot": "patrot"}[call], plan_kernel, k, 1, packet, block_size))
     return forms
+
+
+# The apply family -- what encode_dev, decode_dev and encode_magic_dev launch -- has a record of its own layout
+# behind the fifteen families above (those tuples and Form stay as they are).
+ApplyForm = collections.namedtuple("ApplyForm", "kind R KC IT VW BF DW w acc magic sub loop")
+ApplyForm.__doc__ = """One separately compiled kernel behind encode_dev / decode_dev / encode_magic_dev: kind (1 bytewise, 2
+bit-sliced, 3 bitmatrix, 4 GF(2^w) wordwise or transposed, 5 GF(2^w) bit-sliced), R rows; bytewise: KC (0 = K at run
+time), IT steps of VW dwords per lane, BF branch-free; bit-sliced: DW dwords per lane; kinds 3-5: w; acc: the
+accumulate instantiation of a later input group; magic: the fused stripe-magic instantiation; sub: kind 3, 1 the
+kernel of its word size and 0 the any-w kernel; kind 4, 1 the transposed kernel and 0 the mask-per-bit one; loop:
+bytewise kernels that hold two whole tile loops, 1 the plain-XOR first row's and 0 the other's, -1 where the kernel
+has one loop."""
+APPLY_RECORD_MAX = 64
+
+
+def _apply_forms(buf, n: int) -> list:
+    return [ApplyForm(*(int(x) for x in buf[12 * i:12 * i + 12])) for i in range(n)]
+
+
+def apply_record() -> list:
+    """Test hook: the ApplyForms this thread's last encode_dev / decode_dev / encode_magic_dev call launched from the
+    table dispatch, in order: input groups x row launches x stripe ranges (a compiled network's launch is not among
+    them, nor the magic pass of a two-pass encode_magic_dev)."""
+    buf = (C.c_int * (12 * APPLY_RECORD_MAX))()
+    n = lib().lsec_test_apply_record(buf, APPLY_RECORD_MAX)
+    if n > APPLY_RECORD_MAX:
+        raise ErasureError(f"lsec_test_apply_record: {n} launches, {APPLY_RECORD_MAX} are kept")
+    return _apply_forms(buf, n)
+
+
+def predict_apply(kind: int, k: int, rows: int, w: int = 8, packet: int = 0, block_size: int = 0, magic: bool = False,
+                  variants=(0, 0), row_ones=None) -> list:
+    """Test hook (no GPU): what apply_record() holds after one unsplit call of a k x rows matrix of kernel `kind` while
+    no network is ready, under the two kernel-variant values; magic: encode_magic_dev; row_ones: per row, whether it
+    is all ones.  Asked of the functions the calls themselves go through."""
+    buf = (C.c_int * (12 * 256))()
+    ones = bytes(1 if x else 0 for x in row_ones) if row_ones is not None else None
+    if ones is not None and len(ones) != rows:
+        raise ValueError("row_ones needs one entry per row")
+    n = _check_nonneg(lib().lsec_test_predict_apply(kind, k, rows, w, packet, block_size, 1 if magic else 0, variants[0],
+                                                    variants[1], ones, buf, 256), "lsec_test_predict_apply")
+    return _apply_forms(buf, n)
+
+
+def predict_apply_launch(kind: int, k: int, rows: int, w: int = 8, packet: int = 0, acc: bool = False, magic: bool = False,
+                         dw_pref: int = 0, variants=(0, 0), first_row_ones: bool = False) -> ApplyForm:
+    """Test hook (no GPU): the ApplyForm of one launch of k inputs and `rows` rows, unsplit: predict_apply cuts a call
+    into the launches the engine makes, so a kernel compiled for more rows than a launch ever gets is named here alone."""
+    out = (C.c_int * 12)()
+    _check(lib().lsec_test_predict_apply_launch(kind, k, rows, w, packet, 1 if acc else 0, 1 if magic else 0, dw_pref,
+                                                variants[0], variants[1], 1 if first_row_ones else 0, out),
+           "lsec_test_predict_apply_launch")
+    return ApplyForm(*(int(x) for x in out))
+
+
+def predict_apply_plan(plan: "Plan", erasures=None, block_size: int = 0, magic: bool = False) -> list:
+    """Test hook (no GPU): predict_apply for the plan's own matrices under the kernel variants in force: its encode
+    (erasures None; magic: encode_magic_dev) or the decode of `erasures`."""
+    buf = (C.c_int * (12 * 256))()
+    era = _erasure_array(erasures) if erasures is not None else None
+    n = _check_nonneg(lib().lsec_test_predict_apply_plan(plan._p, era, block_size, 1 if magic else 0, buf, 256),
+                      "lsec_test_predict_apply_plan")
+    return _apply_forms(buf, n)
+
+
+def hold_networks(on: bool = True) -> None:
+    """Test hook: while on, no compiled network counts as ready, so encode_dev / decode_dev run the table kernels
+    under the automatic policy, as on a plan's first calls."""
+    lib().lsec_test_hold_networks(1 if on else 0)
 
 
 def fixed_k() -> tuple:
