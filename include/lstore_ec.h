@@ -222,6 +222,93 @@ int lsec_decode_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *
                                   void *magic, const void *expect, unsigned char *bad,
                                   unsigned int *bad_count, void *stream);
 
+/* The search for the erasure set that fits the magic, one pass: what LStore does when a stripe's magic
+ * does not match and the first guess fails (jerase_brute_recovery / jerase_brute_recurse,
+ * segment/jerasure.c:271-339).  That routine tries erasure combinations in order and stops at the
+ * first whose rebuilt stripe sums to the quorum magic; it is the reference's only answer to silent
+ * corruption, and it covers what lsec_locate_dev cannot: m = 1 plans (RAID4 among them), more than one
+ * corrupt chunk, and m = 2 stripes where two corrupt chunks imitate a third.  Built from
+ * lsec_decode_magic_dev_patterns, which writes in place, it is a copy of the stripes aside and one
+ * launch and one restore per candidate.  Here every candidate is tried on every selected stripe in one
+ * pass that writes no chunk.  Purely additive too: the version stays 3, a caller detects the calls by
+ * their symbols.
+ *
+ * Candidates
+ * - `patterns` / npatterns: the candidate list, in the format lsec_decode_dev_patterns takes -- erasure
+ *   lists of LOGICAL chunk ids back to back, each ended by -1; an empty list is valid.  The order is
+ *   the caller's.  The reference's order is the empty pattern (or its last successful guess) first,
+ *   then sizes ascending, each size in lexicographic order.
+ * - 1 <= npatterns <= 254 (both sentinels below stay past the table), at most min(m, 8) erasures per
+ *   pattern, nstripes * npatterns < 2^31.
+ * Trial magic
+ * - T(s, p) is the word lsec_decode_magic_dev_patterns would write for stripe s if that stripe's
+ *   pattern were p: zlib's adler32 over the k+m chunks in logical order with the erased chunks
+ *   replaced by what the pattern's survivors rebuild.  A RAID4 pattern that loses only the parity
+ *   rebuilds nothing, and T is the sum of the stored bytes.
+ * Outputs
+ * - `expect`: required with nstripes > 0; device memory, 4*nstripes bytes, no alignment requirement,
+ *   only read: the quorum magics.
+ * - `found`: required with nstripes > 0; nstripes bytes, no alignment requirement.  found[s] is the
+ *   lowest p with T(s, p) == expect[s], LSEC_LOCATE_MANY if no candidate matches, and
+ *   LSEC_LOCATE_CLEAN for a stripe that was not selected.  The call sets every byte itself.  found is
+ *   directly usable as stripe_pattern of lsec_decode_dev_patterns or lsec_decode_magic_dev_patterns
+ *   with the same list: both sentinels are >= npatterns.
+ * - `select`: optional (NULL selects every stripe); nstripes bytes of device memory, only read.  A
+ *   stripe with select[s] == 0 is not searched and none of its chunks is read.  The `bad` output of
+ *   lsec_decode_magic_dev_patterns or lsec_check_magic_dev is a valid select.
+ * - `trial`: optional; 4*nstripes*npatterns bytes, no alignment requirement, pure output.  Word
+ *   s*npatterns + p receives T(s, p), little-endian.  Words of stripes not selected are neither read
+ *   nor written.
+ * - `counts`: optional; two 32-bit words, 4-byte aligned: stripes found, stripes marked
+ *   LSEC_LOCATE_MANY.  The call sets them; it does not add to them.
+ * Without LSEC_SEARCH_REPAIR the shards are only read: no byte of any chunk is written.
+ * With LSEC_SEARCH_REPAIR, behind the search on the same stream, every found stripe is rebuilt in
+ *   place: the bytes are those lsec_decode_dev_patterns writes for that stripe with pattern found[s].
+ *   Stripes not found and stripes not selected are neither read again nor written.  Unknown flag bits
+ *   are refused.
+ * What the call can and cannot tell
+ * - A stripe whose stored bytes already sum to expect[s] matches every candidate made of chunks that
+ *   are intact, so found[s] is the first such entry of the list: a caller that wants "nothing to do"
+ *   reported puts the empty pattern first.
+ * - A candidate that is a superset of the corrupt set also matches; the order decides.
+ * - adler32 is a weak sum: a false match is possible, exactly as in the reference.
+ * Rotated call
+ * - devs, n_shift and first_stripe mean what they mean for lsec_check_dev_rotated.  Patterns, found
+ *   and trial are logical: logical chunk c of stripe s is read from devs[(c - rot_s) mod (k+m)] and,
+ *   with the flag, rebuilt there.  n_shift == 0 behaves exactly as the unrotated call; n_shift < 0
+ *   and first_stripe < 0 are refused.
+ * Plans and limits
+ * - lsec_plan_kernel 1 and 2, k <= 64, 1 <= m <= 8.  Layout, alignment and block_size rules are those
+ *   of lsec_decode_dev.  The outputs must not overlap one another or the shards.
+ * - Scratch: 16 bytes per (stripe, candidate) of accumulators from the stream-ordered allocator
+ *   (hipMallocAsync on `stream`), zeroed there and freed there, also when a launch fails.
+ * - Tables: the cache entry lsec_decode_dev_patterns uses for the same list, so the search, the repair
+ *   and a later decode with found share one upload and a repeated call does no matrix work.
+ *   nstripes == 0 validates the arguments and prepares the tables, as lsec_decode_dev_patterns does;
+ *   all device pointers may then be NULL.
+ * Refusals
+ * - In this order: plan kernels 3-5; k or m out of range; whatever lsec_decode_dev_patterns refuses,
+ *   in its order; npatterns > 254; nstripes * npatterns too large; a NULL expect or found with
+ *   nstripes > 0; a misaligned counts; unknown flags.  Each returns -1 with a message for
+ *   lsec_last_error that names this call and the limit, and nothing is enqueued: every argument check
+ *   comes before the first HIP call.  There is no fallback to a launch per candidate.
+ * Enqueued on `stream`; return without synchronising.  0 / -1.  (LSEC_LOCATE_CLEAN and
+ * LSEC_LOCATE_MANY: with lsec_locate_dev, below.) */
+#define LSEC_SEARCH_REPAIR 1   /* flags: rebuild every found stripe in place, behind the search */
+
+int lsec_search_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes,
+                             long long block_size, const int *patterns, int npatterns,
+                             const unsigned char *select, const void *expect,
+                             unsigned char *found, void *trial, unsigned int *counts,
+                             int flags, void *stream);
+
+int lsec_search_dev_patterns_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                                     long long block_size, int n_shift, long long first_stripe,
+                                     const int *patterns, int npatterns,
+                                     const unsigned char *select, const void *expect,
+                                     unsigned char *found, void *trial, unsigned int *counts,
+                                     int flags, void *stream);
+
 /* Parity check of device-resident stripes, one pass: are these stripes consistent, and if not,
  * which parity rows disagree?  `shards` are the k+m logical chunks as for lsec_encode_dev; all
  * of them are only read.  `syndrome` is device memory holding nstripes 32-bit words.

@@ -310,6 +310,14 @@ int decode_magic_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, 
                               const unsigned char *stripe_pattern, const MagicCheck &mc, hipStream_t st);
 int decode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
                              long long first_stripe, const MagicCheck &mc, hipStream_t st);
+// every candidate pattern tried on every selected stripe, nothing written: found[s] = the first whose rebuilt stripe
+// sums to expect[s] (trial, counts: optional); with LSEC_SEARCH_REPAIR the found stripes are then rebuilt in place
+int search_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
+                        const uint8_t *select, const uint8_t *expect, uint8_t *found, uint8_t *trial, unsigned *counts, int flags,
+                        hipStream_t st);
+int search_dev_patterns_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                                const int *patterns, int npatterns, const uint8_t *select, const uint8_t *expect, uint8_t *found,
+                                uint8_t *trial, unsigned *counts, int flags, hipStream_t st);
 // the check, and magic[s] = adler32 of stripe s's k+m logical chunks as stored; expect / bad / bad_count (here the
 // two words [parity-bad, magic-bad]): the verdicts, all optional
 int check_magic_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, const MagicCheck &mc,

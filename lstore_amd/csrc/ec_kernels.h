@@ -201,6 +201,46 @@ hipError_t launch_pattern_magic_finalize(const unsigned long long *acc, const ui
                                          int nstripes, int64_t total_len, uint8_t *magic, const uint8_t *expect,
                                          uint8_t *bad, unsigned *bad_count, hipStream_t stream);
 
+// The search for the erasure set that fits the quorum magic (lsec_search_dev_patterns / _rotated): LStore's
+// jerase_brute_recovery over device-resident stripes, every candidate of every selected stripe tried in one
+// pass.  A trial of candidate p on stripe s is the MG tile of pattern p with its stores left out: the
+// survivors it loads, the rows it forms and the unused survivors it loads for the sum give the magic the
+// stripe would have after that decode, and nothing is written.  The SR kernels (k_patsearch_*: the patterned
+// tile bodies under `if constexpr (SR)`) take one tile per (stripe, candidate, piece of the chunk) -- p from
+// the tile index, never from stripe_pattern, which stays null -- skip every stripe whose select byte is 0
+// before any of its chunks is read, and commit into magic_acc[2(s * npat + p)], [.. + 1]: 16 bytes per
+// (stripe, candidate), zeroed before the first launch.  cand_outer picks the tile order (0: the candidate
+// innermost), plain_loads the load kind (0: non-temporal, as the decode's; 1: plain, which ships).  The table is the logical one of
+// lsec_decode_dev_patterns for the same list; the rotated struct turns every selection into a physical
+// device per stripe as PatternRotArgs does (rot0 / rot_step / rot_n), and the magic ids are the selections
+// themselves.  launch_pattern_search_finalize folds the sums, writes trial and found and counts.  The
+// structs derive from PatternMagicArgs, whose layout stays as it is.
+struct PatternSearchArgs : PatternMagicArgs {
+  const uint8_t *select;   // nstripes bytes (device memory), or null: every stripe is searched
+  uint32_t cand_outer;     // tile order: 0 the candidate innermost, 1 the piece innermost
+  uint32_t plain_loads;    // 0: non-temporal loads, 1: plain ones (host side: selects the kernel)
+};
+struct PatternSearchRotArgs : PatternSearchArgs {};  // the type only selects the kernels (PatShards)
+static_assert(sizeof(PatternSearchArgs) == sizeof(PatternMagicArgs) + 16, "PatternSearchArgs layout");
+static_assert(sizeof(PatternSearchRotArgs) < 4096, "PatternSearchArgs: under the 4 KiB of kernel arguments");
+
+// As launch_pattern_magic_*, over npat candidates per stripe: nstripes * npat * (tiles per chunk) < 2^31,
+// stripe_pattern null; the rotated struct with rot_n = nshards.  The launch shapes are the MG forms' own
+// (patsearch_bytewise_form).
+template <typename Args>
+hipError_t launch_pattern_search_bytewise(const Args &a, int rmax, hipStream_t stream);
+template <typename Args>
+hipError_t launch_pattern_search_bitsliced(const Args &a, int rmax, hipStream_t stream);
+// One launch per call, behind the tile launches, one thread per stripe of the whole call.  A stripe with
+// select[s] == 0 (select may be null): found[s] = kLocateClean and nothing else of it is touched.  Every
+// other: for p = 0 .. npat - 1 the word A = (1 + acc[2q]) mod 65521, B = (total_len + acc[2q + 1]) mod 65521,
+// q = s * npat + p, goes to the 4 little-endian bytes at trial + 4q (trial may be null; no alignment);
+// found[s] = the first p whose word equals the 4 bytes at expect + 4s (no alignment), or kLocateMany.
+// counts (may be null; two words, zeroed by the caller): [0] the stripes found, [1] the kLocateMany ones.
+hipError_t launch_pattern_search_finalize(const unsigned long long *acc, const uint8_t *select, uint32_t npat, int nstripes,
+                                          int64_t total_len, const uint8_t *expect, uint8_t *found, uint8_t *trial,
+                                          unsigned *counts, hipStream_t stream);
+
 // Parity check of device-resident stripes (lsec_check_dev): one streaming pass forms the R parity
 // rows of every stripe in registers, as the encode kernels do, and compares them with the stored
 // parity chunks instead of storing them.  Bit r of syndrome[s] is set when row r of stripe s
@@ -237,6 +277,7 @@ struct LocateArgs : CheckArgs {
   const CoefCell *ratio;      // (R - 1) x K, row-major (device memory): Q
   unsigned long long *hyp;    // nstripes words (device memory, all ones)
 };
+
 
 constexpr unsigned kLocateClean = 0xFF, kLocateMany = 0xFE;  // LSEC_LOCATE_CLEAN / _MANY (lstore_ec.h)
 
@@ -350,6 +391,10 @@ struct PatternRotArgs : PatternArgs {};
 // one output row per pattern (single erasures)
 hipError_t launch_pattern_rot_bytewise(const PatternRotArgs &a, hipStream_t stream);
 hipError_t launch_pattern_rot_bitsliced(const PatternRotArgs &a, hipStream_t stream);
+// The same kernels over any logical table with a stripe_pattern (the repair behind a rotated search, whose
+// stripe_pattern is the search's `found`): rmax = the table's largest erasure count, 1..kPatMaxOut.
+hipError_t launch_pattern_rot_rows_bytewise(const PatternRotArgs &a, int rmax, hipStream_t stream);
+hipError_t launch_pattern_rot_rows_bitsliced(const PatternRotArgs &a, int rmax, hipStream_t stream);
 
 // Parity update for partial-stripe writes (lsec_update_dev): c of a stripe's K data chunks change
 // from old_i to fresh_i, and the code is linear, so every parity row r takes
@@ -526,7 +571,7 @@ hipError_t launch_update_magic_finalize(const unsigned long long *acc, const uns
 // functions record the form at the one place where the template arguments are known; the record
 // is the calling thread's, holds the launches since launch_record_reset() in order (the engine
 // resets it on entry to each of those calls) and costs a few host stores per launch.
-enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic, kFormPatMagic, kFormChkMagic, kFormChkMagicRot, kFormEncMagicRot };
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic, kFormPatMagic, kFormChkMagic, kFormChkMagicRot, kFormEncMagicRot, kFormPatSearch, kFormPatSearchRot };
 struct LaunchForm {
   int family, sliced, R, KC, IT, VW, BF, DW;
 };
@@ -544,6 +589,8 @@ bool predict_masked_launch(bool sliced, int K, int R, int packet, int dw_pref, L
 bool predict_masked_magic_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // and for the patterned decode with the magic (kFormPatMagic; R: the table's rmax, at least 1)
 bool predict_pattern_magic_launch(bool sliced, int K, int R, int packet, LaunchForm *out);
+// and for the search (kFormPatSearch, or kFormPatSearchRot with `rotated`; R: the table's rmax, at least 1)
+bool predict_pattern_search_launch(bool rotated, bool sliced, int K, int R, int packet, LaunchForm *out);
 // and for the check with the magic (kFormChkMagic, or kFormChkMagicRot with `rotated`)
 bool predict_check_magic_launch(bool rotated, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // and for the rotated encode with the magic (kFormEncMagicRot)

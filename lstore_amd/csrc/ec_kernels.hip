@@ -424,6 +424,50 @@ hipError_t launch_pattern_magic_bitsliced(const PatternMagicArgs &a, int rmax, h
   return by_r(rmax, [&](auto r) { return dispatch_patmagic_bitsliced<decltype(r)::value>(a, st, grid); });
 }
 
+// ------------------------------------------------------------------ the search over candidate patterns
+namespace {
+bool rot_fields_ok(uint32_t rot0, uint32_t rot_step, uint32_t rot_n, int nshards);
+
+// tiles of the launch (one per stripe, candidate and piece), or 0: none, or more than 32-bit indices hold
+template <typename Args>
+int pattern_search_grid(const Args &a, int rmax, uint64_t tile_bytes, int64_t bytes) {
+  // (pattern_args_ok's fields without its stripe_pattern-or-rotation rule: the candidate comes from the tile index)
+  if (!(a.K >= 1 && a.K <= kMaxK && rmax >= 1 && rmax <= kPatMaxOut && a.recs && a.cells && a.npat >= 1 && a.npat <= kLocateMany &&
+        a.nshards > a.K && a.nshards <= kPatMaxShards && a.nshards - a.K <= kPatMaxUnused && a.size % 8 == 0 && a.unused &&
+        a.magic_acc && reinterpret_cast<uintptr_t>(a.magic_acc) % 8 == 0 && !a.stripe_pattern))
+    return 0;
+  if constexpr (std::is_same<Args, PatternSearchRotArgs>::value) {
+    if (!rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.nshards)) return 0;
+  }
+  const uint64_t per = (static_cast<uint64_t>(bytes) + tile_bytes - 1) / tile_bytes;
+  const uint64_t tiles = per * static_cast<uint64_t>(a.nstripes) * a.npat;
+  return tiles < (1ull << 31) ? static_cast<int>(tiles) : 0;
+}
+}  // namespace
+
+template <typename Args>
+hipError_t launch_pattern_search_bytewise(const Args &a, int rmax, hipStream_t st) {
+  if (a.nstripes <= 0 || a.size <= 0) return a.nstripes < 0 || a.size < 0 ? hipErrorInvalidValue : hipSuccess;
+  const BwForm f = patsearch_bytewise_form(a.K, rmax);
+  const int grid = pattern_search_grid(a, rmax, BwShape{f.it, f.vw, f.bf}.tile_bytes(), a.size);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(rmax, [&](auto r) { return dispatch_patsearch_bytewise<decltype(r)::value, Args>(a, st, grid); });
+}
+
+template <typename Args>
+hipError_t launch_pattern_search_bitsliced(const Args &a, int rmax, hipStream_t st) {
+  if (a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size <= 0) return a.nstripes < 0 || a.size < 0 ? hipErrorInvalidValue : hipSuccess;
+  const int grid = pattern_search_grid(a, rmax, kBlock * 4, a.size / 8);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(rmax, [&](auto r) { return dispatch_patsearch_bitsliced<decltype(r)::value, Args>(a, st, grid); });
+}
+
+template hipError_t launch_pattern_search_bytewise<PatternSearchArgs>(const PatternSearchArgs &, int, hipStream_t);
+template hipError_t launch_pattern_search_bytewise<PatternSearchRotArgs>(const PatternSearchRotArgs &, int, hipStream_t);
+template hipError_t launch_pattern_search_bitsliced<PatternSearchArgs>(const PatternSearchArgs &, int, hipStream_t);
+template hipError_t launch_pattern_search_bitsliced<PatternSearchRotArgs>(const PatternSearchRotArgs &, int, hipStream_t);
+
 // ------------------------------------------------------------------ check / locate, rotated or not
 namespace {
 bool rot_fields_ok(uint32_t rot0, uint32_t rot_step, uint32_t rot_n, int nshards) {
@@ -595,6 +639,30 @@ hipError_t launch_pattern_rot_bitsliced(const PatternRotArgs &a, hipStream_t st)
   const int grid = tile_grid(kBlock * 4, a.size / 8, a.nstripes);
   if (!grid) return hipErrorInvalidValue;
   return dispatch_patrot_bitsliced(a, st, grid);
+}
+
+namespace {
+// any logical table: the pattern ids from stripe_pattern, the selections rotated per stripe
+bool pattern_rot_rows_args_ok(const PatternRotArgs &a, int rmax) {
+  return pattern_args_ok(a, rmax) && a.stripe_pattern && rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.nshards);
+}
+}  // namespace
+
+hipError_t launch_pattern_rot_rows_bytewise(const PatternRotArgs &a, int rmax, hipStream_t st) {
+  if (!pattern_rot_rows_args_ok(a, rmax)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int grid = tile_grid(bw_auto(a.K, rmax).tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(rmax, [&](auto r) { return dispatch_patrot_rows_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_pattern_rot_rows_bitsliced(const PatternRotArgs &a, int rmax, hipStream_t st) {
+  if (!pattern_rot_rows_args_ok(a, rmax) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int grid = tile_grid(kBlock * 4, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(rmax, [&](auto r) { return dispatch_patrot_rows_bitsliced<decltype(r)::value>(a, st, grid); });
 }
 
 // ------------------------------------------------------------------ parity update
@@ -845,6 +913,19 @@ bool predict_pattern_magic_launch(bool sliced, int K, int R, int packet, LaunchF
   return true;
 }
 
+bool predict_pattern_search_launch(bool rotated, bool sliced, int K, int R, int packet, LaunchForm *out) {
+  if (K < 1 || K > kMaxK || R < 1 || R > kPatMaxOut) return false;
+  const int family = rotated ? kFormPatSearchRot : kFormPatSearch;
+  if (sliced) {
+    if (packet <= 0 || packet % 4 != 0) return false;
+    *out = LaunchForm{family, 1, R, 0, 0, 0, 0, 1};
+    return true;
+  }
+  const BwForm f = patsearch_bytewise_form(K, R);
+  *out = LaunchForm{family, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
+  return true;
+}
+
 bool predict_check_magic_launch(bool rotated, bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out) {
   if (K < 1 || K > kMaxK || R < 1 || R > 8) return false;
   const int family = rotated ? kFormChkMagicRot : kFormChkMagic;
@@ -1058,6 +1139,38 @@ __global__ void k_pattern_magic_finalize(const unsigned long long *acc, const ui
   const bool differs = want != m;
   if (bad) bad[s] = differs ? 1 : 0;
   if (bad_count && differs) atomicAdd(bad_count, 1u);
+}
+
+// The search's verdicts (launch_pattern_search_finalize, ec_kernels.h): acc holds the sums of every (stripe,
+// candidate), per-tile values in [0, M) added up.  expect, found and trial have no alignment: bytewise.
+__global__ void k_pattern_search_finalize(const unsigned long long *acc, const uint8_t *select, uint32_t npat, int nstripes,
+                                          uint64_t total_len, const uint8_t *expect, uint8_t *found, uint8_t *trial,
+                                          unsigned *counts) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nstripes) return;
+  if (select && select[s] == 0) {  // not searched: its accumulators and trial words are neither read nor written
+    found[s] = kLocateClean;
+    return;
+  }
+  const uint8_t *x = expect + 4ll * s;
+  const uint32_t want = x[0] | (x[1] << 8) | (x[2] << 16) | (static_cast<uint32_t>(x[3]) << 24);
+  uint32_t verdict = kLocateMany;
+  for (uint32_t p = 0; p < npat; ++p) {
+    const uint64_t q = static_cast<uint64_t>(s) * npat + p;
+    const uint32_t A = static_cast<uint32_t>((1 + acc[2 * q]) % kAdlerMod);
+    const uint32_t B = static_cast<uint32_t>((total_len % kAdlerMod + acc[2 * q + 1]) % kAdlerMod);
+    const uint32_t m = (B << 16) | A;
+    if (trial) {
+      uint8_t *w = trial + 4 * q;
+      w[0] = m & 255;
+      w[1] = (m >> 8) & 255;
+      w[2] = (m >> 16) & 255;
+      w[3] = m >> 24;
+    }
+    if (verdict == kLocateMany && m == want) verdict = p;
+  }
+  found[s] = static_cast<uint8_t>(verdict);
+  if (counts) atomicAdd(counts + (verdict == kLocateMany ? 1 : 0), 1u);
 }
 
 // The check's magics and verdicts (launch_check_magic_finalize, ec_kernels.h): acc holds each stripe's
@@ -1400,6 +1513,16 @@ hipError_t launch_pattern_magic_finalize(const unsigned long long *acc, const ui
   if (!acc || !magic || total_len < 0 || reinterpret_cast<uintptr_t>(bad_count) % 4 != 0) return hipErrorInvalidValue;
   return launch_kernel(&k_pattern_magic_finalize, dim3((nstripes + 255) / 256), dim3(256), st, acc, stripe_pattern, npat,
                        nstripes, static_cast<uint64_t>(total_len), magic, expect, bad, bad_count);
+}
+
+hipError_t launch_pattern_search_finalize(const unsigned long long *acc, const uint8_t *select, uint32_t npat, int nstripes,
+                                          int64_t total_len, const uint8_t *expect, uint8_t *found, uint8_t *trial,
+                                          unsigned *counts, hipStream_t st) {
+  if (nstripes <= 0) return hipSuccess;
+  if (!acc || !expect || !found || npat < 1 || npat > kLocateMany || total_len < 0 || reinterpret_cast<uintptr_t>(counts) % 4 != 0)
+    return hipErrorInvalidValue;
+  return launch_kernel(&k_pattern_search_finalize, dim3((nstripes + 255) / 256), dim3(256), st, acc, select, npat, nstripes,
+                       static_cast<uint64_t>(total_len), expect, found, trial, counts);
 }
 
 hipError_t launch_check_magic_finalize(const unsigned long long *acc, const unsigned *syndrome, int nstripes,

@@ -1442,10 +1442,11 @@ __device__ __forceinline__ uint32_t rot_back(const Args &a, uint32_t s) {
 }
 
 // Where a patterned tile takes a shard ref from: the record's selection itself (PatternArgs), or
-// the physical device holding that logical chunk in stripe s (PatternRotArgs, ec_kernels.h).
+// the physical device holding that logical chunk in stripe s (PatternRotArgs and PatternSearchRotArgs,
+// ec_kernels.h).
 template <typename Args>
 struct PatShards {
-  static constexpr bool kRot = std::is_same<Args, PatternRotArgs>::value;
+  static constexpr bool kRot = std::is_same<Args, PatternRotArgs>::value || std::is_same<Args, PatternSearchRotArgs>::value;
   const Args &a;
   uint32_t back = 0;
   __device__ __forceinline__ PatShards(const Args &a_, uint32_t s) : a(a_) {
@@ -1478,14 +1479,31 @@ struct PatShards {
 // nout == 0 no longer leaves but takes the checksum-only path (no image is read, nothing is
 // stored), and units past the end of a ragged tile read as zero and add nothing.  red: kBlock / 64
 // words of LDS.  Without MG un, macc and red are not looked at and the code is the plain decode's.
+//
+// SR (lsec_search_dev_patterns / _rotated; Args: PatternSearchArgs, PatternSearchRotArgs; with MG): the
+// trial of a candidate.  A tile belongs to (stripe s, candidate p, piece of the chunk), all three from the
+// tile index (pat_search_tile), and p is a record of the table, never a stripe_pattern id.  The tile reads
+// select[s] first and leaves when it is 0 -- uniform over the workgroup, ahead of every shard access and
+// of block_sum.  Then it is the MG tile with every store to a shard compiled out, and it commits into the
+// accumulator pair of (s, p): macc[2(s * npat + p)], [.. + 1].  NT: pat_load's.
 typedef const __attribute__((address_space(4))) PatUnused ConstUnused;
 
 // the logical chunk id of selection sel in a stripe of pattern p: the records of a call without a
-// stripe_pattern hold the physical devices of rotation p (wave-uniform scalar arithmetic)
+// stripe_pattern hold the physical devices of rotation p (wave-uniform scalar arithmetic); the search's
+// records (SR) are logical whether its shards rotate or not
+template <bool SR = false>
 __device__ __forceinline__ uint32_t pat_logical(const PatternArgs &a, uint32_t p, uint32_t sel) {
-  if (a.stripe_pattern) return sel;
+  if (SR || a.stripe_pattern) return sel;
   const uint32_t c = sel + p;
   return c >= static_cast<uint32_t>(a.nshards) ? c - static_cast<uint32_t>(a.nshards) : c;
+}
+
+// A streaming load of the patterned tiles: non-temporal as everywhere else, or (the search's A/B form)
+// a plain one, which leaves the line in the XCD's L2 for the candidates that read it next.
+template <bool NT, typename V>
+__device__ __forceinline__ V pat_load(uint64_t p) {
+  if constexpr (NT) return __builtin_nontemporal_load(gptr<V>(p));
+  else return *gptr<V>(p);
 }
 
 // bw_inputs for the MG tiles of a full tile: the same loads and arithmetic (`work`: the pattern has
@@ -1493,9 +1511,9 @@ __device__ __forceinline__ uint32_t pat_logical(const PatternArgs &a, uint32_t p
 // X0 and extra() as bw_inputs (the check's MG tiles: its stored parity loads, issued where bw_inputs
 // issues them).  EARLY (K fixed; the caller always has work): an input is handed to seen() right
 // ahead of its own arithmetic, not behind everybody's, so its registers die with its pair as in
-// bw_inputs.  The patterned MG tiles leave all three at their defaults.
-template <int R, int KC, int IT, int VW, bool BF, bool X0 = false, bool EARLY = false, typename Addr, typename Seen,
-          typename Extra = NoLoads>
+// bw_inputs.  The patterned MG tiles leave all three at their defaults.  NT: pat_load's.
+template <int R, int KC, int IT, int VW, bool BF, bool X0 = false, bool EARLY = false, bool NT = true, typename Addr,
+          typename Seen, typename Extra = NoLoads>
 __device__ __forceinline__ void bw_inputs_seen(typename VecT<VW>::type (&acc)[IT][R], ConstCell *cells, int K, bool work,
                                                Addr &&addr, Seen &&seen, Extra &&extra = Extra()) {
   typedef typename VecT<VW>::type V;
@@ -1506,7 +1524,7 @@ __device__ __forceinline__ void bw_inputs_seen(typename VecT<VW>::type (&acc)[IT
     for (int j = 0; j < KC; ++j) {
       const uint64_t p = addr(j);
 #pragma unroll
-      for (int it = 0; it < IT; ++it) v[j][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
+      for (int it = 0; it < IT; ++it) v[j][it] = pat_load<NT, V>(p + it * kStep);
     }
     extra();
     if constexpr (EARLY) {
@@ -1552,7 +1570,7 @@ __device__ __forceinline__ void bw_inputs_seen(typename VecT<VW>::type (&acc)[IT
         if (jj < nj) {
           const uint64_t p = addr(j0 + jj);
 #pragma unroll
-          for (int it = 0; it < IT; ++it) v[jj][it] = __builtin_nontemporal_load(gptr<V>(p + it * kStep));
+          for (int it = 0; it < IT; ++it) v[jj][it] = pat_load<NT, V>(p + it * kStep);
         }
       }
       if (work) {
@@ -1573,7 +1591,30 @@ __device__ __forceinline__ void bw_inputs_seen(typename VecT<VW>::type (&acc)[IT
   }
 }
 
-template <int R, int KC, int IT, int VW, bool BF, bool MG = false, typename Args>
+// The (stripe, candidate, piece) of search tile t, tps pieces per stripe.  cand_outer 0: the candidate runs
+// innermost, so the tiles an XCD takes in a row read the same bytes of one stripe; 1: the piece does.
+template <typename Args>
+__device__ __forceinline__ void pat_search_tile(const Args &a, uint32_t t, uint32_t tps, uint32_t &s, uint32_t &p, uint32_t &piece) {
+  if (a.cand_outer) {
+    const uint32_t sp = t / tps;
+    piece = t - sp * tps;
+    s = sp / a.npat;
+    p = sp - s * a.npat;
+  } else {
+    const uint32_t sq = t / a.npat;
+    p = t - sq * a.npat;
+    s = sq / tps;
+    piece = sq - s * tps;
+  }
+}
+// select[s] != 0, or no select (s uniform over the workgroup)
+template <typename Args>
+__device__ __forceinline__ bool pat_search_selected(const Args &a, uint32_t s) {
+  if (!a.select) return true;
+  return __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(*gptr<uint8_t>(reinterpret_cast<uint64_t>(a.select) + s))) != 0;
+}
+
+template <int R, int KC, int IT, int VW, bool BF, bool MG = false, bool SR = false, bool NT = true, typename Args>
 __device__ __forceinline__ void pat_bytewise_tiles(const Args &a, ConstUnused *un = nullptr, unsigned long long *macc = nullptr,
                                                    uint32_t *red = nullptr) {
   typedef typename VecT<VW>::type V;
@@ -1583,21 +1624,29 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a, ConstUnused *u
   const int K = KC ? KC : a.K;
   const int64_t C = a.size;
   const uint32_t tiles_per_stripe = static_cast<uint32_t>((C + kTile - 1) / kTile);
-  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  if constexpr (SR) ntiles *= a.npat;
   ConstRec *recs = reinterpret_cast<ConstRec *>(reinterpret_cast<uintptr_t>(a.recs));
   ConstCell *images = const_cells(a.cells);
 
   for_tiles<(kTile >= 8192 ? 1 : 8192 / kTile)>(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
-    const uint32_t s = t / tiles_per_stripe;
-    const uint32_t p = stripe_pattern_id(a, s);
-    if (p >= a.npat) return;  // no such pattern: the stripe is left alone
+    uint32_t s, p, piece;
+    if constexpr (SR) {
+      pat_search_tile(a, t, tiles_per_stripe, s, p, piece);
+      if (!pat_search_selected(a, s)) return;  // not searched: none of its chunks is read
+    } else {
+      s = t / tiles_per_stripe;
+      piece = t - s * tiles_per_stripe;
+      p = stripe_pattern_id(a, s);
+      if (p >= a.npat) return;  // no such pattern: the stripe is left alone
+    }
     ConstRec *rec = recs + p;
     const uint32_t nout = rec->nout;
     if (!MG && nout == 0) return;  // nothing to rebuild
     ConstCell *cells = images + rec->cells_off;
     const PatShards<Args> sh(a, s);
-    const int64_t off0 = static_cast<int64_t>(t - s * tiles_per_stripe) * kTile + threadIdx.x * kLane;
-    const bool full = (static_cast<int64_t>(t - s * tiles_per_stripe) + 1) * kTile <= C;  // wave-uniform
+    const int64_t off0 = static_cast<int64_t>(piece) * kTile + threadIdx.x * kLane;
+    const bool full = (static_cast<int64_t>(piece) + 1) * kTile <= C;  // wave-uniform
     MagicLane ml;  // the stripe magic's partial sums (MG only)
 
     V acc[IT][R];
@@ -1608,13 +1657,13 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a, ConstUnused *u
 
     if (full) {
       if constexpr (MG) {
-        bw_inputs_seen<R, KC, IT, VW, BF>(
+        bw_inputs_seen<R, KC, IT, VW, BF, false, false, NT>(
             acc, cells, K, nout != 0,
             [&](int j) LSEC_INLINE {
               const ShardRef in = sh.at(rec->in_sel[j]);
               return in.base + s * in.stride + off0;
             },
-            [&](int j, const V(&v)[IT]) LSEC_INLINE { ml_add<IT, VW>(ml, v, pat_logical(a, p, rec->in_sel[j])); });
+            [&](int j, const V(&v)[IT]) LSEC_INLINE { ml_add<IT, VW>(ml, v, pat_logical<SR>(a, p, rec->in_sel[j])); });
       } else {
         bw_inputs<R, KC, IT, VW, BF, false>(
             acc, cells, K,
@@ -1624,13 +1673,15 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a, ConstUnused *u
             },
             NoLoads());
       }
+      if constexpr (!SR) {
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
-          const ShardRef out = sh.at(rec->out_sel[r]);
-          const uint64_t q = out.base + s * out.stride + off0;
+        for (int r = 0; r < R; ++r) {
+          if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
+            const ShardRef out = sh.at(rec->out_sel[r]);
+            const uint64_t q = out.base + s * out.stride + off0;
 #pragma unroll
-          for (int it = 0; it < IT; ++it) put_nt<false, V>(q + it * kStep, acc[it][r]);
+            for (int it = 0; it < IT; ++it) put_nt<false, V>(q + it * kStep, acc[it][r]);
+          }
         }
       }
     } else {
@@ -1641,18 +1692,20 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a, ConstUnused *u
 #pragma unroll
         for (int it = 0; it < IT; ++it) v[it] = load_ragged<VW>(q, off0 + it * kStep, C);
         if constexpr (MG) {
-          ml_add<IT, VW>(ml, v, pat_logical(a, p, rec->in_sel[j]));
+          ml_add<IT, VW>(ml, v, pat_logical<SR>(a, p, rec->in_sel[j]));
           if (nout == 0) continue;  // checksum only: the record has no image
         }
         bw_acc1<R, IT, VW, BF, false>(acc, v, cells, K, j);
       }
+      if constexpr (!SR) {
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        if (static_cast<uint32_t>(r) < nout) {
-          const ShardRef out = sh.at(rec->out_sel[r]);
-          const uint64_t q = out.base + s * out.stride;
+        for (int r = 0; r < R; ++r) {
+          if (static_cast<uint32_t>(r) < nout) {
+            const ShardRef out = sh.at(rec->out_sel[r]);
+            const uint64_t q = out.base + s * out.stride;
 #pragma unroll
-          for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
+            for (int it = 0; it < IT; ++it) store_ragged<false, VW>(q, off0 + it * kStep, C, acc[it][r]);
+          }
         }
       }
     }
@@ -1664,7 +1717,7 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a, ConstUnused *u
           V o[IT];
 #pragma unroll
           for (int it = 0; it < IT; ++it) o[it] = acc[it][r];
-          ml_add<IT, VW>(ml, o, pat_logical(a, p, rec->out_sel[r]));
+          ml_add<IT, VW>(ml, o, pat_logical<SR>(a, p, rec->out_sel[r]));
         }
       }
       // the survivors the decode did not read, up to four in flight as the inputs are
@@ -1679,16 +1732,16 @@ __device__ __forceinline__ void pat_bytewise_tiles(const Args &a, ConstUnused *u
             const uint64_t q = in.base + s * in.stride;
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
-              if (full) v[uu][it] = __builtin_nontemporal_load(gptr<V>(q + off0 + it * kStep));
+              if (full) v[uu][it] = pat_load<NT, V>(q + off0 + it * kStep);
               else v[uu][it] = load_ragged<VW>(q, off0 + it * kStep, C);
             }
           }
         }
 #pragma unroll
         for (uint32_t uu = 0; uu < 4; ++uu)
-          if (u0 + uu < nu) ml_add<IT, VW>(ml, v[uu], pat_logical(a, p, ur->sel[u0 + uu]));
+          if (u0 + uu < nu) ml_add<IT, VW>(ml, v[uu], pat_logical<SR>(a, p, ur->sel[u0 + uu]));
       }
-      ml_commit(ml, macc, s, a.nshards, static_cast<uint64_t>(C), static_cast<uint64_t>(off0), kStep, red);
+      ml_commit(ml, macc, SR ? s * a.npat + p : s, a.nshards, static_cast<uint64_t>(C), static_cast<uint64_t>(off0), kStep, red);
     }
   }, a.tile_phase);
 }
@@ -1712,8 +1765,8 @@ __global__ __launch_bounds__(kBlock) void k_patmagic_bytewise(PatternMagicArgs a
 
 // k_gf8_bitsliced's lanes (one dword of packet-column space per lane) under a pattern record.
 // MG as in pat_bytewise_tiles: the lanes past the end of a ragged last tile then skip the loads and
-// the stores, but still join the tile's reduction (as k_gf8_bitsliced's do).
-template <int R, bool MG = false, typename Args>
+// the stores, but still join the tile's reduction (as k_gf8_bitsliced's do).  SR, NT as there.
+template <int R, bool MG = false, bool SR = false, bool NT = true, typename Args>
 __device__ __forceinline__ void pat_bitsliced_tiles(const Args &a, ConstUnused *un = nullptr, unsigned long long *macc = nullptr,
                                                     uint32_t *red = nullptr) {
   const int K = a.K;
@@ -1721,20 +1774,28 @@ __device__ __forceinline__ void pat_bitsliced_tiles(const Args &a, ConstUnused *
   const uint32_t col_bytes = static_cast<uint32_t>(a.size / 8);  // nsuper * P
   constexpr uint32_t kTile = kBlock * 4;
   const uint32_t tiles_per_stripe = (col_bytes + kTile - 1) / kTile;
-  const uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  uint32_t ntiles = tiles_per_stripe * static_cast<uint32_t>(a.nstripes);
+  if constexpr (SR) ntiles *= a.npat;
   ConstRec *recs = reinterpret_cast<ConstRec *>(reinterpret_cast<uintptr_t>(a.recs));
   ConstCell *images = const_cells(a.cells);
 
   for_tiles(ntiles, a.tiles, a.tiles_pre, [&](uint32_t t) {
-    const uint32_t s = t / tiles_per_stripe;
-    const uint32_t p = stripe_pattern_id(a, s);
-    if (p >= a.npat) return;
+    uint32_t s, p, piece;
+    if constexpr (SR) {
+      pat_search_tile(a, t, tiles_per_stripe, s, p, piece);
+      if (!pat_search_selected(a, s)) return;
+    } else {
+      s = t / tiles_per_stripe;
+      piece = t - s * tiles_per_stripe;
+      p = stripe_pattern_id(a, s);
+      if (p >= a.npat) return;
+    }
     ConstRec *rec = recs + p;
     const uint32_t nout = rec->nout;
     if (!MG && nout == 0) return;
     ConstCell *cells = images + rec->cells_off;
     const PatShards<Args> sh(a, s);
-    const uint32_t colb = (t - s * tiles_per_stripe) * kTile + threadIdx.x * 4;
+    const uint32_t colb = piece * kTile + threadIdx.x * 4;
     const bool valid = colb < col_bytes;
     if (!MG && !valid) return;  // lanes past the end of a ragged last tile
     const uint32_t sp = colb / P;
@@ -1753,9 +1814,9 @@ __device__ __forceinline__ void pat_bitsliced_tiles(const Args &a, ConstUnused *
         const uint64_t q = in.base + s * in.stride + off;
         uint32_t e[8];
 #pragma unroll
-        for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<uint32_t>(q + x * P));
+        for (int x = 0; x < 8; ++x) e[x] = pat_load<NT, uint32_t>(q + x * P);
         if constexpr (MG) {
-          ml_add<8, 1>(ml, e, pat_logical(a, p, rec->in_sel[j]));
+          ml_add<8, 1>(ml, e, pat_logical<SR>(a, p, rec->in_sel[j]));
           if (nout == 0) continue;  // checksum only: the record has no image
         }
         uint32_t c[R];
@@ -1770,11 +1831,13 @@ __device__ __forceinline__ void pat_bitsliced_tiles(const Args &a, ConstUnused *
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if (static_cast<uint32_t>(r) < nout) {  // wave-uniform
-          const ShardRef out = sh.at(rec->out_sel[r]);
-          const uint64_t q = out.base + s * out.stride + off;
+          if constexpr (!SR) {
+            const ShardRef out = sh.at(rec->out_sel[r]);
+            const uint64_t q = out.base + s * out.stride + off;
 #pragma unroll
-          for (int x = 0; x < 8; ++x) put_nt<false, uint32_t>(q + x * P, acc[r][x]);
-          if constexpr (MG) ml_add<8, 1>(ml, acc[r], pat_logical(a, p, rec->out_sel[r]));
+            for (int x = 0; x < 8; ++x) put_nt<false, uint32_t>(q + x * P, acc[r][x]);
+          }
+          if constexpr (MG) ml_add<8, 1>(ml, acc[r], pat_logical<SR>(a, p, rec->out_sel[r]));
         }
       }
       if constexpr (MG) {
@@ -1786,12 +1849,13 @@ __device__ __forceinline__ void pat_bitsliced_tiles(const Args &a, ConstUnused *
           const uint64_t q = in.base + s * in.stride + off;
           uint32_t e[8];
 #pragma unroll
-          for (int x = 0; x < 8; ++x) e[x] = __builtin_nontemporal_load(gptr<uint32_t>(q + x * P));
-          ml_add<8, 1>(ml, e, pat_logical(a, p, ur->sel[u]));
+          for (int x = 0; x < 8; ++x) e[x] = pat_load<NT, uint32_t>(q + x * P);
+          ml_add<8, 1>(ml, e, pat_logical<SR>(a, p, ur->sel[u]));
         }
       }
     }
-    if constexpr (MG) ml_commit(ml, macc, s, a.nshards, static_cast<uint64_t>(a.size), static_cast<uint64_t>(off), P, red);
+    if constexpr (MG)
+      ml_commit(ml, macc, SR ? s * a.npat + p : s, a.nshards, static_cast<uint64_t>(a.size), static_cast<uint64_t>(off), P, red);
   }, a.tile_phase);
 }
 
@@ -1913,8 +1977,110 @@ hipError_t dispatch_patmagic_bitsliced(const PatternMagicArgs &a, hipStream_t st
   return launch_tiled(&k_patmagic_bitsliced<R>, grid, st, a);
 }
 
+// The search (lsec_search_dev_patterns / _rotated): the MG tile bodies in their SR mode, in the MG forms'
+// own shapes (patsearch_bytewise_form), once per load kind (NT) and per argument struct.
+constexpr BwForm patsearch_bytewise_form(int K, int R) { return patmagic_bytewise_form(K, R); }
+
+template <int R, int KC, int IT, int VW, bool BF, bool NT, typename Args>
+__global__ __launch_bounds__(kBlock) void k_patsearch_bytewise(Args a) {
+  __shared__ uint32_t red[kBlock / 64];
+  pat_bytewise_tiles<R, KC, IT, VW, BF, true, true, NT>(
+      a, reinterpret_cast<ConstUnused *>(reinterpret_cast<uintptr_t>(a.unused)), a.magic_acc, red);
+}
+
+template <int R, bool NT, typename Args>
+__global__ __launch_bounds__(kBlock) void k_patsearch_bitsliced(Args a) {
+  __shared__ uint32_t red[kBlock / 64];
+  pat_bitsliced_tiles<R, true, true, NT>(a, reinterpret_cast<ConstUnused *>(reinterpret_cast<uintptr_t>(a.unused)), a.magic_acc,
+                                         red);
+}
+
+template <typename Args>
+constexpr int patsearch_family() {
+  return std::is_same<Args, PatternSearchRotArgs>::value ? kFormPatSearchRot : kFormPatSearch;
+}
+
+template <int R, int KC, int IT, int VW, bool BF, typename Args>
+hipError_t patsearch_kernel(const Args &a, hipStream_t st, int grid) {
+  record_launch({patsearch_family<Args>(), 0, R, KC, IT, VW, BF ? 1 : 0, 0});
+  if (a.plain_loads) return launch_tiled(&k_patsearch_bytewise<R, KC, IT, VW, BF, false, Args>, grid, st, a);
+  return launch_tiled(&k_patsearch_bytewise<R, KC, IT, VW, BF, true, Args>, grid, st, a);
+}
+
+// grid: the launch's tiles, one per (stripe, candidate, piece)
+template <int R, typename Args>
+hipError_t dispatch_patsearch_bytewise(const Args &a, hipStream_t st, int grid) {
+  const BwForm f = patsearch_bytewise_form(a.K, R);
+  if constexpr (R == 1) {
+    constexpr BwShape sh = bw_auto(0, 1);
+    switch (f.kc) {
+      case 6: return patsearch_kernel<1, 6, sh.it, sh.vw, sh.bf>(a, st, grid);
+      case 10: return patsearch_kernel<1, 10, sh.it, sh.vw, sh.bf>(a, st, grid);
+      default: return patsearch_kernel<1, 0, sh.it, sh.vw, sh.bf>(a, st, grid);
+    }
+  } else {
+    if (f.it == 1) return patsearch_kernel<R, 0, 1, 4, true>(a, st, grid);
+    return patsearch_kernel<R, 0, 2, 4, true>(a, st, grid);
+  }
+}
+
+template <int R, typename Args>
+hipError_t dispatch_patsearch_bitsliced(const Args &a, hipStream_t st, int grid) {
+  record_launch({patsearch_family<Args>(), 1, R, 0, 0, 0, 0, 1});
+  if (a.plain_loads) return launch_tiled(&k_patsearch_bitsliced<R, false, Args>, grid, st, a);
+  return launch_tiled(&k_patsearch_bitsliced<R, true, Args>, grid, st, a);
+}
+
+// instantiated per R in ec_patterns_search_inst.hip
+#define LSEC_DECLARE_PATSEARCH_R(RR)                                                                                 \
+  extern template hipError_t dispatch_patsearch_bytewise<RR, PatternSearchArgs>(const PatternSearchArgs &, hipStream_t, int);       \
+  extern template hipError_t dispatch_patsearch_bitsliced<RR, PatternSearchArgs>(const PatternSearchArgs &, hipStream_t, int);      \
+  extern template hipError_t dispatch_patsearch_bytewise<RR, PatternSearchRotArgs>(const PatternSearchRotArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_patsearch_bitsliced<RR, PatternSearchRotArgs>(const PatternSearchRotArgs &, hipStream_t, int);
+#ifndef LSEC_INSTANTIATING_PATSEARCH
+LSEC_DECLARE_PATSEARCH_R(1) LSEC_DECLARE_PATSEARCH_R(2) LSEC_DECLARE_PATSEARCH_R(3) LSEC_DECLARE_PATSEARCH_R(4)
+LSEC_DECLARE_PATSEARCH_R(5) LSEC_DECLARE_PATSEARCH_R(6) LSEC_DECLARE_PATSEARCH_R(7) LSEC_DECLARE_PATSEARCH_R(8)
+#endif
+
+// The rotated repair behind a search: k_patrot_* for tables of up to R erasures per pattern, in the patterned
+// decode's shapes (pat_bytewise_form), one unit per R (ec_patterns_rot_rows_inst.hip).  One row is the single-row
+// unit's own kernels (dispatch_patrot_*), which no second unit instantiates.
+template <int R, int IT>
+hipError_t patrot_rows_kernel(const PatternRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormPatRot, 0, R, 0, IT, 4, 1, 0});
+  return launch_tiled(&k_patrot_bytewise<R, 0, IT, 4, true>, grid, st, a);
+}
+
+template <int R>
+hipError_t dispatch_patrot_rows_bytewise(const PatternRotArgs &a, hipStream_t st, int grid) {
+  if constexpr (R == 1) {
+    return dispatch_patrot_bytewise(a, st, grid);
+  } else {
+    if (pat_bytewise_form(a.K, R).it == 1) return patrot_rows_kernel<R, 1>(a, st, grid);
+    return patrot_rows_kernel<R, 2>(a, st, grid);
+  }
+}
+
+template <int R>
+hipError_t dispatch_patrot_rows_bitsliced(const PatternRotArgs &a, hipStream_t st, int grid) {
+  if constexpr (R == 1) {
+    return dispatch_patrot_bitsliced(a, st, grid);
+  } else {
+    record_launch({kFormPatRot, 1, R, 0, 0, 0, 0, 1});
+    return launch_tiled(&k_patrot_bitsliced<R>, grid, st, a);
+  }
+}
+
+#define LSEC_DECLARE_PATROT_ROWS_R(RR)                                                                      \
+  extern template hipError_t dispatch_patrot_rows_bytewise<RR>(const PatternRotArgs &, hipStream_t, int);  \
+  extern template hipError_t dispatch_patrot_rows_bitsliced<RR>(const PatternRotArgs &, hipStream_t, int);
+#ifndef LSEC_INSTANTIATING_PATROT_ROWS
+LSEC_DECLARE_PATROT_ROWS_R(1) LSEC_DECLARE_PATROT_ROWS_R(2) LSEC_DECLARE_PATROT_ROWS_R(3) LSEC_DECLARE_PATROT_ROWS_R(4)
+LSEC_DECLARE_PATROT_ROWS_R(5) LSEC_DECLARE_PATROT_ROWS_R(6) LSEC_DECLARE_PATROT_ROWS_R(7) LSEC_DECLARE_PATROT_ROWS_R(8)
+#endif
+
 // instantiated per R in ec_patterns_magic_inst.hip
-#define LSEC_DECLARE_PATMAGIC_R(RR)                                                                     \
+#define LSEC_DECLARE_PATMAGIC_R(RR)                                                                    \
   extern template hipError_t dispatch_patmagic_bytewise<RR>(const PatternMagicArgs &, hipStream_t, int); \
   extern template hipError_t dispatch_patmagic_bitsliced<RR>(const PatternMagicArgs &, hipStream_t, int);
 #ifndef LSEC_INSTANTIATING_PATMAGIC

@@ -989,10 +989,12 @@ uint32_t rot0_from(uint32_t rot0, uint32_t rot_step, int n, long long s0) {
 
 // The launches of a patterned call, split so that tile indices stay 32-bit (as enqueue_apply).  A
 // stripe's pattern id comes from stripe_pattern or, without one, from its rotation.  rotated_repair:
-// the repair behind a rotated locate, whose table is the k+m single erasures of the logical chunks
-// and whose kernel turns each selection into a physical device by the stripe's rotation.
+// kRepairLocate, the repair behind a rotated locate, whose table is the k+m single erasures of the
+// logical chunks and whose kernel turns each selection into a physical device by the stripe's
+// rotation; kRepairSearch, the one behind a rotated search: the same over any logical table.
+enum { kRepairNone = 0, kRepairLocate, kRepairSearch };
 int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::Dev &dv, const lsec_shard_t *sh, int nstripes,
-                     long long C, const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, bool rotated_repair,
+                     long long C, const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, int rotated_repair,
                      hipStream_t st) {
   const lio_erasure_plan_t *p = &e->pub;
   const int n = p->data_strips + p->parity_strips;
@@ -1016,7 +1018,10 @@ int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::De
     for (int i = 0; i < n; ++i) a.sh[i] = shard_from(sh[i], s0);
     a.stripe_pattern = stripe_pattern ? stripe_pattern + s0 : nullptr;
     a.rot0 = rotates ? rot0_from(rot0, rot_step, n, s0) : 0;
-    if (rotated_repair) {
+    if (rotated_repair == kRepairSearch) {
+      const hipError_t err = sliced ? lsec::launch_pattern_rot_rows_bitsliced(a, tab.rmax, st) : lsec::launch_pattern_rot_rows_bytewise(a, tab.rmax, st);
+      if (err != hipSuccess) return fail("rotated repair kernel launch failed: %s", hipGetErrorString(err));
+    } else if (rotated_repair) {
       const hipError_t err = sliced ? lsec::launch_pattern_rot_bitsliced(a, st) : lsec::launch_pattern_rot_bytewise(a, st);
       if (err != hipSuccess) return fail("rotated repair kernel launch failed: %s", hipGetErrorString(err));
     } else {
@@ -1040,7 +1045,7 @@ int decode_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long l
   const PatternTable *tab = nullptr;
   PatternTable::Dev dv;
   if (pattern_table_dev(e, patterns, npatterns, nullptr, 0, &tab, &dv)) return -1;
-  return enqueue_patterns(e, *tab, dv, sh, nstripes, C, stripe_pattern, 0, 0, false, st);
+  return enqueue_patterns(e, *tab, dv, sh, nstripes, C, stripe_pattern, 0, 0, kRepairNone, st);
 }
 
 int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
@@ -1057,7 +1062,7 @@ int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
   if (pattern_table_dev(e, nullptr, 0, lost, n_shift, &tab, &dv)) return -1;
   const int n = p->data_strips + p->parity_strips;
   return enqueue_patterns(e, *tab, dv, devs, nstripes, C, nullptr, pattern_rot0(n, n_shift, first_stripe),
-                          static_cast<uint32_t>(n_shift % n), false, st);
+                          static_cast<uint32_t>(n_shift % n), kRepairNone, st);
 }
 
 // ---------------------------------------------------------------- patterned decode with the stripe magics
@@ -1213,6 +1218,147 @@ int decode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes,
   const int n = p->data_strips + p->parity_strips;
   return enqueue_patterns_magic(e, name, *tab, dv, unused, devs, nstripes, C, nullptr, pattern_rot0(n, n_shift, first_stripe),
                                 static_cast<uint32_t>(n_shift % n), mc, st);
+}
+
+// ---------------------------------------------------------------- the search for the erasure set that fits the magic
+// lsec_search_dev_patterns / _rotated: jerase_brute_recovery (segment/jerasure.c:271-339) over device-resident
+// stripes.  The table is the cache entry lsec_decode_dev_patterns uses for the same list, with the magic
+// form's unused-survivor records, so the search, the repair and a later decode with `found` share one
+// upload.  The SR kernels (ec_kernels.h, PatternSearchArgs) try every candidate on every selected stripe
+// over 16 bytes per (stripe, candidate) of accumulators from the stream-ordered allocator -- zeroed before
+// the first launch, advancing by 2 * s0 * npatterns words per launch, freed on the stream, also when a
+// launch fails -- and one finalize launch behind them writes trial and found and counts.  A launch takes
+// whole stripes with all their candidates: the split counts (stripe, candidate) pairs, and
+// lsec_test_set_pattern_split lowers it.  With LSEC_SEARCH_REPAIR the patterned decode follows on the
+// stream with found as its stripe_pattern (rotated: the k_patrot_* kernels of the table's row count).
+// Every refusal names the call; all of them come before the first HIP call.
+// The form that ships is the better measured one (profiles/search_ab.jsonl): the candidate innermost
+// in the tile order, plain loads.  lsec_test_set_search_form picks another for A/B runs.
+std::atomic<int> g_search_cand_outer{0}, g_search_plain_loads{1};
+
+namespace {
+
+struct SearchCall {
+  const char *name;
+  bool rotated;
+  int n_shift;
+  long long first_stripe;
+  const uint8_t *select;
+  const uint8_t *expect;
+  uint8_t *found;
+  uint8_t *trial;
+  unsigned *counts;
+  int flags;
+};
+
+constexpr int kSearchMaxPatterns = 254;  // LSEC_LOCATE_MANY and LSEC_LOCATE_CLEAN stay past the table
+
+// stripes per launch: every stripe brings npat candidates' tiles
+long long search_launch_stripes(long long C, int npat) { return std::max(1LL, launch_stripes(C, false) / npat); }
+
+int search_dev(PlanExt *e, const SearchCall &c, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns,
+               int npatterns, hipStream_t st) {
+  const char *name = c.name;
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  if (!patterns) return fail("%s: patterns is NULL", name);
+  if (nstripes < 0) return fail("%s: nstripes %d is negative", name, nstripes);
+  if (c.rotated && c.n_shift < 0) return fail("%s: n_shift %d is negative", name, c.n_shift);
+  if (c.rotated && c.first_stripe < 0) return fail("%s: first_stripe %lld is negative", name, c.first_stripe);
+  if (named(name, pattern_limits(p) || check_geometry(p, C) ? -1 : 0)) return -1;
+  {
+    PatternLists pl;  // the lists' own refusals, ahead of the search's (pattern_table_dev parses them again)
+    if (named(name, parse_pattern_lists(p, patterns, npatterns, nullptr, 0, pl))) return -1;
+  }
+  if (npatterns > kSearchMaxPatterns)
+    return fail("%s: npatterns=%d outside 1..%d (found[] keeps LSEC_LOCATE_MANY and LSEC_LOCATE_CLEAN past the table)", name,
+                npatterns, kSearchMaxPatterns);
+  if (static_cast<long long>(nstripes) * npatterns >= (1LL << 31))
+    return fail("%s: nstripes * npatterns = %lld is not below 2^31 (stripe, candidate) pairs per call", name,
+                static_cast<long long>(nstripes) * npatterns);
+  if (nstripes > 0 && !c.expect) return fail("%s: expect is NULL", name);
+  if (nstripes > 0 && !c.found) return fail("%s: found is NULL", name);
+  if (reinterpret_cast<uintptr_t>(c.counts) % 4 != 0)
+    return fail("%s: counts %p is not a multiple of 4 bytes (two 32-bit words)", name, static_cast<const void *>(c.counts));
+  if (c.flags & ~LSEC_SEARCH_REPAIR) return fail("%s: unknown flags 0x%x (LSEC_SEARCH_REPAIR = 1 is the only one)", name, c.flags);
+  const PatternTable *tab = nullptr;
+  PatternTable::Dev dv;
+  const lsec::PatUnused *unused = nullptr;
+  if (named(name, pattern_table_dev(e, patterns, npatterns, nullptr, 0, &tab, &dv)) || named(name, pattern_unused_dev(e, tab, &unused)))
+    return -1;
+  if (nstripes <= 0) return 0;
+
+  const int n = p->data_strips + p->parity_strips;
+  const int rmax = std::max(1, tab->rmax);
+  const uint32_t rot_step = c.rotated ? static_cast<uint32_t>(c.n_shift % n) : 0;
+  const uint32_t rot0 = c.rotated ? pattern_rot0(n, c.n_shift, c.first_stripe) : 0;
+  lsec::PatternSearchRotArgs a;  // (PatternSearchArgs, which the unrotated launches take)
+  std::memset(static_cast<void *>(&a), 0, sizeof(a));
+  a.recs = dv.recs;
+  a.cells = dv.cells;
+  a.unused = unused;
+  a.npat = static_cast<uint32_t>(npatterns);
+  a.K = p->data_strips;
+  a.packet = p->packet_size;
+  a.nshards = n;
+  a.size = C;
+  a.rot_step = rot_step;
+  a.rot_n = c.rotated ? static_cast<uint32_t>(n) : 0;
+  a.cand_outer = g_search_cand_outer.load(std::memory_order_relaxed) ? 1 : 0;
+  a.plain_loads = g_search_plain_loads.load(std::memory_order_relaxed) ? 1 : 0;
+  const bool sliced = kernel_kind(p->method, p->w) == KBITSLICED;
+  const unsigned long long acc_bytes = 16ull * nstripes * npatterns;
+  unsigned long long *acc = nullptr;
+  hipError_t err = hipMallocAsync(reinterpret_cast<void **>(&acc), acc_bytes, st);
+  if (err == hipSuccess && (err = hipMemsetAsync(acc, 0, acc_bytes, st)) != hipSuccess) (void)hipFreeAsync(acc, st);
+  if (err != hipSuccess) return fail("%s: the magic accumulators (%llu bytes): %s", name, acc_bytes, hipGetErrorString(err));
+  int rc = 0;
+  if (c.counts && (err = hipMemsetAsync(c.counts, 0, 2 * sizeof(unsigned), st)) != hipSuccess)
+    rc = fail("%s: zeroing counts: %s", name, hipGetErrorString(err));
+  long long per = search_launch_stripes(C, npatterns);
+  if (const int hook = g_pattern_split.load(std::memory_order_relaxed); hook > 0) per = std::min<long long>(per, hook);
+  if (rc == 0)
+    rc = for_launches(nstripes, per, [&](long long s0, int ns) {
+      a.nstripes = ns;
+      for (int i = 0; i < n; ++i) a.sh[i] = shard_from(sh[i], s0);
+      a.select = c.select ? c.select + s0 : nullptr;
+      a.rot0 = c.rotated ? rot0_from(rot0, rot_step, n, s0) : 0;
+      a.magic_acc = acc + 2 * s0 * npatterns;
+      hipError_t le;
+      if (c.rotated) le = sliced ? lsec::launch_pattern_search_bitsliced(a, rmax, st) : lsec::launch_pattern_search_bytewise(a, rmax, st);
+      else {
+        const lsec::PatternSearchArgs &u = a;
+        le = sliced ? lsec::launch_pattern_search_bitsliced(u, rmax, st) : lsec::launch_pattern_search_bytewise(u, rmax, st);
+      }
+      if (le != hipSuccess) return fail("%s: kernel launch failed: %s", name, hipGetErrorString(le));
+      return 0;
+    });
+  if (rc == 0) {
+    err = lsec::launch_pattern_search_finalize(acc, c.select, a.npat, nstripes, static_cast<int64_t>(n) * C, c.expect, c.found,
+                                               c.trial, c.counts, st);
+    if (err != hipSuccess) rc = fail("%s: finalize launch failed: %s", name, hipGetErrorString(err));
+  }
+  err = hipFreeAsync(acc, st);
+  if (err != hipSuccess && rc == 0) rc = fail("%s: freeing the magic accumulators: %s", name, hipGetErrorString(err));
+  if (rc || !(c.flags & LSEC_SEARCH_REPAIR)) return rc;
+  // every found stripe rebuilt in place: found[s] < npatterns names its pattern, both sentinels leave a stripe alone
+  return named(name, enqueue_patterns(e, *tab, dv, sh, nstripes, C, c.found, rot0, rot_step, c.rotated ? kRepairSearch : kRepairNone, st));
+}
+
+}  // namespace
+
+int search_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
+                        const uint8_t *select, const uint8_t *expect, uint8_t *found, uint8_t *trial, unsigned *counts, int flags,
+                        hipStream_t st) {
+  const SearchCall c = {"lsec_search_dev_patterns", false, 0, 0, select, expect, found, trial, counts, flags};
+  return search_dev(e, c, sh, nstripes, C, patterns, npatterns, st);
+}
+
+int search_dev_patterns_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
+                                const int *patterns, int npatterns, const uint8_t *select, const uint8_t *expect, uint8_t *found,
+                                uint8_t *trial, unsigned *counts, int flags, hipStream_t st) {
+  const SearchCall c = {"lsec_search_dev_patterns_rotated", true, n_shift, first_stripe, select, expect, found, trial, counts, flags};
+  return search_dev(e, c, devs, nstripes, C, patterns, npatterns, st);
 }
 
 // ---------------------------------------------------------------- check / locate, rotated or not
@@ -1470,7 +1616,7 @@ int scrub_dev(PlanExt *e, const ScrubCall &c, const lsec_shard_t *sh, int nstrip
                                                                       nstripes, k, R, rot0, rot_step, static_cast<uint32_t>(n), st)
                                    : lsec::launch_locate_finalize(syndrome, c.hyp, c.located, c.counts, nstripes, k, R, st);
   if (err != hipSuccess) return fail("%slocate finalize launch failed: %s", c.rotated ? "rotated " : "", hipGetErrorString(err));
-  if (repair) return enqueue_patterns(e, *tab, dv, sh, nstripes, C, c.located, rot0, rot_step, c.rotated, st);
+  if (repair) return enqueue_patterns(e, *tab, dv, sh, nstripes, C, c.located, rot0, rot_step, c.rotated ? kRepairLocate : kRepairNone, st);
   return 0;
 }
 
@@ -2387,6 +2533,28 @@ int lsec_test_predict_masked_magic_form(int plan_kernel, int K, int R, int packe
   const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
   std::memcpy(form, v, sizeof(v));
   return 0;
+}
+
+// Test hook, not in include/ (no GPU): the form (family 16, or 17 with `rotated`, of the launch record)
+// lsec_search_dev_patterns and lsec_search_dev_patterns_rotated launch for a plan of kernel 1 or 2 with K inputs and a
+// table of at most R erasures per pattern (R >= 1), from the function the dispatch calls.
+int lsec_test_predict_search_form(int rotated, int plan_kernel, int K, int R, int packet, int *form) {
+  if (!form) return fail("lsec_test_predict_search_form: NULL output");
+  if (plan_kernel != KBYTEWISE && plan_kernel != KBITSLICED) return fail("lsec_test_predict_search_form: plan kernel %d", plan_kernel);
+  lsec::LaunchForm f;
+  if (!lsec::predict_pattern_search_launch(rotated != 0, plan_kernel == KBITSLICED, K, R, packet, &f))
+    return fail("lsec_test_predict_search_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
+  const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
+  std::memcpy(form, v, sizeof(v));
+  return 0;
+}
+
+// Test hook, not in include/: the search's tile order (cand_outer 0: the candidate innermost, the default; 1: the
+// piece of the chunk innermost) and load kind (plain_loads 0: non-temporal; 1: plain, the default) for A/B runs in
+// one process (tools/search_ab.py).  The results do not depend on either.
+void lsec_test_set_search_form(int cand_outer, int plain_loads) {
+  g_search_cand_outer.store(cand_outer ? 1 : 0, std::memory_order_relaxed);
+  g_search_plain_loads.store(plain_loads ? 1 : 0, std::memory_order_relaxed);
 }
 
 // Test hook, not in include/ (no GPU): the form (family 12 of the launch record) lsec_decode_magic_dev_patterns and

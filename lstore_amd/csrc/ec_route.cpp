@@ -669,6 +669,35 @@ int lsec_decode_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *
                                   static_cast<hipStream_t>(stream));
 }
 
+// (the ladder of lsec_decode_magic_dev_patterns, then the search's own rungs in search_dev)
+int lsec_search_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shards, int nstripes, long long block_size,
+                             const int *patterns, int npatterns, const unsigned char *select, const void *expect,
+                             unsigned char *found, void *trial, unsigned int *counts, int flags, void *stream) {
+  static const char name[] = "lsec_search_dev_patterns";
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (decode_magic_limits(plan, name)) return -1;
+  if (!shards) return fail("%s: shards is NULL", name);
+  if (named(name, check_shards(plan, shards, nstripes))) return -1;
+  return search_dev_patterns(e, shards, nstripes, block_size, patterns, npatterns, select, static_cast<const uint8_t *>(expect),
+                             found, static_cast<uint8_t *>(trial), counts, flags, static_cast<hipStream_t>(stream));
+}
+
+int lsec_search_dev_patterns_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                                     int n_shift, long long first_stripe, const int *patterns, int npatterns,
+                                     const unsigned char *select, const void *expect, unsigned char *found, void *trial,
+                                     unsigned int *counts, int flags, void *stream) {
+  static const char name[] = "lsec_search_dev_patterns_rotated";
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (decode_magic_limits(plan, name)) return -1;
+  if (!devs) return fail("%s: devs is NULL", name);
+  if (named(name, check_shards(plan, devs, nstripes))) return -1;
+  return search_dev_patterns_rotated(e, devs, nstripes, block_size, n_shift, first_stripe, patterns, npatterns, select,
+                                     static_cast<const uint8_t *>(expect), found, static_cast<uint8_t *>(trial), counts, flags,
+                                     static_cast<hipStream_t>(stream));
+}
+
 int lsec_check_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
                            int n_shift, long long first_stripe, unsigned int *syndrome, unsigned int *bad_count,
                            void *stream) {

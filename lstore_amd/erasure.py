@@ -87,12 +87,15 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_encode_dev_rotated", "lsec_update_dev_rotated", "lsec_update_dev_masked",
            "lsec_update_dev_masked_rotated", "lsec_update_magic_dev_masked", "lsec_update_magic_dev_masked_rotated",
            "lsec_decode_magic_dev_patterns", "lsec_decode_magic_dev_rotated",
-           "lsec_check_magic_dev", "lsec_check_magic_dev_rotated", "lsec_encode_magic_dev_rotated")
+           "lsec_check_magic_dev", "lsec_check_magic_dev_rotated", "lsec_encode_magic_dev_rotated",
+           "lsec_search_dev_patterns", "lsec_search_dev_patterns_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
 # lsec_locate_dev: the two sentinels of located[] and the flag
 LOCATE_CLEAN, LOCATE_MANY, LOCATE_REPAIR = 0xFF, 0xFE, 1
+# lsec_search_dev_patterns: the flag (found[] takes the two sentinels of located[])
+SEARCH_REPAIR = 1
 # lsec_check_magic_dev: the bits of bad[]
 SCRUB_BAD_PARITY, SCRUB_BAD_MAGIC = 1, 2
 # lsec_update_dev: the flag
@@ -174,6 +177,14 @@ def lib():
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lsec_decode_magic_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
                                                 C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lsec_search_dev_patterns.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.lsec_search_dev_patterns_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
+                                                   C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.lsec_test_predict_search_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.lsec_test_set_search_form.argtypes = [C.c_int, C.c_int]
+    L.lsec_test_set_search_form.restype = None
     L.lsec_check_magic_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
     L.lsec_check_magic_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
@@ -661,6 +672,54 @@ class Plan:
                                             0 if expect is None else expect.data_ptr(), 0 if bad is None else bad.data_ptr(),
                                             0 if bad_count is None else bad_count.data_ptr(), _stream_handle(stream))
 
+    def search_dev_patterns_refs(self, refs, nstripes: int, block_size: int, patterns, expect_ptr: int, found_ptr: int,
+                                 select_ptr: int = 0, trial_ptr: int = 0, counts_ptr: int = 0, flags: int = 0,
+                                 stream: int = 0) -> None:
+        """lsec_search_dev_patterns: every candidate of `patterns` (a sequence of erasure lists of logical chunk ids) tried
+        on every selected stripe, no chunk written.  found_ptr (1 byte per stripe): the first candidate whose rebuilt
+        stripe sums to the 4 bytes at expect_ptr + 4*s, LOCATE_MANY if none does, LOCATE_CLEAN where the byte at
+        select_ptr + s (0: every stripe is selected) is 0.  trial_ptr (4 bytes per stripe and candidate) and counts_ptr
+        (two aligned uint32: found, LOCATE_MANY) are optional (0).  flags: SEARCH_REPAIR rebuilds every found stripe in
+        place behind the search.  refs None / pointers 0 with nstripes == 0: only prepare the tables."""
+        patterns = list(patterns)
+        _check(lib().lsec_search_dev_patterns(self._p, None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                              _pattern_array(patterns), len(patterns), select_ptr or None, expect_ptr or None,
+                                              found_ptr or None, trial_ptr or None, counts_ptr or None, flags, stream),
+               "lsec_search_dev_patterns")
+
+    def search_dev_patterns_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int, patterns,
+                                         expect_ptr: int, found_ptr: int, select_ptr: int = 0, trial_ptr: int = 0,
+                                         counts_ptr: int = 0, flags: int = 0, stream: int = 0) -> None:
+        """lsec_search_dev_patterns_rotated: search_dev_patterns_refs over the k+m PHYSICAL devices of a rotated LUN
+        (refs[i]: device i, as check_dev_rotated_refs).  Patterns, found and trial are those of the logical view."""
+        patterns = list(patterns)
+        _check(lib().lsec_search_dev_patterns_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes,
+                                                      block_size, n_shift, first_stripe, _pattern_array(patterns),
+                                                      len(patterns), select_ptr or None, expect_ptr or None, found_ptr or None,
+                                                      trial_ptr or None, counts_ptr or None, flags, stream),
+               "lsec_search_dev_patterns_rotated")
+
+    def search_dev_patterns(self, data, parity, patterns, expect, found, select=None, trial=None, counts=None,
+                            repair: bool = False, stream=None) -> None:
+        """torch: search data [N,k,C] / parity [N,m,C] for the candidate pattern that fits each stripe's quorum magic.
+        expect: uint8 device tensor of 4 bytes per stripe; found, select: uint8 [N]; trial: uint8 of 4 bytes per stripe
+        and candidate; counts: a 32-bit tensor of two elements; repair: rebuild the found stripes in place."""
+        refs, n, size = self.tensor_refs(data, parity)
+        npat = len(list(patterns))
+        for what, t, want in (("expect", expect, 4 * n), ("found", found, n), ("select", select, n),
+                              ("trial", trial, 4 * n * npat)):
+            if t is None and what in ("select", "trial"):
+                continue
+            if t is None or t.dtype.itemsize != 1 or not t.is_cuda or not t.is_contiguous() or t.numel() != want:
+                raise ValueError(f"{what} must be a contiguous uint8 device tensor of {want} bytes")
+        if counts is not None and (counts.dtype.itemsize != 4 or not counts.is_cuda or not counts.is_contiguous()
+                                   or counts.numel() != 2):
+            raise ValueError("counts must be a contiguous 32-bit device tensor of two elements")
+        self.search_dev_patterns_refs(refs, n, size, patterns, expect.data_ptr(), found.data_ptr(),
+                                      0 if select is None else select.data_ptr(), 0 if trial is None else trial.data_ptr(),
+                                      0 if counts is None else counts.data_ptr(), SEARCH_REPAIR if repair else 0,
+                                      _stream_handle(stream))
+
     def check_dev_refs(self, refs, nstripes: int, block_size: int, syndrome_ptr: int, bad_count_ptr: int = 0,
                        stream: int = 0) -> None:
         """lsec_check_dev: one-pass parity check.  syndrome_ptr: device address of nstripes uint32 words,
@@ -1009,9 +1068,14 @@ CHKMAGIC_FAMILIES = ("chkmagic", "chkmagicrot")
 ENCMAGIC_FAMILIES = ("encmagicrot",)
 
 
+# and behind those (ENCMAGIC_FAMILIES stays as it is too): family numbers 16 and 17, the search over candidate patterns
+# and its rotated form
+SEARCH_FAMILIES = ("patsearch", "patsearchrot")
+
+
 def _form(v) -> Form:
     return Form((FORM_FAMILIES + MASKED_FAMILIES + MAGIC_FAMILIES + PATMAGIC_FAMILIES + CHKMAGIC_FAMILIES +
-                 ENCMAGIC_FAMILIES)[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
+                 ENCMAGIC_FAMILIES + SEARCH_FAMILIES)[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
 
 
 def launch_record() -> list:
@@ -1062,6 +1126,23 @@ def predict_pattern_magic_form(plan_kernel: int, k: int, rows: int, packet: int 
     _check(lib().lsec_test_predict_pattern_magic_form(plan_kernel, k, rows, packet, out),
            "lsec_test_predict_pattern_magic_form")
     return _form(out)
+
+
+def predict_search_form(rotated: bool, plan_kernel: int, k: int, rows: int, packet: int = 0) -> Form:
+    """Test hook (no GPU): the Form ("patsearch", or "patsearchrot" with `rotated`) search_dev_patterns_refs and
+    search_dev_patterns_rotated_refs launch for a plan of that kernel with k inputs and a candidate list of at most
+    `rows` erasures per pattern (at least 1: a list of empty patterns launches the one-row form)."""
+    out = (C.c_int * 8)()
+    _check(lib().lsec_test_predict_search_form(1 if rotated else 0, plan_kernel, k, rows, packet, out),
+           "lsec_test_predict_search_form")
+    return _form(out)
+
+
+def set_search_form(cand_outer: bool = False, plain_loads: bool = True) -> None:
+    """Test hook: the search's tile order (cand_outer: the piece of the chunk innermost, not the candidate) and load
+    kind (plain_loads: plain, not non-temporal) for A/B runs; the defaults are what ships, and the results do not depend
+    on either."""
+    lib().lsec_test_set_search_form(1 if cand_outer else 0, 1 if plain_loads else 0)
 
 
 def predict_check_magic_form(rotated: bool, plan_kernel: int, k: int, rows: int, packet: int = 0, block_size: int = 0) -> Form:
