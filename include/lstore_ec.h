@@ -309,6 +309,88 @@ int lsec_search_dev_patterns_rotated(lio_erasure_plan_t *plan, const lsec_shard_
                                      unsigned char *found, void *trial, unsigned int *counts,
                                      int flags, void *stream);
 
+/* The read path's quorum vote, on the device: the first thing LStore does per stripe when it reads or scrubs
+ * (segjerase_read_func, segment/jerasure.c:1383-1462) -- the majority vote over the k+m stored 4-byte magics and
+ * the classification built on it -- for a caller whose images and magics already sit in device memory.  Its
+ * `quorum` is directly the `expect`, and its `ids` the `stripe_pattern`, of lsec_decode_magic_dev_patterns,
+ * lsec_check_magic_dev and lsec_search_dev_patterns, so a read or a scrub is one chain of calls on one stream
+ * with no host step.  Purely additive too: the version stays 3, a caller detects the calls by their symbols.
+ *
+ * Inputs
+ * - `stored`: k+m entries, required.  The stored magic of entry i for stripe s is the 4 bytes at
+ *   base + s*stride: device memory, only read, no alignment requirement on base or stride (LStore's
+ *   [magic | chunk] records: {image_i, C+4}).  base == NULL: that device is unreadable for the whole call.
+ *   Plain call: entry i is logical chunk i.  Rotated call: entry i is physical device i, and logical chunk c of
+ *   stripe s is entry (c - rot_s) mod (k+m), rot_s exactly as for lsec_check_dev_rotated; n_shift == 0 behaves
+ *   as the plain call, n_shift < 0 and first_stripe < 0 are refused.
+ * - `shards` / `devs`: optional (NULL).  The chunks, under the layout rule of lsec_check_dev /
+ *   lsec_check_dev_rotated.  Only the blank scan reads them.  With NULL there is no scan: LSEC_VOTE_BLANK is
+ *   never reported (such stripes are LSEC_VOTE_OK) and block_size is not looked at.  An entry whose `stored`
+ *   base is NULL is not validated and never read.
+ * - `patterns` / npatterns: optional (NULL / 0; with NULL patterns, ids must be NULL too).  The list format of
+ *   lsec_decode_dev_patterns: erasure lists of LOGICAL chunk ids, each ended by -1.  1 <= npatterns <= 254 (as
+ *   for the search: both sentinels stay past the table), at most min(m, 8) erasures per pattern.
+ * Per stripe (all ids logical)
+ * - The quorum is the largest group of readable chunks whose 4 stored bytes are equal; between groups of equal
+ *   size the one whose first member has the lowest id wins (the reference's "first group with the largest
+ *   count").  An unreadable chunk is in no group.
+ * - `quorum`: required with nstripes > 0; 4*nstripes bytes, no alignment requirement.  The quorum's 4 bytes as
+ *   stored; 0 when no chunk is readable.
+ * - `outside`: optional; nstripes 64-bit words, 8-byte aligned.  Bit c is set when logical chunk c is outside
+ *   the quorum (unreadable, or another magic).  Bits k+m and above are 0.
+ * - `cls`: required with nstripes > 0; nstripes bytes.
+ *     LSEC_VOTE_LOST      no chunk is readable, or the quorum has fewer than k members;
+ *     LSEC_VOTE_BLANK     chunks were given, all k+m are in the quorum, its bytes are all 0 and every byte of
+ *                         all k+m chunks is 0 (never written);
+ *     LSEC_VOTE_OK        all k data chunks are in the quorum and the stripe is not BLANK;
+ *     LSEC_VOTE_DEGRADED  otherwise.
+ *   This is step 1 of lsec_segment_read, with one difference: an unreadable chunk never shadows a readable
+ *   group of the same size (it matters only for k = 1).
+ * - `ids`: optional; nstripes bytes, usable as stripe_pattern of the patterned calls with the same list.
+ *     DEGRADED: the lowest p whose erasure set equals the outside set, LSEC_LOCATE_MANY if the list has none;
+ *     OK with LSEC_VOTE_PARANOID: the same lookup (the outside set is then empty or parity-only: the paranoid
+ *       read verifies the stripe and rebuilds the parity outside the quorum);
+ *     OK without the flag, and BLANK: LSEC_LOCATE_CLEAN (the patterned calls skip the stripe);
+ *     LOST: LSEC_LOCATE_MANY.
+ * - `counts`: optional; five 32-bit words, 4-byte aligned: the stripes of class OK, DEGRADED, BLANK and LOST,
+ *   then the stripes whose lookup found no pattern.  The call sets them; it does not add to them.
+ * The call sets every output element itself.  Outputs must not overlap one another, `stored` or the chunks.
+ * Cost
+ * - The vote reads (k+m)*4 bytes per stripe.  The blank scan reads the k+m chunks of a stripe only when all its
+ *   magics are zero and agree (a blank candidate), and stops launching loads for a stripe once a nonzero byte
+ *   was seen; a stripe that is no candidate costs no chunk read.
+ * - Scratch: 16 bytes per stripe from the stream-ordered allocator (hipMallocAsync on `stream`), zeroed there and
+ *   freed there, also when a launch fails.
+ * - Tables: the list's masks live in the cache entry lsec_decode_dev_patterns uses for the same list, so vote,
+ *   decode, search and repair share one table and a repeated call does no matrix work and no upload.
+ *   nstripes == 0 validates the arguments and, with patterns, prepares the tables as lsec_decode_dev_patterns
+ *   does; all device pointers may then be NULL.
+ * Plans and limits
+ * - lsec_plan_kernel 1 and 2, 1 <= m <= 8, k + m <= 64 (the mask is one word, a stripe is one wavefront).
+ * Refusals
+ * - In this order: plan kernels 3-5; k, m or k+m out of range; a NULL stored; a negative nstripes; (rotated) a
+ *   negative n_shift or first_stripe; whatever lsec_decode_dev_patterns refuses about the list, in its order;
+ *   npatterns > 254; ids without patterns; with chunks, the layout and block_size refusals of lsec_check_dev;
+ *   a NULL quorum or cls with nstripes > 0; a misaligned outside or counts; unknown flag bits.  Each returns -1
+ *   with a message for lsec_last_error that names this call and the limit, and nothing is enqueued: every
+ *   argument check comes before the first HIP call.  There is no host fallback.
+ * Enqueued on `stream`; return without synchronising.  0 / -1. */
+#define LSEC_VOTE_OK        0  /* every data chunk is in the quorum (parity chunks may be outside it) */
+#define LSEC_VOTE_DEGRADED  1  /* a data chunk is outside the quorum, and the quorum has >= k chunks */
+#define LSEC_VOTE_BLANK     2  /* never written: all k+m magics zero and every byte of every chunk zero */
+#define LSEC_VOTE_LOST      3  /* quorum smaller than k, or no device readable */
+#define LSEC_VOTE_PARANOID  1  /* flags: OK stripes get a pattern id too (verify every stripe) */
+
+int lsec_vote_dev(lio_erasure_plan_t *plan, const lsec_shard_t *stored, const lsec_shard_t *shards,
+                  int nstripes, long long block_size, const int *patterns, int npatterns,
+                  void *quorum, unsigned char *cls, unsigned char *ids,
+                  unsigned long long *outside, unsigned int *counts, int flags, void *stream);
+int lsec_vote_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *stored, const lsec_shard_t *devs,
+                          int nstripes, long long block_size, int n_shift, long long first_stripe,
+                          const int *patterns, int npatterns,
+                          void *quorum, unsigned char *cls, unsigned char *ids,
+                          unsigned long long *outside, unsigned int *counts, int flags, void *stream);
+
 /* Parity check of device-resident stripes, one pass: are these stripes consistent, and if not,
  * which parity rows disagree?  `shards` are the k+m logical chunks as for lsec_encode_dev; all
  * of them are only read.  `syndrome` is device memory holding nstripes 32-bit words.

@@ -115,6 +115,11 @@ struct PatternTable {
   // lsec_decode_magic_dev_* call on a device
   std::vector<lsec::PatUnused> unused;
   DevImage dev_unused;
+  // what the vote looks a stripe's outside set up in: each pattern's erasure set as one 64-bit mask of logical ids
+  // (ids of 64 and above, which no vote sees, leave no bit), built with the table and uploaded at the first
+  // lsec_vote_dev* call on a device
+  std::vector<unsigned long long> masks;
+  DevImage dev_masks;
   struct Dev {                   // the pair on one device, as enqueue_patterns takes it
     const lsec::PatRecord *recs = nullptr;
     const CoefCell *cells = nullptr;
@@ -157,6 +162,7 @@ struct PlanImpl {
       f(tab.second.dev_recs);
       f(tab.second.dev_cells);
       f(tab.second.dev_unused);
+      f(tab.second.dev_masks);
     }
   }
 };
@@ -318,6 +324,18 @@ int search_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long l
 int search_dev_patterns_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, int n_shift, long long first_stripe,
                                 const int *patterns, int npatterns, const uint8_t *select, const uint8_t *expect, uint8_t *found,
                                 uint8_t *trial, unsigned *counts, int flags, hipStream_t st);
+// the quorum vote over the k+m stored magics of every stripe (stored[i]: 4 bytes at base + s * stride, a NULL base:
+// unreadable; rotated: physical device i), the blank scan over the chunks (sh, may be null) and the lookup of each
+// stripe's outside set in the pattern list (may be null): the head of the read, whose quorum / ids feed the calls above
+struct VoteOut {
+  uint8_t *quorum, *cls, *ids;
+  unsigned long long *outside;
+  unsigned *counts;
+};
+int vote_dev(PlanExt *e, const lsec_shard_t *stored, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns,
+             int npatterns, const VoteOut &out, int flags, hipStream_t st);
+int vote_dev_rotated(PlanExt *e, const lsec_shard_t *stored, const lsec_shard_t *devs, int nstripes, long long C, int n_shift,
+                     long long first_stripe, const int *patterns, int npatterns, const VoteOut &out, int flags, hipStream_t st);
 // the check, and magic[s] = adler32 of stripe s's k+m logical chunks as stored; expect / bad / bad_count (here the
 // two words [parity-bad, magic-bad]): the verdicts, all optional
 int check_magic_dev(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, unsigned *syndrome, const MagicCheck &mc,

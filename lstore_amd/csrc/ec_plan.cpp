@@ -24,6 +24,7 @@
 
 #include "ec_jit.h"
 #include "ec_engine.h"
+#include "ec_vote.h"
 
 #include <unistd.h>
 
@@ -924,6 +925,11 @@ int fill_pattern_table(PlanExt *e, PatternLists &pl, PatternTable &tab) {
     if (pattern_record(e, lists[i], rots[i], tab.recs[i], tab.unused[i], rows[i])) return -1;
     tab.rmax = std::max(tab.rmax, static_cast<int>(tab.recs[i].nout));
   }
+  // each entry's erasure set as a mask of logical ids: what lsec_vote_dev compares a stripe's outside set with
+  tab.masks.assign(np, 0);
+  for (size_t i = 0; i < np; ++i)
+    for (int id : lists[i])
+      if (id < 64) tab.masks[i] |= 1ull << id;
   // one CoefCell[rmax][k] image per entry with something to rebuild; rows past its count are zero cells
   tab.cells.clear();
   CoefCell zero;
@@ -1359,6 +1365,164 @@ int search_dev_patterns_rotated(PlanExt *e, const lsec_shard_t *devs, int nstrip
                                 uint8_t *trial, unsigned *counts, int flags, hipStream_t st) {
   const SearchCall c = {"lsec_search_dev_patterns_rotated", true, n_shift, first_stripe, select, expect, found, trial, counts, flags};
   return search_dev(e, c, devs, nstripes, C, patterns, npatterns, st);
+}
+
+// ---------------------------------------------------------------- the quorum vote over the stored magics
+// lsec_vote_dev / _rotated: the first step of segjerase_read_func (segment/jerasure.c:1383-1462) over device-resident
+// magics and chunks, so that the quorum and stripe_pattern arrays the calls above take are made where they are used.
+// Three launches (ec_vote.h) over 16 bytes per stripe of scratch from the stream-ordered allocator -- zeroed there and
+// freed there, also when a launch fails: the vote of the whole call, the blank scan in ranges of stripes whose tile
+// indices stay 32-bit (lsec_test_set_pattern_split lowers them; skipped without chunks), and the finalize.  The list's
+// masks are one more member of the cache entry lsec_decode_dev_patterns uses for the same list (PatternTable::masks),
+// uploaded at the first vote on a device.  Every refusal names the call; all of them come before the first HIP call.
+// The scan's form that ships is the best measured one (profiles/vote_ab.jsonl): non-temporal loads,
+// tiles of two 16-byte steps per lane;
+// lsec_test_set_vote_form picks another for A/B runs.
+std::atomic<int> g_vote_plain_loads{0}, g_vote_steps{2};
+
+namespace {
+
+struct VoteCall {
+  const char *name;
+  bool rotated;
+  int n_shift;
+  long long first_stripe;
+};
+
+// the table's erasure masks on the current device: uploaded once, cached with the table
+int pattern_masks_dev(PlanExt *e, const PatternTable *ctab, const unsigned long long **out) {
+  int dev = 0;
+  HIP_OK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  PatternTable &tab = *const_cast<PatternTable *>(ctab);  // (a node of the plan's own map, guarded by its mutex)
+  const void *p = tab.dev_masks.find(dev);
+  if (!p && tab.dev_masks.get(dev, tab.masks.data(), sizeof(unsigned long long) * tab.masks.size(), "hipMemcpy(pattern masks)",
+                              nullptr, &p))
+    return -1;
+  *out = static_cast<const unsigned long long *>(p);
+  return 0;
+}
+
+int vote_path(PlanExt *e, const VoteCall &c, const lsec_shard_t *stored, const lsec_shard_t *sh, int nstripes, long long C,
+              const int *patterns, int npatterns, const VoteOut &o, int flags, hipStream_t st) {
+  const char *name = c.name;
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  const int kind = kernel_kind(p->method, p->w);
+  if (kind != KBYTEWISE && kind != KBITSLICED)
+    return fail("%s needs plan kernel 1 (bytewise GF(2^8)) or 2 (bit-sliced GF(2^8)); %s (w=%d) is plan kernel %d", name,
+                JE_method[p->method], p->w, kind);
+  const int k = p->data_strips, m = p->parity_strips, n = k + m;
+  if (k < 1 || k > lsec::kMaxK) return fail("%s: k=%d outside 1..%d", name, k, lsec::kMaxK);
+  if (m < 1 || m > 8) return fail("%s: m=%d outside 1..8", name, m);
+  if (n > lsec::kVoteMaxShards)
+    return fail("%s: k+m=%d exceeds %d (one bit of the outside mask and one lane of the wave per chunk)", name, n, lsec::kVoteMaxShards);
+  if (!stored) return fail("%s: stored is NULL", name);
+  if (nstripes < 0) return fail("%s: nstripes %d is negative", name, nstripes);
+  if (c.rotated && c.n_shift < 0) return fail("%s: n_shift %d is negative", name, c.n_shift);
+  if (c.rotated && c.first_stripe < 0) return fail("%s: first_stripe %lld is negative", name, c.first_stripe);
+  if (patterns) {
+    PatternLists pl;  // the lists' own refusals (pattern_table_dev parses them again)
+    if (named(name, parse_pattern_lists(p, patterns, npatterns, nullptr, 0, pl))) return -1;
+    if (npatterns > kSearchMaxPatterns)
+      return fail("%s: npatterns=%d outside 1..%d (ids[] keeps LSEC_LOCATE_MANY and LSEC_LOCATE_CLEAN past the table)", name,
+                  npatterns, kSearchMaxPatterns);
+  }
+  if (o.ids && !patterns) return fail("%s: ids is given without patterns (there is no list to look the outside set up in)", name);
+  if (sh) {
+    // lsec_check_dev's rule for every chunk the scan can read: an entry whose stored base is NULL is never read
+    for (int i = 0; i < n; ++i) {
+      if (!stored[i].base) continue;
+      if (reinterpret_cast<uintptr_t>(sh[i].base) % 8 != 0)
+        return fail("%s: shard %d: base %p is not a multiple of 8 bytes (lsec_shard_t)", name, i, sh[i].base);
+      if (nstripes > 1 && sh[i].stride % 8 != 0)
+        return fail("%s: shard %d: stride %lld is not a multiple of 8 bytes (lsec_shard_t)", name, i, sh[i].stride);
+    }
+    if (named(name, check_geometry(p, C))) return -1;
+  }
+  if (nstripes > 0 && !o.quorum) return fail("%s: quorum is NULL (4 bytes per stripe, required with nstripes > 0)", name);
+  if (nstripes > 0 && !o.cls) return fail("%s: cls is NULL (1 byte per stripe, required with nstripes > 0)", name);
+  if (reinterpret_cast<uintptr_t>(o.outside) % 8 != 0)
+    return fail("%s: outside %p is not a multiple of 8 bytes (64-bit words)", name, static_cast<const void *>(o.outside));
+  if (reinterpret_cast<uintptr_t>(o.counts) % 4 != 0)
+    return fail("%s: counts %p is not a multiple of 4 bytes (five 32-bit words)", name, static_cast<const void *>(o.counts));
+  if (flags & ~LSEC_VOTE_PARANOID) return fail("%s: unknown flags 0x%x (LSEC_VOTE_PARANOID = 1 is the only one)", name, flags);
+  const unsigned long long *masks = nullptr;
+  if (patterns) {
+    const PatternTable *tab = nullptr;
+    PatternTable::Dev dv;
+    if (named(name, pattern_table_dev(e, patterns, npatterns, nullptr, 0, &tab, &dv)) || named(name, pattern_masks_dev(e, tab, &masks)))
+      return -1;
+  }
+  if (nstripes <= 0) return 0;
+
+  const unsigned long long scratch_bytes = sizeof(lsec::VoteScratch) * static_cast<unsigned long long>(nstripes);
+  lsec::VoteScratch *scratch = nullptr;
+  hipError_t err = hipMallocAsync(reinterpret_cast<void **>(&scratch), scratch_bytes, st);
+  if (err == hipSuccess && (err = hipMemsetAsync(scratch, 0, scratch_bytes, st)) != hipSuccess) (void)hipFreeAsync(scratch, st);
+  if (err != hipSuccess) return fail("%s: the vote's scratch (%llu bytes): %s", name, scratch_bytes, hipGetErrorString(err));
+  int rc = 0;
+  if (o.counts && (err = hipMemsetAsync(o.counts, 0, 5 * sizeof(unsigned), st)) != hipSuccess)
+    rc = fail("%s: zeroing counts: %s", name, hipGetErrorString(err));
+  const bool scans = sh != nullptr && C > 0;
+  if (rc == 0) {
+    lsec::VoteArgs a;
+    std::memset(static_cast<void *>(&a), 0, sizeof(a));
+    a.masks = masks;
+    a.npat = patterns ? static_cast<uint32_t>(npatterns) : 0;
+    a.rot_n = c.rotated ? static_cast<uint32_t>(n) : 0;
+    a.rot_step = c.rotated ? static_cast<uint32_t>(c.n_shift % n) : 0;
+    a.rot0 = c.rotated ? pattern_rot0(n, c.n_shift, c.first_stripe) : 0;
+    a.n = n;
+    a.K = k;
+    a.nstripes = nstripes;
+    a.scan = sh != nullptr;  // (chunks of no bytes are all zero: such a candidate stays blank)
+    a.quorum = o.quorum;
+    a.outside = o.outside;
+    a.scratch = scratch;
+    for (int i = 0; i < n; ++i) a.stored[i] = {reinterpret_cast<uint64_t>(stored[i].base), stored[i].stride};
+    err = lsec::launch_vote(a, st);
+    if (err != hipSuccess) rc = fail("%s: vote kernel launch failed: %s", name, hipGetErrorString(err));
+  }
+  if (rc == 0 && scans) {
+    const int steps = g_vote_steps.load(std::memory_order_relaxed), plain = g_vote_plain_loads.load(std::memory_order_relaxed);
+    lsec::VoteScanArgs a;
+    std::memset(static_cast<void *>(&a), 0, sizeof(a));
+    a.n = n;
+    a.size = C;
+    long long per = std::max(1LL, launch_stripes(C, false, lsec::vote_scan_tile_bytes(steps)) / n);
+    if (const int hook = g_pattern_split.load(std::memory_order_relaxed); hook > 0) per = std::min<long long>(per, hook);
+    rc = for_launches(nstripes, per, [&](long long s0, int ns) {
+      a.nstripes = ns;
+      a.scratch = scratch + s0;
+      // (an entry whose stored base is NULL keeps a zero ref: no stripe of the call is a candidate then)
+      for (int i = 0; i < n; ++i) a.sh[i] = stored[i].base ? shard_from(sh[i], s0) : ShardRef{0, 0};
+      const hipError_t le = lsec::launch_vote_scan(a, plain, steps, st);
+      if (le != hipSuccess) return fail("%s: blank scan kernel launch failed: %s", name, hipGetErrorString(le));
+      return 0;
+    });
+  }
+  if (rc == 0) {
+    err = lsec::launch_vote_finalize(scratch, nstripes, (flags & LSEC_VOTE_PARANOID) ? 1 : 0, patterns ? 1 : 0, o.cls, o.ids, o.counts, st);
+    if (err != hipSuccess) rc = fail("%s: finalize launch failed: %s", name, hipGetErrorString(err));
+  }
+  err = hipFreeAsync(scratch, st);
+  if (err != hipSuccess && rc == 0) rc = fail("%s: freeing the vote's scratch: %s", name, hipGetErrorString(err));
+  return rc;
+}
+
+}  // namespace
+
+int vote_dev(PlanExt *e, const lsec_shard_t *stored, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns,
+             int npatterns, const VoteOut &out, int flags, hipStream_t st) {
+  const VoteCall c = {"lsec_vote_dev", false, 0, 0};
+  return vote_path(e, c, stored, sh, nstripes, C, patterns, npatterns, out, flags, st);
+}
+
+int vote_dev_rotated(PlanExt *e, const lsec_shard_t *stored, const lsec_shard_t *devs, int nstripes, long long C, int n_shift,
+                     long long first_stripe, const int *patterns, int npatterns, const VoteOut &out, int flags, hipStream_t st) {
+  const VoteCall c = {"lsec_vote_dev_rotated", true, n_shift, first_stripe};
+  return vote_path(e, c, stored, devs, nstripes, C, patterns, npatterns, out, flags, st);
 }
 
 // ---------------------------------------------------------------- check / locate, rotated or not
@@ -2555,6 +2719,14 @@ int lsec_test_predict_search_form(int rotated, int plan_kernel, int K, int R, in
 void lsec_test_set_search_form(int cand_outer, int plain_loads) {
   g_search_cand_outer.store(cand_outer ? 1 : 0, std::memory_order_relaxed);
   g_search_plain_loads.store(plain_loads ? 1 : 0, std::memory_order_relaxed);
+}
+
+// Test hook, not in include/: the blank scan's load kind (plain_loads 0: non-temporal; 1: plain) and its tile (steps:
+// 16-byte steps per lane, 2 or 4; anything else: 2) for A/B runs in one process (tools/vote_ab.py).  The results do
+// not depend on either.
+void lsec_test_set_vote_form(int plain_loads, int steps) {
+  g_vote_plain_loads.store(plain_loads ? 1 : 0, std::memory_order_relaxed);
+  g_vote_steps.store(steps == 4 ? 4 : 2, std::memory_order_relaxed);
 }
 
 // Test hook, not in include/ (no GPU): the form (family 12 of the launch record) lsec_decode_magic_dev_patterns and

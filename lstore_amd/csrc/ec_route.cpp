@@ -698,6 +698,27 @@ int lsec_search_dev_patterns_rotated(lio_erasure_plan_t *plan, const lsec_shard_
                                      static_cast<hipStream_t>(stream));
 }
 
+// (the whole ladder is vote_path's: the chunks are optional, and an entry whose stored base is NULL is not validated)
+int lsec_vote_dev(lio_erasure_plan_t *plan, const lsec_shard_t *stored, const lsec_shard_t *shards, int nstripes,
+                  long long block_size, const int *patterns, int npatterns, void *quorum, unsigned char *cls, unsigned char *ids,
+                  unsigned long long *outside, unsigned int *counts, int flags, void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  const VoteOut out = {static_cast<uint8_t *>(quorum), cls, ids, outside, counts};
+  return vote_dev(e, stored, shards, nstripes, block_size, patterns, npatterns, out, flags, static_cast<hipStream_t>(stream));
+}
+
+int lsec_vote_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *stored, const lsec_shard_t *devs, int nstripes,
+                          long long block_size, int n_shift, long long first_stripe, const int *patterns, int npatterns,
+                          void *quorum, unsigned char *cls, unsigned char *ids, unsigned long long *outside,
+                          unsigned int *counts, int flags, void *stream) {
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  const VoteOut out = {static_cast<uint8_t *>(quorum), cls, ids, outside, counts};
+  return vote_dev_rotated(e, stored, devs, nstripes, block_size, n_shift, first_stripe, patterns, npatterns, out, flags,
+                          static_cast<hipStream_t>(stream));
+}
+
 int lsec_check_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
                            int n_shift, long long first_stripe, unsigned int *syndrome, unsigned int *bad_count,
                            void *stream) {

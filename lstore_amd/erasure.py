@@ -88,7 +88,8 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_update_dev_masked_rotated", "lsec_update_magic_dev_masked", "lsec_update_magic_dev_masked_rotated",
            "lsec_decode_magic_dev_patterns", "lsec_decode_magic_dev_rotated",
            "lsec_check_magic_dev", "lsec_check_magic_dev_rotated", "lsec_encode_magic_dev_rotated",
-           "lsec_search_dev_patterns", "lsec_search_dev_patterns_rotated")
+           "lsec_search_dev_patterns", "lsec_search_dev_patterns_rotated",
+           "lsec_vote_dev", "lsec_vote_dev_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -96,6 +97,9 @@ READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
 LOCATE_CLEAN, LOCATE_MANY, LOCATE_REPAIR = 0xFF, 0xFE, 1
 # lsec_search_dev_patterns: the flag (found[] takes the two sentinels of located[])
 SEARCH_REPAIR = 1
+# lsec_vote_dev: the classes of cls[] and the flag (ids[] takes the two sentinels of located[])
+VOTE_OK, VOTE_DEGRADED, VOTE_BLANK, VOTE_LOST = range(4)
+VOTE_PARANOID = 1
 # lsec_check_magic_dev: the bits of bad[]
 SCRUB_BAD_PARITY, SCRUB_BAD_MAGIC = 1, 2
 # lsec_update_dev: the flag
@@ -185,6 +189,13 @@ def lib():
     L.lsec_test_predict_search_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.lsec_test_set_search_form.argtypes = [C.c_int, C.c_int]
     L.lsec_test_set_search_form.restype = None
+    L.lsec_vote_dev.argtypes = [P, C.POINTER(ShardRef), C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.lsec_vote_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int,
+                                        C.c_longlong, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.lsec_test_set_vote_form.argtypes = [C.c_int, C.c_int]
+    L.lsec_test_set_vote_form.restype = None
     L.lsec_check_magic_dev.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
     L.lsec_check_magic_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
@@ -720,6 +731,35 @@ class Plan:
                                       0 if counts is None else counts.data_ptr(), SEARCH_REPAIR if repair else 0,
                                       _stream_handle(stream))
 
+    def vote_dev_refs(self, stored, refs, nstripes: int, block_size: int, patterns, quorum_ptr: int, cls_ptr: int,
+                      ids_ptr: int = 0, outside_ptr: int = 0, counts_ptr: int = 0, flags: int = 0, stream: int = 0) -> None:
+        """lsec_vote_dev: the quorum vote over the k+m stored magics of every stripe.  stored: k+m (base, stride), the 4
+        bytes at base + s*stride are chunk i's stored magic (no alignment; base 0: unreadable; None: NULL).  refs: the
+        chunks, read by the blank scan alone (None: no scan, no VOTE_BLANK).  patterns: a sequence of erasure lists of
+        logical chunk ids to look each stripe's outside set up in, or None.  quorum_ptr (4 bytes per stripe), cls_ptr (1
+        byte per stripe: VOTE_OK / _DEGRADED / _BLANK / _LOST); ids_ptr (1 byte per stripe, usable as stripe_pattern),
+        outside_ptr (aligned uint64 per stripe) and counts_ptr (five aligned uint32) are optional (0).  flags:
+        VOTE_PARANOID gives OK stripes a pattern id too."""
+        pats = None if patterns is None else list(patterns)
+        _check(lib().lsec_vote_dev(self._p, None if stored is None else self.shard_refs(stored),
+                                   None if refs is None else self.shard_refs(refs), nstripes, block_size,
+                                   None if pats is None else _pattern_array(pats), 0 if pats is None else len(pats),
+                                   quorum_ptr or None, cls_ptr or None, ids_ptr or None, outside_ptr or None,
+                                   counts_ptr or None, flags, stream), "lsec_vote_dev")
+
+    def vote_dev_rotated_refs(self, stored, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int, patterns,
+                              quorum_ptr: int, cls_ptr: int, ids_ptr: int = 0, outside_ptr: int = 0, counts_ptr: int = 0,
+                              flags: int = 0, stream: int = 0) -> None:
+        """lsec_vote_dev_rotated: vote_dev_refs over the k+m PHYSICAL devices of a rotated LUN (stored[i], refs[i]: device
+        i, as check_dev_rotated_refs).  Patterns, ids and outside are those of the logical view."""
+        pats = None if patterns is None else list(patterns)
+        _check(lib().lsec_vote_dev_rotated(self._p, None if stored is None else self.shard_refs(stored),
+                                           None if refs is None else self.shard_refs(refs), nstripes, block_size, n_shift,
+                                           first_stripe, None if pats is None else _pattern_array(pats),
+                                           0 if pats is None else len(pats), quorum_ptr or None, cls_ptr or None,
+                                           ids_ptr or None, outside_ptr or None, counts_ptr or None, flags, stream),
+               "lsec_vote_dev_rotated")
+
     def check_dev_refs(self, refs, nstripes: int, block_size: int, syndrome_ptr: int, bad_count_ptr: int = 0,
                        stream: int = 0) -> None:
         """lsec_check_dev: one-pass parity check.  syndrome_ptr: device address of nstripes uint32 words,
@@ -1143,6 +1183,12 @@ def set_search_form(cand_outer: bool = False, plain_loads: bool = True) -> None:
     kind (plain_loads: plain, not non-temporal) for A/B runs; the defaults are what ships, and the results do not depend
     on either."""
     lib().lsec_test_set_search_form(1 if cand_outer else 0, 1 if plain_loads else 0)
+
+
+def set_vote_form(plain_loads: bool = False, steps: int = 2) -> None:
+    """Test hook: the load kind of the vote's blank scan (plain_loads: plain, not non-temporal) and its tile (steps: 2 or
+    4 16-byte steps per lane) for A/B runs; the defaults are what ships, and the results do not depend on either."""
+    lib().lsec_test_set_vote_form(1 if plain_loads else 0, steps)
 
 
 def predict_check_magic_form(rotated: bool, plan_kernel: int, k: int, rows: int, packet: int = 0, block_size: int = 0) -> Form:
