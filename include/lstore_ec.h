@@ -222,6 +222,63 @@ int lsec_decode_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *
                                   void *magic, const void *expect, unsigned char *bad,
                                   unsigned int *bad_count, void *stream);
 
+/* The patterned decodes over the physical devices of a rotated LUN: lsec_decode_dev_patterns and
+ * lsec_decode_magic_dev_patterns for a caller who holds device images, not logical shards -- the layout
+ * lsec_segment_write produces.  They are the middle step of the device-resident read of a rotated LUN:
+ * the `ids` of lsec_vote_dev_rotated (or the `found` of lsec_search_dev_patterns_rotated, the `located`
+ * of lsec_locate_dev_rotated) are their stripe_pattern, and the `bad` of the magic call is the `select`
+ * of lsec_search_dev_patterns_rotated.  Purely additive too: the version stays 3, a caller detects the
+ * calls by their symbols.
+ *
+ * Devices and patterns
+ * - devs, n_shift and first_stripe mean exactly what they mean for lsec_check_dev_rotated: devs[i]
+ *   (i < k+m) is PHYSICAL device i, rot_s = ((first_stripe + s) * n_shift) mod (k+m).  n_shift >= k+m is
+ *   taken mod k+m; n_shift < 0 and first_stripe < 0 are refused; first_stripe may be anything up to
+ *   2^63 - 1.
+ * - `patterns`, npatterns and stripe_pattern are those of lsec_decode_dev_patterns: erasure lists of
+ *   LOGICAL chunk ids back to back, each ended by -1, and one byte per stripe in device memory.
+ * - Logical chunk c of stripe s is read from devs[(c - rot_s) mod (k+m)] and, if it is erased, rebuilt
+ *   there.  The entry of an unreadable device points at memory that receives the rebuilt chunks, as for
+ *   lsec_decode_dev_rotated.  All k+m entries of devs are validated.
+ * Plain call
+ * - The bytes left on the devices are exactly those lsec_decode_dev_patterns leaves for the logical view
+ *   of each stripe with that stripe's pattern.  Only erased slots are written.  A stripe with an empty
+ *   pattern, a RAID4 parity-only pattern or an id >= npatterns is neither read nor written.
+ * - n_shift == 0 behaves exactly as lsec_decode_dev_patterns over devs.
+ * - Limits: those of lsec_decode_dev_patterns -- plan kernels 1 and 2, k <= 64, k + m <= 128, at most 8
+ *   erasures per pattern, 1 <= npatterns <= 256.
+ * Magic call
+ * - Everything lsec_decode_magic_dev_patterns specifies holds for the logical view: magic[s] is zlib's
+ *   adler32 over the k+m chunks in LOGICAL order as they lie after the decode (the rotation never enters
+ *   a position weight); an empty pattern checksums without writing, k+m reads; for an id >= npatterns no
+ *   chunk is read or written, the magic word is neither read nor written and bad[s] = 0.
+ * - expect, bad and bad_count behave as in lsec_decode_magic_dev_patterns.
+ * - Scratch: 16 bytes per stripe from the stream-ordered allocator (hipMallocAsync on `stream`), zeroed
+ *   there and freed there, also when a launch fails.
+ * - Limits: those of lsec_decode_magic_dev_patterns -- k <= 64, 1 <= m <= 8.  n_shift == 0 behaves
+ *   exactly as lsec_decode_magic_dev_patterns.
+ * Tables
+ * - Both calls use the cache entry lsec_decode_dev_patterns uses for the same list (the magic call adds
+ *   the unused-survivor records), so vote, decode, search and repair over one list share one upload and
+ *   a repeated call does no matrix work and no upload.  nstripes == 0 validates the arguments and
+ *   prepares the tables as lsec_decode_dev_patterns does; all device pointers may then be NULL.
+ * Refusals
+ * - The ladder of lsec_decode_dev_patterns / lsec_decode_magic_dev_patterns in their order, with a
+ *   negative n_shift and then a negative first_stripe directly behind a negative nstripes.  Each returns
+ *   -1 with a message for lsec_last_error that names the call that was made, and nothing is enqueued:
+ *   every argument check comes before the first HIP call.  There is no fallback.
+ * Enqueued on `stream`; return without synchronising.  0 / -1. */
+int lsec_decode_dev_patterns_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                                     long long block_size, int n_shift, long long first_stripe,
+                                     const int *patterns, int npatterns,
+                                     const unsigned char *stripe_pattern, void *stream);
+int lsec_decode_magic_dev_patterns_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes,
+                                           long long block_size, int n_shift, long long first_stripe,
+                                           const int *patterns, int npatterns,
+                                           const unsigned char *stripe_pattern, void *magic,
+                                           const void *expect, unsigned char *bad,
+                                           unsigned int *bad_count, void *stream);
+
 /* The search for the erasure set that fits the magic, one pass: what LStore does when a stripe's magic
  * does not match and the first guess fails (jerase_brute_recovery / jerase_brute_recurse,
  * segment/jerasure.c:271-339).  That routine tries erasure combinations in order and stops at the
@@ -276,7 +333,8 @@ int lsec_decode_magic_dev_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *
  * - devs, n_shift and first_stripe mean what they mean for lsec_check_dev_rotated.  Patterns, found
  *   and trial are logical: logical chunk c of stripe s is read from devs[(c - rot_s) mod (k+m)] and,
  *   with the flag, rebuilt there.  n_shift == 0 behaves exactly as the unrotated call; n_shift < 0
- *   and first_stripe < 0 are refused.
+ *   and first_stripe < 0 are refused.  found is the stripe_pattern of lsec_decode_dev_patterns_rotated
+ *   and lsec_decode_magic_dev_patterns_rotated over the same devices and list.
  * Plans and limits
  * - lsec_plan_kernel 1 and 2, k <= 64, 1 <= m <= 8.  Layout, alignment and block_size rules are those
  *   of lsec_decode_dev.  The outputs must not overlap one another or the shards.
@@ -346,7 +404,8 @@ int lsec_search_dev_patterns_rotated(lio_erasure_plan_t *plan, const lsec_shard_
  *     LSEC_VOTE_DEGRADED  otherwise.
  *   This is step 1 of lsec_segment_read, with one difference: an unreadable chunk never shadows a readable
  *   group of the same size (it matters only for k = 1).
- * - `ids`: optional; nstripes bytes, usable as stripe_pattern of the patterned calls with the same list.
+ * - `ids`: optional; nstripes bytes, usable as stripe_pattern of the patterned calls with the same list
+ *   (the rotated vote's: of lsec_decode_dev_patterns_rotated and lsec_decode_magic_dev_patterns_rotated).
  *     DEGRADED: the lowest p whose erasure set equals the outside set, LSEC_LOCATE_MANY if the list has none;
  *     OK with LSEC_VOTE_PARANOID: the same lookup (the outside set is then empty or parity-only: the paranoid
  *       read verifies the stripe and rebuilds the parity outside the quorum);

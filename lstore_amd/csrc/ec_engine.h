@@ -298,13 +298,19 @@ int update_magic_dev_masked_rotated(PlanExt *e, const lsec_shard_t *devs, int ns
 // stripes that do not share an erasure pattern, one launch per 32-bit range of tiles
 int build_pattern_table(PlanExt *e, const int *patterns, int npatterns, const int *lost, int n_shift, PatternTable &tab);
 uint32_t pattern_rot0(int n, int n_shift, long long first_stripe);
-int decode_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
-                        const unsigned char *stripe_pattern, hipStream_t st);
+// rot: the shards are the k+m devices of a rotated LUN and the patterns stay logical (lsec_*_dev_patterns_rotated),
+// or null: logical shards.  name: in front of every refusal, or null (lsec_decode_dev_patterns: its messages as they are)
+struct PatternRot {
+  int n_shift;
+  long long first_stripe;
+};
+int decode_dev_patterns(PlanExt *e, const char *name, const PatternRot *rot, const lsec_shard_t *sh, int nstripes, long long C,
+                        const int *patterns, int npatterns, const unsigned char *stripe_pattern, hipStream_t st);
 int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
                        long long first_stripe, hipStream_t st);
 // the same decodes, and magic[s] = adler32 of stripe s's k+m logical chunks as the decode leaves them (a stripe whose
 // pattern id is >= npatterns is skipped); expect / bad / bad_count: the comparison with the quorum magics, all optional
-int named(const char *name, int rc);  // rc != 0: lsec_last_error's message gets "<name>: " in front; returns rc
+int named(const char *name, int rc);  // rc != 0: lsec_last_error's message gets "<name>: " in front (name null: stays); returns rc
 int decode_magic_limits(const lio_erasure_plan_t *p, const char *name);  // plan kernels 1 and 2, k <= 64, 1 <= m <= 8
 struct MagicCheck {
   uint8_t *magic;
@@ -312,8 +318,9 @@ struct MagicCheck {
   uint8_t *bad;
   unsigned *bad_count;
 };
-int decode_magic_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
-                              const unsigned char *stripe_pattern, const MagicCheck &mc, hipStream_t st);
+int decode_magic_dev_patterns(PlanExt *e, const char *name, const PatternRot *rot, const lsec_shard_t *sh, int nstripes,
+                              long long C, const int *patterns, int npatterns, const unsigned char *stripe_pattern,
+                              const MagicCheck &mc, hipStream_t st);
 int decode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
                              long long first_stripe, const MagicCheck &mc, hipStream_t st);
 // every candidate pattern tried on every selected stripe, nothing written: found[s] = the first whose rebuilt stripe

@@ -224,6 +224,15 @@ struct PatternSearchRotArgs : PatternSearchArgs {};  // the type only selects th
 static_assert(sizeof(PatternSearchArgs) == sizeof(PatternMagicArgs) + 16, "PatternSearchArgs layout");
 static_assert(sizeof(PatternSearchRotArgs) < 4096, "PatternSearchArgs: under the 4 KiB of kernel arguments");
 
+// The MG kernels over the k+m devices of a rotated LUN with a logical pattern per stripe
+// (lsec_decode_magic_dev_patterns_rotated): the logical table of lsec_decode_dev_patterns, a stripe_pattern,
+// and rot0 / rot_step / rot_n = nshards as PatternRotArgs has them, so that logical chunk c of stripe s is
+// sh[(c - rot_s) mod nshards].  The magic ids are the selections themselves.  The type only selects the
+// kernels (PatShards); the launch shapes are a constant of their own (patmagicrot_bytewise_form).
+struct PatternMagicRotArgs : PatternMagicArgs {};
+hipError_t launch_pattern_magic_rot_bytewise(const PatternMagicRotArgs &a, int rmax, hipStream_t stream);
+hipError_t launch_pattern_magic_rot_bitsliced(const PatternMagicRotArgs &a, int rmax, hipStream_t stream);
+
 // As launch_pattern_magic_*, over npat candidates per stripe: nstripes * npat * (tiles per chunk) < 2^31,
 // stripe_pattern null; the rotated struct with rot_n = nshards.  The launch shapes are the MG forms' own
 // (patsearch_bytewise_form).
@@ -571,7 +580,7 @@ hipError_t launch_update_magic_finalize(const unsigned long long *acc, const uns
 // functions record the form at the one place where the template arguments are known; the record
 // is the calling thread's, holds the launches since launch_record_reset() in order (the engine
 // resets it on entry to each of those calls) and costs a few host stores per launch.
-enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic, kFormPatMagic, kFormChkMagic, kFormChkMagicRot, kFormEncMagicRot, kFormPatSearch, kFormPatSearchRot };
+enum LaunchFamily { kFormChk = 1, kFormLoc, kFormChkRot, kFormLocRot, kFormPat, kFormPatRot, kFormUpd, kFormEncRot, kFormUpdRot, kFormUpdMask, kFormUpdMaskMagic, kFormPatMagic, kFormChkMagic, kFormChkMagicRot, kFormEncMagicRot, kFormPatSearch, kFormPatSearchRot, kFormPatMagicRot };
 struct LaunchForm {
   int family, sliced, R, KC, IT, VW, BF, DW;
 };
@@ -589,6 +598,8 @@ bool predict_masked_launch(bool sliced, int K, int R, int packet, int dw_pref, L
 bool predict_masked_magic_launch(bool sliced, int K, int R, int packet, int dw_pref, LaunchForm *out);
 // and for the patterned decode with the magic (kFormPatMagic; R: the table's rmax, at least 1)
 bool predict_pattern_magic_launch(bool sliced, int K, int R, int packet, LaunchForm *out);
+// and for that decode over rotating shards with a stripe_pattern (kFormPatMagicRot)
+bool predict_pattern_magic_rot_launch(bool sliced, int K, int R, int packet, LaunchForm *out);
 // and for the search (kFormPatSearch, or kFormPatSearchRot with `rotated`; R: the table's rmax, at least 1)
 bool predict_pattern_search_launch(bool rotated, bool sliced, int K, int R, int packet, LaunchForm *out);
 // and for the check with the magic (kFormChkMagic, or kFormChkMagicRot with `rotated`)

@@ -428,6 +428,32 @@ hipError_t launch_pattern_magic_bitsliced(const PatternMagicArgs &a, int rmax, h
 namespace {
 bool rot_fields_ok(uint32_t rot0, uint32_t rot_step, uint32_t rot_n, int nshards);
 
+// the rotated MG launch: a logical table with a stripe_pattern, and the rotation of all nshards devices
+bool pattern_magic_rot_args_ok(const PatternMagicRotArgs &a, int rmax) {
+  return pattern_magic_args_ok(a, rmax) && a.stripe_pattern && rot_fields_ok(a.rot0, a.rot_step, a.rot_n, a.nshards);
+}
+}  // namespace
+
+hipError_t launch_pattern_magic_rot_bytewise(const PatternMagicRotArgs &a, int rmax, hipStream_t st) {
+  if (!pattern_magic_rot_args_ok(a, rmax)) return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const BwForm f = patmagicrot_bytewise_form(a.K, rmax);
+  const int grid = tile_grid(BwShape{f.it, f.vw, f.bf}.tile_bytes(), a.size, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(rmax, [&](auto r) { return dispatch_patmagicrot_bytewise<decltype(r)::value>(a, st, grid); });
+}
+
+hipError_t launch_pattern_magic_rot_bitsliced(const PatternMagicRotArgs &a, int rmax, hipStream_t st) {
+  if (!pattern_magic_rot_args_ok(a, rmax) || a.packet <= 0 || a.packet % 4 != 0 || a.size % (8LL * a.packet) != 0)
+    return hipErrorInvalidValue;
+  if (a.nstripes <= 0 || a.size == 0) return hipSuccess;
+  const int grid = tile_grid(kBlock * 4, a.size / 8, a.nstripes);
+  if (!grid) return hipErrorInvalidValue;
+  return by_r(rmax, [&](auto r) { return dispatch_patmagicrot_bitsliced<decltype(r)::value>(a, st, grid); });
+}
+
+namespace {
+
 // tiles of the launch (one per stripe, candidate and piece), or 0: none, or more than 32-bit indices hold
 template <typename Args>
 int pattern_search_grid(const Args &a, int rmax, uint64_t tile_bytes, int64_t bytes) {
@@ -910,6 +936,18 @@ bool predict_pattern_magic_launch(bool sliced, int K, int R, int packet, LaunchF
   }
   const BwForm f = patmagic_bytewise_form(K, R);
   *out = LaunchForm{kFormPatMagic, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
+  return true;
+}
+
+bool predict_pattern_magic_rot_launch(bool sliced, int K, int R, int packet, LaunchForm *out) {
+  if (K < 1 || K > kMaxK || R < 1 || R > kPatMaxOut) return false;
+  if (sliced) {
+    if (packet <= 0 || packet % 4 != 0) return false;
+    *out = LaunchForm{kFormPatMagicRot, 1, R, 0, 0, 0, 0, 1};
+    return true;
+  }
+  const BwForm f = patmagicrot_bytewise_form(K, R);
+  *out = LaunchForm{kFormPatMagicRot, 0, R, f.kc, f.it, f.vw, f.bf ? 1 : 0, 0};
   return true;
 }
 

@@ -1442,11 +1442,12 @@ __device__ __forceinline__ uint32_t rot_back(const Args &a, uint32_t s) {
 }
 
 // Where a patterned tile takes a shard ref from: the record's selection itself (PatternArgs), or
-// the physical device holding that logical chunk in stripe s (PatternRotArgs and PatternSearchRotArgs,
-// ec_kernels.h).
+// the physical device holding that logical chunk in stripe s (PatternRotArgs, PatternSearchRotArgs and
+// PatternMagicRotArgs, ec_kernels.h).
 template <typename Args>
 struct PatShards {
-  static constexpr bool kRot = std::is_same<Args, PatternRotArgs>::value || std::is_same<Args, PatternSearchRotArgs>::value;
+  static constexpr bool kRot = std::is_same<Args, PatternRotArgs>::value || std::is_same<Args, PatternSearchRotArgs>::value ||
+                               std::is_same<Args, PatternMagicRotArgs>::value;
   const Args &a;
   uint32_t back = 0;
   __device__ __forceinline__ PatShards(const Args &a_, uint32_t s) : a(a_) {
@@ -1470,7 +1471,8 @@ struct PatShards {
 // Instantiated for the one-row kernel only (dispatch_pat_bytewise).  Args: PatternArgs, or
 // PatternRotArgs for the rotated single-erasure repair (the same tile body up to PatShards).
 //
-// MG (lsec_decode_magic_dev_patterns / _rotated; Args: PatternMagicArgs): the tile also sums the
+// MG (lsec_decode_magic_dev_patterns / _rotated / _patterns_rotated; Args: PatternMagicArgs, or PatternMagicRotArgs
+// for logical patterns over rotating shards): the tile also sums the
 // stripe's adler32 magic over all of its chunks as the decode leaves them.  One MagicLane takes every
 // survivor the tile loads, every row it rebuilds (r < nout) and the pattern's unused survivors
 // (PatUnused, loaded here for the checksum alone), each at its LOGICAL chunk id (pat_logical), and the
@@ -1763,6 +1765,17 @@ __global__ __launch_bounds__(kBlock) void k_patmagic_bytewise(PatternMagicArgs a
       a, reinterpret_cast<ConstUnused *>(reinterpret_cast<uintptr_t>(a.unused)), a.magic_acc, red);
 }
 
+// The MG tile over the devices of a rotated LUN with a logical pattern per stripe
+// (lsec_decode_magic_dev_patterns_rotated): every selection becomes a physical device through PatShards,
+// whose rotation stays in scalar registers (rot_back), and the magic ids are the selections themselves
+// (pat_logical with a stripe_pattern).  The stores are on.
+template <int R, int KC, int IT, int VW, bool BF>
+__global__ __launch_bounds__(kBlock) void k_patmagicrot_bytewise(PatternMagicRotArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  pat_bytewise_tiles<R, KC, IT, VW, BF, true>(
+      a, reinterpret_cast<ConstUnused *>(reinterpret_cast<uintptr_t>(a.unused)), a.magic_acc, red);
+}
+
 // k_gf8_bitsliced's lanes (one dword of packet-column space per lane) under a pattern record.
 // MG as in pat_bytewise_tiles: the lanes past the end of a ragged last tile then skip the loads and
 // the stores, but still join the tile's reduction (as k_gf8_bitsliced's do).  SR, NT as there.
@@ -1875,6 +1888,12 @@ __global__ __launch_bounds__(kBlock) void k_patmagic_bitsliced(PatternMagicArgs 
   pat_bitsliced_tiles<R, true>(a, reinterpret_cast<ConstUnused *>(reinterpret_cast<uintptr_t>(a.unused)), a.magic_acc, red);
 }
 
+template <int R>
+__global__ __launch_bounds__(kBlock) void k_patmagicrot_bitsliced(PatternMagicRotArgs a) {
+  __shared__ uint32_t red[kBlock / 64];
+  pat_bitsliced_tiles<R, true>(a, reinterpret_cast<ConstUnused *>(reinterpret_cast<uintptr_t>(a.unused)), a.magic_acc, red);
+}
+
 // The patterned bytewise kernel takes the automatic shape (bw_auto) of the table's row count and
 // K.  The one-row kernel has fixed-K forms for K = 6 and 10; tables of two or more rows run with
 // K at run time: their fixed-K forms, with every input's 2 x 16 B in flight on top of the
@@ -1975,6 +1994,38 @@ template <int R>
 hipError_t dispatch_patmagic_bitsliced(const PatternMagicArgs &a, hipStream_t st, int grid) {
   record_launch({kFormPatMagic, 1, R, 0, 0, 0, 0, 1});
   return launch_tiled(&k_patmagic_bitsliced<R>, grid, st, a);
+}
+
+// The MG forms over rotating shards (lsec_decode_magic_dev_patterns_rotated; DESIGN.md 3.7.3 has their
+// registers beside the unrotated ones'): the MG forms' own shapes, through a constant of their own.
+constexpr BwForm patmagicrot_bytewise_form(int K, int R) { return patmagic_bytewise_form(K, R); }
+
+template <int R, int KC, int IT, int VW, bool BF>
+hipError_t patmagicrot_kernel(const PatternMagicRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormPatMagicRot, 0, R, KC, IT, VW, BF ? 1 : 0, 0});
+  return launch_tiled(&k_patmagicrot_bytewise<R, KC, IT, VW, BF>, grid, st, a);
+}
+
+template <int R>
+hipError_t dispatch_patmagicrot_bytewise(const PatternMagicRotArgs &a, hipStream_t st, int grid) {
+  const BwForm f = patmagicrot_bytewise_form(a.K, R);
+  if constexpr (R == 1) {
+    constexpr BwShape sh = bw_auto(0, 1);
+    switch (f.kc) {
+      case 6: return patmagicrot_kernel<1, 6, sh.it, sh.vw, sh.bf>(a, st, grid);
+      case 10: return patmagicrot_kernel<1, 10, sh.it, sh.vw, sh.bf>(a, st, grid);
+      default: return patmagicrot_kernel<1, 0, sh.it, sh.vw, sh.bf>(a, st, grid);
+    }
+  } else {
+    if (f.it == 1) return patmagicrot_kernel<R, 0, 1, 4, true>(a, st, grid);
+    return patmagicrot_kernel<R, 0, 2, 4, true>(a, st, grid);
+  }
+}
+
+template <int R>
+hipError_t dispatch_patmagicrot_bitsliced(const PatternMagicRotArgs &a, hipStream_t st, int grid) {
+  record_launch({kFormPatMagicRot, 1, R, 0, 0, 0, 0, 1});
+  return launch_tiled(&k_patmagicrot_bitsliced<R>, grid, st, a);
 }
 
 // The search (lsec_search_dev_patterns / _rotated): the MG tile bodies in their SR mode, in the MG forms'
@@ -2086,6 +2137,15 @@ LSEC_DECLARE_PATROT_ROWS_R(5) LSEC_DECLARE_PATROT_ROWS_R(6) LSEC_DECLARE_PATROT_
 #ifndef LSEC_INSTANTIATING_PATMAGIC
 LSEC_DECLARE_PATMAGIC_R(1) LSEC_DECLARE_PATMAGIC_R(2) LSEC_DECLARE_PATMAGIC_R(3) LSEC_DECLARE_PATMAGIC_R(4)
 LSEC_DECLARE_PATMAGIC_R(5) LSEC_DECLARE_PATMAGIC_R(6) LSEC_DECLARE_PATMAGIC_R(7) LSEC_DECLARE_PATMAGIC_R(8)
+#endif
+
+// instantiated per R in ec_patterns_magic_rot_inst.hip
+#define LSEC_DECLARE_PATMAGICROT_R(RR)                                                                         \
+  extern template hipError_t dispatch_patmagicrot_bytewise<RR>(const PatternMagicRotArgs &, hipStream_t, int); \
+  extern template hipError_t dispatch_patmagicrot_bitsliced<RR>(const PatternMagicRotArgs &, hipStream_t, int);
+#ifndef LSEC_INSTANTIATING_PATMAGICROT
+LSEC_DECLARE_PATMAGICROT_R(1) LSEC_DECLARE_PATMAGICROT_R(2) LSEC_DECLARE_PATMAGICROT_R(3) LSEC_DECLARE_PATMAGICROT_R(4)
+LSEC_DECLARE_PATMAGICROT_R(5) LSEC_DECLARE_PATMAGICROT_R(6) LSEC_DECLARE_PATMAGICROT_R(7) LSEC_DECLARE_PATMAGICROT_R(8)
 #endif
 
 // instantiated per R in ec_patterns_inst.hip

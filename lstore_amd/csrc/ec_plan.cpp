@@ -994,18 +994,19 @@ uint32_t rot0_from(uint32_t rot0, uint32_t rot_step, int n, long long s0) {
 }
 
 // The launches of a patterned call, split so that tile indices stay 32-bit (as enqueue_apply).  A
-// stripe's pattern id comes from stripe_pattern or, without one, from its rotation.  rotated_repair:
-// kRepairLocate, the repair behind a rotated locate, whose table is the k+m single erasures of the
+// stripe's pattern id comes from stripe_pattern or, without one, from its rotation.  rot_mode:
+// kRotSingles, the repair behind a rotated locate, whose table is the k+m single erasures of the
 // logical chunks and whose kernel turns each selection into a physical device by the stripe's
-// rotation; kRepairSearch, the one behind a rotated search: the same over any logical table.
-enum { kRepairNone = 0, kRepairLocate, kRepairSearch };
+// rotation; kRotLogical, the same over any logical table with a stripe_pattern: the repair behind a
+// rotated search and lsec_decode_dev_patterns_rotated.
+enum { kRotNone = 0, kRotSingles, kRotLogical };
 int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::Dev &dv, const lsec_shard_t *sh, int nstripes,
-                     long long C, const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, int rotated_repair,
+                     long long C, const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, int rot_mode,
                      hipStream_t st) {
   const lio_erasure_plan_t *p = &e->pub;
   const int n = p->data_strips + p->parity_strips;
   if (nstripes <= 0 || C == 0 || tab.rmax == 0) return 0;  // rmax 0: every pattern is empty
-  const bool rotates = rotated_repair || !stripe_pattern;
+  const bool rotates = rot_mode || !stripe_pattern;
   lsec::PatternRotArgs a;  // (PatternArgs, which the type's rotated launches take too)
   std::memset(static_cast<void *>(&a), 0, sizeof(a));
   a.recs = dv.recs;
@@ -1024,10 +1025,10 @@ int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::De
     for (int i = 0; i < n; ++i) a.sh[i] = shard_from(sh[i], s0);
     a.stripe_pattern = stripe_pattern ? stripe_pattern + s0 : nullptr;
     a.rot0 = rotates ? rot0_from(rot0, rot_step, n, s0) : 0;
-    if (rotated_repair == kRepairSearch) {
+    if (rot_mode == kRotLogical) {
       const hipError_t err = sliced ? lsec::launch_pattern_rot_rows_bitsliced(a, tab.rmax, st) : lsec::launch_pattern_rot_rows_bytewise(a, tab.rmax, st);
-      if (err != hipSuccess) return fail("rotated repair kernel launch failed: %s", hipGetErrorString(err));
-    } else if (rotated_repair) {
+      if (err != hipSuccess) return fail("rotated pattern kernel launch failed: %s", hipGetErrorString(err));
+    } else if (rot_mode) {
       const hipError_t err = sliced ? lsec::launch_pattern_rot_bitsliced(a, st) : lsec::launch_pattern_rot_bytewise(a, st);
       if (err != hipSuccess) return fail("rotated repair kernel launch failed: %s", hipGetErrorString(err));
     } else {
@@ -1038,20 +1039,36 @@ int enqueue_patterns(PlanExt *e, const PatternTable &tab, const PatternTable::De
   });
 }
 
-}  // namespace
-
-int decode_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
-                        const unsigned char *stripe_pattern, hipStream_t st) {
-  lsec::launch_record_reset();  // (lsec_test_launch_record)
-  lio_erasure_plan_t *p = &e->pub;
+// The rungs the calls with a pattern list and a stripe_pattern share, in their order (the rotation's two only for a
+// call over rotated devices); the message is the caller's to name.
+int patterns_call_args(const lio_erasure_plan_t *p, const PatternRot *rot, int nstripes, long long C, const int *patterns,
+                       const unsigned char *stripe_pattern) {
   if (!patterns) return fail("patterns is NULL");
   if (nstripes < 0) return fail("nstripes %d is negative", nstripes);
+  if (rot && rot->n_shift < 0) return fail("n_shift %d is negative", rot->n_shift);
+  if (rot && rot->first_stripe < 0) return fail("first_stripe %lld is negative", rot->first_stripe);
   if (nstripes > 0 && !stripe_pattern) return fail("stripe_pattern is NULL");
   if (pattern_limits(p) || check_geometry(p, C)) return -1;
+  return 0;
+}
+
+}  // namespace
+
+// lsec_decode_dev_patterns (rot null, name null: its messages stand as they are) and lsec_decode_dev_patterns_rotated:
+// one path, the rotation a parameter.  Rotated, the launches are the k_patrot_* kernels of the table's row count over
+// the same logical table, which is what the repair behind a rotated search runs.
+int decode_dev_patterns(PlanExt *e, const char *name, const PatternRot *rot, const lsec_shard_t *sh, int nstripes, long long C,
+                        const int *patterns, int npatterns, const unsigned char *stripe_pattern, hipStream_t st) {
+  lsec::launch_record_reset();  // (lsec_test_launch_record)
+  lio_erasure_plan_t *p = &e->pub;
+  if (named(name, patterns_call_args(p, rot, nstripes, C, patterns, stripe_pattern))) return -1;
   const PatternTable *tab = nullptr;
   PatternTable::Dev dv;
-  if (pattern_table_dev(e, patterns, npatterns, nullptr, 0, &tab, &dv)) return -1;
-  return enqueue_patterns(e, *tab, dv, sh, nstripes, C, stripe_pattern, 0, 0, kRepairNone, st);
+  if (named(name, pattern_table_dev(e, patterns, npatterns, nullptr, 0, &tab, &dv))) return -1;
+  const int n = p->data_strips + p->parity_strips;
+  const uint32_t rot0 = rot ? pattern_rot0(n, rot->n_shift, rot->first_stripe) : 0;
+  const uint32_t rot_step = rot ? static_cast<uint32_t>(rot->n_shift % n) : 0;
+  return named(name, enqueue_patterns(e, *tab, dv, sh, nstripes, C, stripe_pattern, rot0, rot_step, rot ? kRotLogical : kRotNone, st));
 }
 
 int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
@@ -1068,11 +1085,11 @@ int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
   if (pattern_table_dev(e, nullptr, 0, lost, n_shift, &tab, &dv)) return -1;
   const int n = p->data_strips + p->parity_strips;
   return enqueue_patterns(e, *tab, dv, devs, nstripes, C, nullptr, pattern_rot0(n, n_shift, first_stripe),
-                          static_cast<uint32_t>(n_shift % n), kRepairNone, st);
+                          static_cast<uint32_t>(n_shift % n), kRotNone, st);
 }
 
 // ---------------------------------------------------------------- patterned decode with the stripe magics
-// lsec_decode_magic_dev_patterns / _rotated: the plain calls' table, launches and split, with the MG
+// lsec_decode_magic_dev_patterns / _rotated / _patterns_rotated: the plain calls' table, launches and split, with the MG
 // kernels (ec_kernels.h, PatternMagicArgs) over 16 bytes per stripe of accumulators from the
 // stream-ordered allocator -- zeroed before the first launch, advancing by 2 * s0 words per launch,
 // freed on the stream -- and one finalize launch behind the tile launches.  The table is the plain
@@ -1080,7 +1097,7 @@ int decode_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long 
 // on a device and cached with it.  Every refusal names the call; all of them come before the first
 // HIP call.
 int named(const char *name, int rc) {
-  if (rc) {
+  if (rc && name) {
     const std::string why = tl_err;  // the shared rule's message, behind the call's name
     fail("%s: %s", name, why.c_str());
   }
@@ -1126,17 +1143,20 @@ int pattern_unused_dev(PlanExt *e, const PatternTable *ctab, const lsec::PatUnus
 }
 
 // enqueue_patterns for the MG kernels.  A table whose patterns are all empty still launches (one row:
-// its tiles only checksum).
+// its tiles only checksum).  rot_logical: the shards are the devices of a rotated LUN and the table is
+// a logical one with a stripe_pattern (the k_patmagicrot_* kernels); without a stripe_pattern the
+// table's own records rotate (k_patmagic_*), as in enqueue_patterns.
 int enqueue_patterns_magic(PlanExt *e, const char *name, const PatternTable &tab, const PatternTable::Dev &dv,
                            const lsec::PatUnused *unused, const lsec_shard_t *sh, int nstripes, long long C,
-                           const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, const MagicCheck &mc,
-                           hipStream_t st) {
+                           const unsigned char *stripe_pattern, uint32_t rot0, uint32_t rot_step, bool rot_logical,
+                           const MagicCheck &mc, hipStream_t st) {
   const lio_erasure_plan_t *p = &e->pub;
   const int n = p->data_strips + p->parity_strips;
   if (nstripes <= 0) return 0;
-  const bool rotates = !stripe_pattern;
+  if (rot_logical && !stripe_pattern) return fail("%s: a rotated logical table needs a stripe_pattern", name);
+  const bool rotates = rot_logical || !stripe_pattern;  // (rot_n stays 0 otherwise: nothing divides by it)
   const int rmax = std::max(1, tab.rmax);
-  lsec::PatternMagicArgs a;
+  lsec::PatternMagicRotArgs a;  // (PatternMagicArgs, which the other launches take)
   std::memset(static_cast<void *>(&a), 0, sizeof(a));
   a.recs = dv.recs;
   a.cells = dv.cells;
@@ -1163,7 +1183,9 @@ int enqueue_patterns_magic(PlanExt *e, const char *name, const PatternTable &tab
       a.stripe_pattern = stripe_pattern ? stripe_pattern + s0 : nullptr;
       a.rot0 = rotates ? rot0_from(rot0, rot_step, n, s0) : 0;
       a.magic_acc = acc + 2 * s0;
-      const hipError_t le = sliced ? lsec::launch_pattern_magic_bitsliced(a, rmax, st) : lsec::launch_pattern_magic_bytewise(a, rmax, st);
+      hipError_t le;
+      if (rot_logical) le = sliced ? lsec::launch_pattern_magic_rot_bitsliced(a, rmax, st) : lsec::launch_pattern_magic_rot_bytewise(a, rmax, st);
+      else le = sliced ? lsec::launch_pattern_magic_bitsliced(a, rmax, st) : lsec::launch_pattern_magic_bytewise(a, rmax, st);
       if (le != hipSuccess) return fail("%s: kernel launch failed: %s", name, hipGetErrorString(le));
       return 0;
     });
@@ -1179,15 +1201,14 @@ int enqueue_patterns_magic(PlanExt *e, const char *name, const PatternTable &tab
 
 }  // namespace
 
-int decode_magic_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, long long C, const int *patterns, int npatterns,
-                              const unsigned char *stripe_pattern, const MagicCheck &mc, hipStream_t st) {
-  static const char name[] = "lsec_decode_magic_dev_patterns";
+// lsec_decode_magic_dev_patterns (rot null) and lsec_decode_magic_dev_patterns_rotated: one path, the rotation a
+// parameter.
+int decode_magic_dev_patterns(PlanExt *e, const char *name, const PatternRot *rot, const lsec_shard_t *sh, int nstripes,
+                              long long C, const int *patterns, int npatterns, const unsigned char *stripe_pattern,
+                              const MagicCheck &mc, hipStream_t st) {
   lsec::launch_record_reset();  // (lsec_test_launch_record)
   lio_erasure_plan_t *p = &e->pub;
-  if (!patterns) return fail("%s: patterns is NULL", name);
-  if (nstripes < 0) return fail("%s: nstripes %d is negative", name, nstripes);
-  if (nstripes > 0 && !stripe_pattern) return fail("%s: stripe_pattern is NULL", name);
-  if (named(name, pattern_limits(p) || check_geometry(p, C) ? -1 : 0)) return -1;
+  if (named(name, patterns_call_args(p, rot, nstripes, C, patterns, stripe_pattern))) return -1;
   {
     PatternLists pl;  // the lists' own refusals, ahead of the magic's (pattern_table_dev parses them again)
     if (named(name, parse_pattern_lists(p, patterns, npatterns, nullptr, 0, pl))) return -1;
@@ -1198,7 +1219,10 @@ int decode_magic_dev_patterns(PlanExt *e, const lsec_shard_t *sh, int nstripes, 
   const lsec::PatUnused *unused = nullptr;
   if (named(name, pattern_table_dev(e, patterns, npatterns, nullptr, 0, &tab, &dv)) || named(name, pattern_unused_dev(e, tab, &unused)))
     return -1;
-  return enqueue_patterns_magic(e, name, *tab, dv, unused, sh, nstripes, C, stripe_pattern, 0, 0, mc, st);
+  const int n = p->data_strips + p->parity_strips;
+  const uint32_t rot0 = rot ? pattern_rot0(n, rot->n_shift, rot->first_stripe) : 0;
+  const uint32_t rot_step = rot ? static_cast<uint32_t>(rot->n_shift % n) : 0;
+  return enqueue_patterns_magic(e, name, *tab, dv, unused, sh, nstripes, C, stripe_pattern, rot0, rot_step, rot != nullptr, mc, st);
 }
 
 int decode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes, long long C, const int *lost, int n_shift,
@@ -1223,7 +1247,7 @@ int decode_magic_dev_rotated(PlanExt *e, const lsec_shard_t *devs, int nstripes,
     return -1;
   const int n = p->data_strips + p->parity_strips;
   return enqueue_patterns_magic(e, name, *tab, dv, unused, devs, nstripes, C, nullptr, pattern_rot0(n, n_shift, first_stripe),
-                                static_cast<uint32_t>(n_shift % n), mc, st);
+                                static_cast<uint32_t>(n_shift % n), false, mc, st);
 }
 
 // ---------------------------------------------------------------- the search for the erasure set that fits the magic
@@ -1348,7 +1372,7 @@ int search_dev(PlanExt *e, const SearchCall &c, const lsec_shard_t *sh, int nstr
   if (err != hipSuccess && rc == 0) rc = fail("%s: freeing the magic accumulators: %s", name, hipGetErrorString(err));
   if (rc || !(c.flags & LSEC_SEARCH_REPAIR)) return rc;
   // every found stripe rebuilt in place: found[s] < npatterns names its pattern, both sentinels leave a stripe alone
-  return named(name, enqueue_patterns(e, *tab, dv, sh, nstripes, C, c.found, rot0, rot_step, c.rotated ? kRepairSearch : kRepairNone, st));
+  return named(name, enqueue_patterns(e, *tab, dv, sh, nstripes, C, c.found, rot0, rot_step, c.rotated ? kRotLogical : kRotNone, st));
 }
 
 }  // namespace
@@ -1780,7 +1804,7 @@ int scrub_dev(PlanExt *e, const ScrubCall &c, const lsec_shard_t *sh, int nstrip
                                                                       nstripes, k, R, rot0, rot_step, static_cast<uint32_t>(n), st)
                                    : lsec::launch_locate_finalize(syndrome, c.hyp, c.located, c.counts, nstripes, k, R, st);
   if (err != hipSuccess) return fail("%slocate finalize launch failed: %s", c.rotated ? "rotated " : "", hipGetErrorString(err));
-  if (repair) return enqueue_patterns(e, *tab, dv, sh, nstripes, C, c.located, rot0, rot_step, c.rotated ? kRepairLocate : kRepairNone, st);
+  if (repair) return enqueue_patterns(e, *tab, dv, sh, nstripes, C, c.located, rot0, rot_step, c.rotated ? kRotSingles : kRotNone, st);
   return 0;
 }
 
@@ -2739,6 +2763,21 @@ int lsec_test_predict_pattern_magic_form(int plan_kernel, int K, int R, int pack
   lsec::LaunchForm f;
   if (!lsec::predict_pattern_magic_launch(plan_kernel == KBITSLICED, K, R, packet, &f))
     return fail("lsec_test_predict_pattern_magic_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
+  const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
+  std::memcpy(form, v, sizeof(v));
+  return 0;
+}
+
+// Test hook, not in include/ (no GPU): the form (family 18 of the launch record) lsec_decode_magic_dev_patterns_rotated
+// launches for a plan of kernel 1 or 2 with K inputs and a table of at most R erasures per pattern (a table of empty
+// patterns launches the one-row form), from the function the dispatch calls.
+int lsec_test_predict_pattern_magic_rot_form(int plan_kernel, int K, int R, int packet, int *form) {
+  if (!form) return fail("lsec_test_predict_pattern_magic_rot_form: NULL output");
+  if (plan_kernel != KBYTEWISE && plan_kernel != KBITSLICED)
+    return fail("lsec_test_predict_pattern_magic_rot_form: plan kernel %d", plan_kernel);
+  lsec::LaunchForm f;
+  if (!lsec::predict_pattern_magic_rot_launch(plan_kernel == KBITSLICED, K, R, packet, &f))
+    return fail("lsec_test_predict_pattern_magic_rot_form: no kernel for K=%d R=%d packet=%d", K, R, packet);
   const int v[8] = {f.family, f.sliced, f.R, f.KC, f.IT, f.VW, f.BF, f.DW};
   std::memcpy(form, v, sizeof(v));
   return 0;

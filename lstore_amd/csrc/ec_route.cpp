@@ -627,7 +627,21 @@ int lsec_decode_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t *shard
   if (!e) return fail("not an lstore_ec plan");
   if (!shards) return fail("shards is NULL");
   if (check_shards(plan, shards, nstripes)) return -1;
-  return decode_dev_patterns(e, shards, nstripes, block_size, patterns, npatterns, stripe_pattern,
+  return decode_dev_patterns(e, nullptr, nullptr, shards, nstripes, block_size, patterns, npatterns, stripe_pattern,
+                             static_cast<hipStream_t>(stream));
+}
+
+// (lsec_decode_dev_patterns' ladder behind the call's name, the rotation's two rungs behind the negative nstripes)
+int lsec_decode_dev_patterns_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                                     int n_shift, long long first_stripe, const int *patterns, int npatterns,
+                                     const unsigned char *stripe_pattern, void *stream) {
+  static const char name[] = "lsec_decode_dev_patterns_rotated";
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (!devs) return fail("%s: devs is NULL", name);
+  if (named(name, check_shards(plan, devs, nstripes))) return -1;
+  const PatternRot rot = {n_shift, first_stripe};
+  return decode_dev_patterns(e, name, &rot, devs, nstripes, block_size, patterns, npatterns, stripe_pattern,
                              static_cast<hipStream_t>(stream));
 }
 
@@ -651,7 +665,23 @@ int lsec_decode_magic_dev_patterns(lio_erasure_plan_t *plan, const lsec_shard_t 
   if (!shards) return fail("%s: shards is NULL", name);
   if (named(name, check_shards(plan, shards, nstripes))) return -1;
   const MagicCheck mc = {static_cast<uint8_t *>(magic), static_cast<const uint8_t *>(expect), bad, bad_count};
-  return decode_magic_dev_patterns(e, shards, nstripes, block_size, patterns, npatterns, stripe_pattern, mc,
+  return decode_magic_dev_patterns(e, name, nullptr, shards, nstripes, block_size, patterns, npatterns, stripe_pattern, mc,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int lsec_decode_magic_dev_patterns_rotated(lio_erasure_plan_t *plan, const lsec_shard_t *devs, int nstripes, long long block_size,
+                                           int n_shift, long long first_stripe, const int *patterns, int npatterns,
+                                           const unsigned char *stripe_pattern, void *magic, const void *expect,
+                                           unsigned char *bad, unsigned int *bad_count, void *stream) {
+  static const char name[] = "lsec_decode_magic_dev_patterns_rotated";
+  PlanExt *e = ext_of(plan);
+  if (!e) return fail("not an lstore_ec plan");
+  if (decode_magic_limits(plan, name)) return -1;
+  if (!devs) return fail("%s: devs is NULL", name);
+  if (named(name, check_shards(plan, devs, nstripes))) return -1;
+  const MagicCheck mc = {static_cast<uint8_t *>(magic), static_cast<const uint8_t *>(expect), bad, bad_count};
+  const PatternRot rot = {n_shift, first_stripe};
+  return decode_magic_dev_patterns(e, name, &rot, devs, nstripes, block_size, patterns, npatterns, stripe_pattern, mc,
                                    static_cast<hipStream_t>(stream));
 }
 

@@ -89,7 +89,8 @@ EXPORTS = ("nearest_prime", "et_method_type", "et_new_plan", "et_generate_plan",
            "lsec_decode_magic_dev_patterns", "lsec_decode_magic_dev_rotated",
            "lsec_check_magic_dev", "lsec_check_magic_dev_rotated", "lsec_encode_magic_dev_rotated",
            "lsec_search_dev_patterns", "lsec_search_dev_patterns_rotated",
-           "lsec_vote_dev", "lsec_vote_dev_rotated")
+           "lsec_vote_dev", "lsec_vote_dev_rotated",
+           "lsec_decode_dev_patterns_rotated", "lsec_decode_magic_dev_patterns_rotated")
 
 # read / inspect flags and stripe states (include/lstore_ec.h)
 READ_PARANOID, MAGIC_LEGACY, INSPECT_FIX, MAX_DEVS = 1, 2, 4, 256
@@ -181,6 +182,12 @@ def lib():
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lsec_decode_magic_dev_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
                                                 C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lsec_decode_dev_patterns_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
+                                                   C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p]
+    L.lsec_decode_magic_dev_patterns_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
+                                                         C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lsec_test_predict_pattern_magic_rot_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.lsec_search_dev_patterns.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.POINTER(C.c_int), C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.lsec_search_dev_patterns_rotated.argtypes = [P, C.POINTER(ShardRef), C.c_int, C.c_longlong, C.c_int, C.c_longlong,
@@ -683,6 +690,31 @@ class Plan:
                                             0 if expect is None else expect.data_ptr(), 0 if bad is None else bad.data_ptr(),
                                             0 if bad_count is None else bad_count.data_ptr(), _stream_handle(stream))
 
+    def decode_dev_patterns_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
+                                         patterns, stripe_pattern_ptr: int, stream: int = 0) -> None:
+        """lsec_decode_dev_patterns_rotated: decode_dev_patterns_refs over the k+m PHYSICAL devices of a rotated LUN
+        (refs[i]: device i, as check_dev_rotated_refs).  The patterns and stripe_pattern are those of the logical view:
+        logical chunk c of stripe s is read from, and if erased rebuilt on, the device that holds it in that stripe.
+        refs None / pointers 0 with nstripes == 0: only prepare the tables."""
+        patterns = list(patterns)
+        _check(lib().lsec_decode_dev_patterns_rotated(self._p, None if refs is None else self.shard_refs(refs), nstripes,
+                                                      block_size, n_shift, first_stripe, _pattern_array(patterns),
+                                                      len(patterns), stripe_pattern_ptr or None, stream),
+               "lsec_decode_dev_patterns_rotated")
+
+    def decode_magic_dev_patterns_rotated_refs(self, refs, nstripes: int, block_size: int, n_shift: int, first_stripe: int,
+                                               patterns, stripe_pattern_ptr: int, magic_ptr: int, expect_ptr: int = 0,
+                                               bad_ptr: int = 0, bad_count_ptr: int = 0, stream: int = 0) -> None:
+        """lsec_decode_magic_dev_patterns_rotated: decode_dev_patterns_rotated_refs with the magics, expect, bad and
+        bad_count of decode_magic_dev_patterns_refs; the magics are over the LOGICAL stripes, whatever the rotation."""
+        patterns = list(patterns)
+        _check(lib().lsec_decode_magic_dev_patterns_rotated(self._p, None if refs is None else self.shard_refs(refs),
+                                                            nstripes, block_size, n_shift, first_stripe,
+                                                            _pattern_array(patterns), len(patterns),
+                                                            stripe_pattern_ptr or None, magic_ptr or None, expect_ptr or None,
+                                                            bad_ptr or None, bad_count_ptr or None, stream),
+               "lsec_decode_magic_dev_patterns_rotated")
+
     def search_dev_patterns_refs(self, refs, nstripes: int, block_size: int, patterns, expect_ptr: int, found_ptr: int,
                                  select_ptr: int = 0, trial_ptr: int = 0, counts_ptr: int = 0, flags: int = 0,
                                  stream: int = 0) -> None:
@@ -1113,9 +1145,14 @@ ENCMAGIC_FAMILIES = ("encmagicrot",)
 SEARCH_FAMILIES = ("patsearch", "patsearchrot")
 
 
+# and behind those (SEARCH_FAMILIES stays as it is too): family number 18, the patterned decode that leaves the magics
+# over the devices of a rotated LUN with a logical pattern per stripe
+PATMAGICROT_FAMILIES = ("patmagicrot",)
+
+
 def _form(v) -> Form:
     return Form((FORM_FAMILIES + MASKED_FAMILIES + MAGIC_FAMILIES + PATMAGIC_FAMILIES + CHKMAGIC_FAMILIES +
-                 ENCMAGIC_FAMILIES + SEARCH_FAMILIES)[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
+                 ENCMAGIC_FAMILIES + SEARCH_FAMILIES + PATMAGICROT_FAMILIES)[v[0] - 1], bool(v[1]), *(int(x) for x in v[2:8]))
 
 
 def launch_record() -> list:
@@ -1165,6 +1202,16 @@ def predict_pattern_magic_form(plan_kernel: int, k: int, rows: int, packet: int 
     out = (C.c_int * 8)()
     _check(lib().lsec_test_predict_pattern_magic_form(plan_kernel, k, rows, packet, out),
            "lsec_test_predict_pattern_magic_form")
+    return _form(out)
+
+
+def predict_pattern_magic_rot_form(plan_kernel: int, k: int, rows: int, packet: int = 0) -> Form:
+    """Test hook (no GPU): the Form ("patmagicrot") decode_magic_dev_patterns_rotated_refs launches for a plan of
+    kernel 1 or 2 with k inputs and a table of at most `rows` erasures per pattern (a table of empty patterns: 1),
+    asked of the function the dispatch itself calls."""
+    out = (C.c_int * 8)()
+    _check(lib().lsec_test_predict_pattern_magic_rot_form(plan_kernel, k, rows, packet, out),
+           "lsec_test_predict_pattern_magic_rot_form")
     return _form(out)
 
 
